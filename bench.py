@@ -6,7 +6,7 @@ A "step" is one matvec = set_weights (upward pass) + evaluate at the sources (do
 pass), exactly what one FGMRES `matvec` closure call does in the reference
 (ferreus_rbf/src/rbf.rs:1357-1364), on weights already resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 without a launcher (WORLD_SIZE unset): this process starts N rank processes itself --
@@ -15,7 +15,12 @@ rank holds the whole tree and owns a contiguous Morton range of target leaves (s
 the total work is one matvec over all points); the owned potentials are exchanged with one RCCL
 all-gather over xGMI per step.
 
-Rank 0 prints ONE JSON line of under 4 KB (`compact_line`): the contract's keys, `roofline` of the dominant kernel,
+A plain run sets up, warms up, times the K steps and prints ONE JSON line of the contract's keys (metric, value, unit,
+n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config) -- nothing else.
+`--dump-outputs DIR` writes what the last timed step computed to DIR (see `dump_outputs`); the inputs are seeded, so two
+builds can be compared output for output.  Everything below runs only with `--full`.
+
+With `--full`, rank 0 prints ONE JSON line of under 4 KB (`compact_line`): the contract's keys, `roofline` of the dominant kernel,
 `cpu_baseline` (N = 1), `dense_rows_rel_err` (32 rows of the dense sum computed in plain torch on rank 0 after the
 exchange), `source_hash`, and per extra configuration only its step time, dense-row error and the dominant kernel's
 roofline kernel / bound / frac.  Everything else -- per-phase rooflines, instruction-issue figures, tree statistics,
@@ -109,13 +114,13 @@ def parse():
     ap.add_argument("--nrhs", type=int, default=1)
     ap.add_argument("--base-range", type=float, default=1.0)
     ap.add_argument("--total-sill", type=float, default=1.0)
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="with --full: the CPU port's rate (N = 1)")
     ap.add_argument("--dropin", default="auto", choices=["auto", "off"],
-                    help="auto: with the default workload at N = 1 also time the drop-in boundary on host buffers "
+                    help="with --full, auto: with the default workload at N = 1 also time the drop-in boundary on host buffers "
                          "(patched and unchanged caller; detail file + one small entry of the line)")
     ap.add_argument("--cpu-points", type=int, default=0, help="points of the CPU sample (0: points/8)")
     ap.add_argument("--configs", default="auto",
-                    help="comma list of: auto (with the default workload: the other single-GPU configs at N = 1, "
+                    help="with --full, a comma list of: auto (with the default workload: the other single-GPU configs at N = 1, "
                          "config 5 = 40M Spheroidal3 at N > 1), off, solve (config 3 end to end: 10M thin-plate spline "
                          "FGMRES + Schwarz, N = 1), extensions (the labelled extensions, N = 1), config5 (config 5 at "
                          "N > 1 whatever the headline workload)")
@@ -131,8 +136,20 @@ def parse():
                     help="with --inprocess: explicit device list, e.g. 0,0,0,0 = four logical parts on device 0 (a functional "
                          "rehearsal on a one-GPU box, never a scaling number); default 0..gpus-1")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where the full record goes (the stdout line is the compact one)")
-    return ap.parse_args()
+                    help="with --full: where the full record goes (the stdout line is the compact one)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: phase times and rooflines, FP64 microbenchmarks, dense-row "
+                         "checks, the partition check (N > 1), the drop-in's host-buffer timings, the other configurations "
+                         "(--configs), the CPU baseline (--cpu-baseline) and the detail file.  Without it a run sets up, warms "
+                         "up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (the K x N potentials) to DIR/*.npy; "
+                         "a fixed, seeded column sample when the whole would exceed 64 MB")
+    args = ap.parse_args()
+    extra = {c.strip() for c in args.configs.split(",") if c.strip()} - {"auto", "off"}
+    if extra and not args.full:
+        ap.error(f"--configs {','.join(sorted(extra))} needs --full")
+    return args
 
 
 # --------------------------------------------------------------------------- N > 1 without a launcher
@@ -546,8 +563,9 @@ def phase_roofline(stats, N, K, order, kernel, per_step_ms, valu_lane_rate=None)
     return out
 
 
-def time_matvecs(torch, dist, tree, w, out, steps, warmup, world, pm, stream):
-    """W untimed + exactly K timed steps between barrier + synchronize; returns (seconds, phases, counts)."""
+def time_matvecs(torch, dist, tree, w, out, steps, warmup, world, pm, stream, profile=True):
+    """W untimed + exactly K timed steps between barrier + synchronize; returns (seconds, phases, counts).  Without
+    `profile` no phase events are recorded and phases / counts are None."""
     N, K = w.shape[1], w.shape[0]
 
     def step():
@@ -569,8 +587,9 @@ def time_matvecs(torch, dist, tree, w, out, steps, warmup, world, pm, stream):
     if world > 1:
         dist.barrier()
     sync()
-    tree.set_profiling(True)
-    tree.phase_ms(reset=True)
+    if profile:
+        tree.set_profiling(True)
+        tree.phase_ms(reset=True)
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -579,9 +598,50 @@ def time_matvecs(torch, dist, tree, w, out, steps, warmup, world, pm, stream):
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if not profile:
+        return elapsed, None, None
     phases, counts = tree.phase_ms(counts=True)
     tree.set_profiling(False)
     return elapsed, phases, counts
+
+
+# --dump-outputs: at most this many bytes of array data (the .npy headers stay well inside the 64 MB allowed)
+DUMP_BYTES = 60 << 20
+
+
+def dump_outputs(directory, out):
+    """What the timed path computed in its last step -- the K x N potentials a caller of bbfmm_matvec_device receives --
+    as DIR/potentials.npy (float64).  When the whole would exceed DUMP_BYTES: the same seeded choice of point columns
+    every run (it depends only on N and K), the potentials at them, and their indices as DIR/potentials_columns.npy
+    (float64, exact below 2^53)."""
+    os.makedirs(directory, exist_ok=True)
+    y = out.detach().cpu().numpy().astype(np.float64, copy=False)
+    K, N = y.shape
+    if y.nbytes > DUMP_BYTES:
+        m = DUMP_BYTES // (8 * (K + 1))
+        cols = np.sort(np.random.default_rng(7).choice(N, m, replace=False))
+        y = y[:, cols]
+        np.save(os.path.join(directory, "potentials_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(directory, "potentials.npy"), np.ascontiguousarray(y))
+
+
+def headline_line(args, world, steps, elapsed, parallelism):
+    """The contract's keys of the result line, as the plain and the --full run print them."""
+    N, K = args.points, args.nrhs
+    return {
+        "metric": "BBFMM matvecs/s", "value": steps / elapsed, "unit": "matvecs/s", "n_gpus": world,
+        "steps": steps, "warmup": args.warmup, "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{N} uniform 3D points, {args.kernel}, order {args.order}, {K} rhs, adaptive sparse tree, "
+                               f"ACA eps=1e-{args.order}, set_weights + evaluate at the sources",
+                   "points": N, "kernel": args.kernel, "order": args.order, "nrhs": K, "parallelism": parallelism},
+    }
+
+
+def write_line(line, stdout_fd):
+    """A plain run's result line (the contract's keys only) to the real stdout."""
+    sys.stdout.flush()
+    os.write(stdout_fd, (json.dumps(line) + "\n").encode())
 
 
 def dense_rows_err(torch, dev, cfg_kernel, br, sill, pts, w, out, rows=32):
@@ -877,13 +937,24 @@ def main_inprocess(args):
     for _ in range(args.warmup):
         tree.matvec_device(w.data_ptr(), N, K, out.data_ptr(), N, sync=False)
     sync()
-    tree.set_profiling(True)
-    tree.phase_ms(reset=True)
+    if args.full:
+        tree.set_profiling(True)
+        tree.phase_ms(reset=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         tree.matvec_device(w.data_ptr(), N, K, out.data_ptr(), N, sync=False)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    parallelism = (f"ONE process, device group {devices}: slot exchange of the coarse multipoles by peer copies, "
+                   "owned blocks back to the first device (device-resident) / to the host (host buffers)"
+                   + ("; LOGICAL parts on one device: a functional rehearsal, never a scaling number" if logical else ""))
+    entry = "inprocess (one process, one handle over the devices; not the default one-process-per-GPU line)"
+    if not args.full:
+        line = headline_line(args, len(set(devices)), args.steps, elapsed, parallelism)
+        line["entry"] = entry
+        return write_line(line, real_stdout)
     parts = []
     for g in range(G):
         ms, cnt = tree.part_phase_ms(g)
@@ -915,18 +986,10 @@ def main_inprocess(args):
     dominant, roofline = roofline_of(stats, N, K, args.kernel, per_launch, G, None, None)
     roofline["part"] = slow
     line = {
-        "metric": "BBFMM matvecs/s", "value": args.steps / elapsed, "unit": "matvecs/s", "n_gpus": len(set(devices)),
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "entry": "inprocess (one process, one handle over the devices; not the default one-process-per-GPU line)",
+        **headline_line(args, len(set(devices)), args.steps, elapsed, parallelism),
+        "entry": entry,
         "value_host_buffers": 1e3 / host_ms, "ms_per_step_host_buffers": host_ms,
         "host_vs_device_resident_rel_diff": host_vs_device,
-        "config": {"workload": f"{N} uniform 3D points, {args.kernel}, order {args.order}, {K} rhs, adaptive sparse tree, "
-                               f"ACA eps=1e-{args.order}, set_weights + evaluate at the sources",
-                   "points": N, "kernel": args.kernel, "order": args.order, "nrhs": K,
-                   "parallelism": f"ONE process, device group {devices}: slot exchange of the coarse multipoles by peer copies, "
-                                  "owned blocks back to the first device (device-resident) / to the host (host buffers)"
-                                  + ("; LOGICAL parts on one device: a functional rehearsal, never a scaling number" if logical else "")},
         "roofline": roofline, "dense_rows_rel_err": err, "dense_rows": 32,
         "phase_ms_per_step_per_part": parts, "part_sum_ms": sums,
         "tree": {"depth": stats.depth, "cells": stats.n_cells, "leaves": stats.n_leaves, "build_s_all_parts": t_build},
@@ -1018,18 +1081,30 @@ def main():
         from ferreus_rbf_rs_amd.distributed import PartitionedMatvec
         tree.set_partition(rank, world)
         pm = PartitionedMatvec(tree, N, K, dev)   # all-reduce of the coarse multipoles + all-gather of the owned rows
-        assert pm.check_partition(), "partition does not cover the targets exactly once"
+        if args.full:
+            assert pm.check_partition(), "partition does not cover the targets exactly once"
 
     stream = torch.cuda.ExternalStream(tree.stream(), device=dev)
-    elapsed, phases, counts = time_matvecs(torch, dist, tree, w, out, args.steps, args.warmup, world, pm, stream)
+    elapsed, phases, counts = time_matvecs(torch, dist, tree, w, out, args.steps, args.warmup, world, pm, stream,
+                                           profile=args.full)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.exchange == "rccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:                # every rank holds the whole result after the all-gather
+        dump_outputs(args.dump_outputs, out)
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = args.steps / elapsed                     # whole-job matvecs/s (one matvec spans all ranks)
     default_workload = (N, args.kernel, args.order, K) == (10_000_000, "LinearRbf", 7, 1)
+    parallelism = (f"target-subtree partition x{world}: all-reduce of {pm.count * 8 * K / 1e6:.1f} MB "
+                   f"coarse multipoles + all-gather of owned potentials, {args.exchange}") if world > 1 else "single GPU"
+
+    if not args.full:                                # a plain run: the headline figure and nothing else
+        if rank == 0:
+            write_line(headline_line(args, world, args.steps, elapsed, parallelism), real_stdout)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     line = None
     valu_lane_rate = None
@@ -1066,17 +1141,7 @@ def main():
                 roofline["counters_from"] = cj["file"]
         compulsory_bytes = N * (16 * 3 + 16 * K) + 4 * C * n * 8 * K
         line = {
-            "metric": "BBFMM matvecs/s", "value": value, "unit": "matvecs/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{N} uniform 3D points, {args.kernel}, order {args.order}, "
-                                   f"{K} rhs, adaptive sparse tree, ACA eps=1e-{args.order}, "
-                                   "set_weights + evaluate at the sources",
-                       "points": N, "kernel": args.kernel, "order": args.order, "nrhs": K,
-                       "parallelism": (f"target-subtree partition x{world}: all-reduce of {pm.count * 8 * K / 1e6:.1f} MB "
-                                       f"coarse multipoles + all-gather of owned potentials, {args.exchange}")
-                       if world > 1 else "single GPU"},
+            **headline_line(args, world, args.steps, elapsed, parallelism),
             "roofline": roofline,
             "achieved_hbm_gbps_compulsory": compulsory_bytes / (elapsed / args.steps) * 1e-9,
             "phase_ms_per_step": {k: phases[k] / args.steps for k in phases},

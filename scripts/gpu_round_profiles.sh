@@ -1,35 +1,36 @@
 #!/bin/bash
 # One GPU job that produces every measurement the bench line quotes, named by round:
-#   bash scripts/gpu_round_profiles.sh r02_b          (run through gpurun; outputs under gpurun_out/, copy to profiles/)
-#  1. python bench.py (default: headline + the other single-GPU configs + cpu_baseline)      -> <tag>_bench.json (the <4 KB line)
+#   bash scripts/gpu_round_profiles.sh r02_b          (outputs under $OUT, default bench_out/; copy what is kept to profiles/)
+#  1. python bench.py --full (headline + the other single-GPU configs + cpu_baseline)       -> <tag>_bench.json (the <4 KB line)
 #                                                                                              + <tag>_bench_detail.json (full record)
 #  2. rocprofv3 --kernel-trace --stats of the same command (headline only)                    -> <tag>_kernel_stats.csv
 #  3. PMC passes, one counter / derived metric per pass, no tracing domains besides kernel-trace:
 #     FETCH_SIZE, WRITE_SIZE (HBM-side bytes; FETCH_SIZE x2 on gfx950 for 16-B/lane reads, KiB units),
 #     MfmaUtil, MfmaFlopsF64 (matrix pipe), VALUBusy, VALUUtilization (near field)            -> <tag>_counters.json (+ .txt)
 #     The JSON carries bench.py's source_hash: the bench only quotes counters taken on the sources it runs.
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-ROOT=$GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$ROOT/bench_out}          # where the results land (set OUT to collect them elsewhere)
+cd "$ROOT"; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)
 TAG=${1:-r04_final}
-python3 bench.py --steps 20 --warmup 5 --detail-file gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-wc -c gpurun_out/${TAG}_bench.json
-grep -v "bench detail" gpurun_out/${TAG}_bench.err | tail -2; cut -c1-400 gpurun_out/${TAG}_bench.json
+python3 bench.py --full --steps 20 --warmup 5 --detail-file $OUT/${TAG}_bench_detail.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+wc -c $OUT/${TAG}_bench.json
+grep -v "bench detail" $OUT/${TAG}_bench.err | tail -2; cut -c1-400 $OUT/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
-rm -rf $ROOT/gpurun_out/prof_$TAG
-rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/prof_$TAG -- python3 $ROOT/bench.py --steps 10 --warmup 2 --cpu-baseline off --configs off --dropin off > $ROOT/gpurun_out/${TAG}_bench_under_rocprof.json 2>$ROOT/gpurun_out/prof_${TAG}.err
-cp $ROOT/gpurun_out/prof_$TAG/*/*_kernel_stats.csv $ROOT/gpurun_out/${TAG}_kernel_stats.csv
-head -12 $ROOT/gpurun_out/${TAG}_kernel_stats.csv | cut -c1-150
+rm -rf $OUT/prof_$TAG
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python3 $ROOT/bench.py --steps 10 --warmup 2 --cpu-baseline off --configs off --dropin off > $OUT/${TAG}_bench_under_rocprof.json 2>$OUT/prof_${TAG}.err
+cp $OUT/prof_$TAG/*/*_kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
+head -12 $OUT/${TAG}_kernel_stats.csv | cut -c1-150
 for c in FETCH_SIZE WRITE_SIZE MfmaUtil MfmaFlopsF64 VALUBusy VALUUtilization; do
-  rm -rf $ROOT/gpurun_out/pmc_$c
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $ROOT/gpurun_out/pmc_$c -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-baseline off --configs off --dropin off > $ROOT/gpurun_out/pmc_$c.txt 2>&1
+  rm -rf $OUT/pmc_$c
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$c -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-baseline off --configs off --dropin off > $OUT/pmc_$c.txt 2>&1
 done
 cd $ROOT
-python3 - "$TAG" <<'PY'
+ROOT="$ROOT" OUT="$OUT" python3 - "$TAG" <<'PY'
 import csv, glob, collections, os, json, sys
-sys.path.insert(0, os.environ['GRAFT_REPO_ROOT'])
+sys.path.insert(0, os.environ['ROOT'])
 import bench
 tag = sys.argv[1]
-root = os.environ['GRAFT_REPO_ROOT'] + '/gpurun_out'
+root = os.environ['OUT']
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for c in ('FETCH_SIZE', 'WRITE_SIZE', 'MfmaUtil', 'MfmaFlopsF64', 'VALUBusy', 'VALUUtilization'):
     for f in glob.glob(root + '/pmc_%s/*/*_counter_collection.csv' % c):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Extracts the integer tables the reference ships for this path into tests/golden/reference_tables.json.
+"""Extracts the integer tables the reference ships for this path into tests/golden/reference_tables.json, and its
+SHA-256 into reference_tables.json.sha256.
 
 Run in the build container (needs /root/reference; the GPU box has only the JSON):
     python tests/golden/make_reference_tables.py
@@ -15,6 +16,7 @@ These are the only bit-exact vectors the reference holds for the BBFMM path (SUR
 (oracle/bbfmm_oracle.py) and the product (csrc/morton.hpp) replace the lookup tables by bit arithmetic and
 are tested against them in tests/test_reference_tables.py.
 """
+import hashlib
 import json
 import os
 import re
@@ -76,6 +78,11 @@ def main():
     with open(path, "w") as f:
         json.dump(out, f, separators=(",", ":"), sort_keys=True)
         f.write("\n")
+    # the digest of what was extracted: tests/test_reference_tables.py holds the committed file to it without the reference
+    with open(path, "rb") as f:
+        digest = hashlib.sha256(f.read()).hexdigest()
+    with open(path + ".sha256", "w") as f:
+        f.write(f"{digest}  reference_tables.json\n")
     print(path, {k: (len(v) if isinstance(v, list) else v) for k, v in consts.items()})
     return 0
 

@@ -218,3 +218,37 @@ def test_full_size_cpu_figure_is_the_newest_committed_run(tmp_path, monkeypatch)
     assert got["matvecs_per_s_full_size"] == 0.0905 and got["file"].endswith("r05_cpu_port_full_10M.json")
     real = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r05_cpu_port_full_10M.json")))
     assert 0.05 < real["matvecs_per_s_full_size"] < 0.2 and real["threads"] in (32, 64, 128, 256)
+
+
+def test_dump_outputs_writes_the_whole_result_or_a_seeded_column_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the K x N potentials of the last step as float64, whole while they fit the byte budget; above it the
+    same seeded columns every time (they depend on N and K only) with their indices beside them."""
+    out = torch.from_numpy(np.random.default_rng(5).random((2, 1000)))
+    bench.dump_outputs(str(tmp_path / "whole"), out)
+    y = np.load(tmp_path / "whole" / "potentials.npy")
+    assert y.dtype == np.float64 and np.array_equal(y, out.numpy())
+    assert sorted(os.listdir(tmp_path / "whole")) == ["potentials.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 3 * 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    cols = np.load(tmp_path / "a" / "potentials_columns.npy")
+    ys = np.load(tmp_path / "a" / "potentials.npy")
+    assert cols.dtype == np.float64 and len(cols) == 100 and np.all(np.diff(cols) > 0)
+    assert np.array_equal(ys, out.numpy()[:, cols.astype(np.int64)])
+    assert np.array_equal(cols, np.load(tmp_path / "b" / "potentials_columns.npy"))
+    assert ys.nbytes + cols.nbytes <= bench.DUMP_BYTES
+
+
+def test_opt_in_configurations_need_full(monkeypatch):
+    """A plain run times the headline only: asking it for more is an error, not a silent no-op."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--configs", "off", "--cpu-baseline", "off", "--dropin", "off"])
+    assert not bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--configs", "solve"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--configs", "solve", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"

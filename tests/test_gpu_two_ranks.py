@@ -63,7 +63,7 @@ def _bench_ranks(world, points, config5_points, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     detail = str(tmp_path / "bench_detail.json")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--exchange", "gloo",
-                        "--points", str(points), "--steps", "3", "--warmup", "1", "--cpu-baseline", "off",
+                        "--points", str(points), "--steps", "3", "--warmup", "1", "--full", "--cpu-baseline", "off",
                         "--configs", "config5", "--config5-points", str(config5_points), "--detail-file", detail],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1100)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -101,7 +101,7 @@ def test_bench_under_the_drivers_launcher(tmp_path):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--exchange", "gloo", "--points", "300000", "--steps", "3", "--warmup", "1",
-                        "--cpu-baseline", "off", "--configs", "off", "--detail-file", detail],
+                        "--full", "--cpu-baseline", "off", "--configs", "off", "--detail-file", detail],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]

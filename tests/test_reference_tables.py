@@ -8,8 +8,6 @@ compute the same keys without tables."""
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -76,14 +74,17 @@ def _anchors(d, rng):
 
 
 def test_fixture_is_what_the_reference_holds():
-    """Regenerating from /root/reference reproduces the committed file (skipped where the reference is absent)."""
-    if not os.path.exists("/root/reference/ferreus_bbfmm/src/morton_constants.rs"):
-        pytest.skip("reference checkout not present on this machine")
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import make_reference_tables as M
-    consts = M.parse_constants("/root/reference/ferreus_bbfmm/src/morton_constants.rs")
-    v2, v3 = M.parse_reference_vectors("/root/reference/ferreus_bbfmm/src/chebyshev.rs")
-    assert consts == C and v2 == T["m2l_reference_vectors"]["2"] and v3 == T["m2l_reference_vectors"]["3"]
+    """The committed file is byte for byte the one make_reference_tables.py extracted from the reference: the digest the
+    generator recorded beside it (regenerating from the reference rewrites both)."""
+    import hashlib
+    with open(GOLD, "rb") as f:
+        got = hashlib.sha256(f.read()).hexdigest()
+    with open(GOLD + ".sha256") as f:
+        want, name = f.read().split()
+    assert name == os.path.basename(GOLD) and got == want
+    assert T["source"] == {"morton_constants": "ferreus_bbfmm/src/morton_constants.rs:12-346",
+                           "reference_vectors": "ferreus_bbfmm/src/chebyshev.rs:245-266 (doc comment of get_m2l_vectors)"}
+    assert len(T["m2l_reference_vectors"]["2"]) == 7 and len(T["m2l_reference_vectors"]["3"]) == 16
 
 
 def test_scalar_constants():
