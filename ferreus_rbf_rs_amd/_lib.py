@@ -68,6 +68,15 @@ SIGNATURES = {
                                                             c_i64, c_i64, c_p, c_i64, c_p, c_i64,
                                                             c_p]),
     "bbfmm_source_points": (ctypes.c_int, [c_p, c_p, c_i64]),
+    "bbfmm_isosurface_tables": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
+    "bbfmm_isosurface_lattice": (ctypes.c_int, [c_p, c_p, c_f64, c_p]),
+    "bbfmm_build_isosurfaces": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_i64, c_p]),
+    "bbfmm_isosurfaces_from_values": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_i64, c_p]),
+    "bbfmm_isosurface_count": (c_i32, [c_p]),
+    "bbfmm_isosurface_size": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
+    "bbfmm_isosurface_copy": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
+    "bbfmm_isosurface_error": (ctypes.c_char_p, [c_p]),
+    "bbfmm_isosurface_destroy": (None, [c_p]),
     "bbfmm_prepare_target_subset": (ctypes.c_int, [c_p, c_p, c_i64]),
     "bbfmm_fast_matrix_vector_product": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p,
                                                         c_i64, c_f64, c_p]),

@@ -1,4 +1,5 @@
 // extern "C" boundary: include/ferreus_bbfmm_hip.h over bbfmm::FmmTree.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -12,6 +13,7 @@
 #include "device_group.hpp"
 #include "ferreus_bbfmm_hip.h"
 #include "fmm_tree.hpp"
+#include "isosurface.hpp"
 #include "morton.hpp"
 
 struct bbfmm_handle {
@@ -266,6 +268,198 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
     return h->tree.evaluate(w, rows, k, ldw, x, m, ldx, out, ldo, grad, ldg, true, true, bad_point_index);
     END_GUARD(h)
 }
+
+// ---- isosurfaces (isosurface.hpp)
+} // extern "C"
+
+struct bbfmm_isosurface_result {
+    std::vector<bbfmm::iso::Mesh> meshes;
+    std::string err;
+};
+
+// Arguments shared by both extraction entry points; false with *err set on a bad one.
+static bool iso_args(const double *extents, double resolution, const double *isovalues, int32_t n_iso,
+                     bbfmm::iso::Lattice *lat, std::string *err) {
+    if (!bbfmm::iso::make_lattice(extents, resolution, lat, err)) return false;
+    if (n_iso < 1 || !isovalues) {
+        *err = "isosurface: at least one isovalue is needed";
+        return false;
+    }
+    for (int32_t q = 0; q < n_iso; ++q)
+        if (!std::isfinite(isovalues[q])) {
+            *err = "isosurface: isovalues must be finite";
+            return false;
+        }
+    return true;
+}
+
+static int iso_fail(bbfmm_handle *h, bbfmm_isosurface_result *r, int rc, const std::string &msg) {
+    if (h) h->err = msg;
+    if (r) r->err = msg;
+    return rc;
+}
+
+extern "C" {
+
+int bbfmm_isosurface_tables(int32_t *edge_deltas, int32_t *reverse_edge, int32_t *owned_tet_edges,
+                            int32_t *tet_edge_pairs, int32_t *mt_table) {
+    using namespace bbfmm::iso;
+    if (!edge_deltas || !reverse_edge || !owned_tet_edges || !tet_edge_pairs || !mt_table) return BBFMM_BAD_ARGUMENT;
+    for (int e = 0; e < 14; ++e) {
+        for (int a = 0; a < 3; ++a) edge_deltas[3 * e + a] = kEdgeDeltas[e][a];
+        reverse_edge[e] = kReverseEdge[e];
+    }
+    for (int t = 0; t < 6; ++t) {
+        for (int a = 0; a < 3; ++a) owned_tet_edges[3 * t + a] = kOwnedTetEdges[t][a];
+        for (int a = 0; a < 2; ++a) tet_edge_pairs[2 * t + a] = kTetEdgePairs[t][a];
+    }
+    for (int c = 0; c < 16; ++c) {
+        mt_table[7 * c] = kMtCount[c];
+        for (int r = 0; r < 2; ++r)
+            for (int a = 0; a < 3; ++a) mt_table[7 * c + 1 + 3 * r + a] = r < kMtCount[c] ? kMtTable[c][r][a] : -1;
+    }
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_lattice(bbfmm_handle *h, const double *extents, double resolution, int64_t *info_out) {
+    if (!info_out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: info_out must not be null");
+    bbfmm::iso::Lattice lat;
+    std::string err;
+    try {
+        if (!bbfmm::iso::make_lattice(extents, resolution, &lat, &err)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
+    } catch (const std::bad_alloc &) {
+        return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "out of host memory");
+    }
+    for (int a = 0; a < 3; ++a) {
+        info_out[a] = lat.max_ijk[a];
+        info_out[5 + a] = lat.lo[a];
+        info_out[8 + a] = lat.dims[a];
+    }
+    info_out[3] = lat.n_keys;
+    info_out[4] = lat.n_nodes;
+    if (h) h->err.clear();
+    return BBFMM_OK;
+}
+
+int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                            int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                            bbfmm_isosurface_result **out) {
+    GUARD(h)
+    if (out) *out = nullptr;
+    if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
+    if (h->tree.tree().d != 3) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: only supported for 3D (d = 3)");
+    bbfmm::iso::Lattice lat;
+    std::string err;
+    if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
+    if (drift)
+        for (int a = 0; a < 4; ++a)
+            if (!std::isfinite(drift[a])) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: drift must be finite");
+    if (h->tree.host_only()) return iso_fail(h, nullptr, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
+    if (h->group) {
+        const int rc = group_rc(h, h->group->prepare_primary(true)); // the stored expansions of the primary (Leaves mode)
+        if (rc != BBFMM_OK) return rc;
+    }
+    FmmTree &t = h->tree;
+    // every node of E inside the tree's cube (points_to_leaves saturates coordinates below the tree, as the reference's
+    // Morton encoding does, so the bounds are checked here); the device pass of extract() then finds every leaf
+    for (int a = 0; a < 3; ++a) {
+        const auto &tr = t.tree();
+        const double w0 = lat.lo_world[a] + static_cast<double>(lat.lo[a]) * lat.spacing[a];
+        const double w1 = lat.lo_world[a] + static_cast<double>(lat.lo[a] + lat.dims[a] - 1) * lat.spacing[a];
+        if (w0 < tr.center[a] - tr.radius || w1 > tr.center[a] + tr.radius)
+            return iso_fail(h, nullptr, BBFMM_POINT_OUTSIDE_TREE,
+                            "isosurface: lattice nodes on axis " + std::to_string(a) + " span [" + std::to_string(w0) + ", " +
+                                std::to_string(w1) + "], outside the tree extents [" + std::to_string(tr.center[a] - tr.radius) +
+                                ", " + std::to_string(tr.center[a] + tr.radius) + "] (pad the tree's extents, as rbf.rs:992-998 does)");
+    }
+    bbfmm::iso::FieldFn fn = [&t](const double *x0, const double *x1, const double *x2, int64_t m, double *vals) {
+        int64_t bad = -1;
+        return t.evaluate_leaves_device(x0, x1, x2, m, vals, &bad);
+    };
+    bbfmm::iso::Request req;
+    req.isovalues = isovalues;
+    req.n_iso = n_isovalues;
+    req.drift = drift;
+    req.d_field_out = d_field_out;
+    req.budget_bytes = batch_bytes;
+    std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
+    const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);
+    if (rc != BBFMM_OK) {
+        // a failure of the field evaluation has its message in the tree
+        if (err.empty()) err = t.last_error();
+        return iso_fail(h, nullptr, rc, err);
+    }
+    *out = r.release();
+    return BBFMM_OK;
+    END_GUARD(h)
+}
+
+int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                  bbfmm_isosurface_result **out) {
+    if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
+    *out = nullptr;
+    bbfmm_isosurface_result *r = nullptr;
+    try {
+        r = new bbfmm_isosurface_result();
+        *out = r;
+        if (h) {
+            h->err.clear();
+            h->tree.bind_device();
+        }
+        bbfmm::iso::Lattice lat;
+        std::string err;
+        if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+        if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
+        if (h && h->tree.host_only()) return iso_fail(h, r, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
+        if (h && h->group) {
+            const int rc = group_rc(h, h->group->prepare_primary(true));
+            if (rc != BBFMM_OK) return iso_fail(h, r, rc, h->err);
+        }
+        hipStream_t st = h ? h->tree.stream() : nullptr;
+        bool own = false;
+        if (!h) {
+            const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+            if (e != hipSuccess) return iso_fail(h, r, BBFMM_DEVICE_ERROR, std::string("isosurface: hipStreamCreate: ") + hipGetErrorString(e));
+            own = true;
+        }
+        bbfmm::iso::Request req;
+        req.isovalues = isovalues;
+        req.n_iso = n_isovalues;
+        req.host_field = values;
+        req.budget_bytes = batch_bytes;
+        const int rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
+        if (own) (void)hipStreamDestroy(st);
+        if (rc != BBFMM_OK) return iso_fail(h, r, rc, err);
+        return BBFMM_OK;
+    } catch (const std::bad_alloc &) {
+        return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "out of host memory");
+    } catch (const std::exception &e) {
+        return iso_fail(h, r, BBFMM_BAD_ARGUMENT, std::string("exception: ") + e.what());
+    }
+}
+
+int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r) { return r ? static_cast<int32_t>(r->meshes.size()) : -1; }
+
+int bbfmm_isosurface_size(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_vertices, int64_t *n_facets) {
+    if (!r || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    if (n_vertices) *n_vertices = static_cast<int64_t>(r->meshes[i].vertices.size() / 3);
+    if (n_facets) *n_facets = static_cast<int64_t>(r->meshes[i].facets.size() / 3);
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_copy(const bbfmm_isosurface_result *r, int32_t i, double *vertices, int64_t *facets) {
+    if (!r || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    const bbfmm::iso::Mesh &m = r->meshes[i];
+    if ((!vertices && !m.vertices.empty()) || (!facets && !m.facets.empty())) return BBFMM_BAD_ARGUMENT;
+    if (!m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(double));
+    if (!m.facets.empty()) std::memcpy(facets, m.facets.data(), m.facets.size() * sizeof(int64_t));
+    return BBFMM_OK;
+}
+
+const char *bbfmm_isosurface_error(const bbfmm_isosurface_result *r) { return r ? r->err.c_str() : "null result"; }
+
+void bbfmm_isosurface_destroy(bbfmm_isosurface_result *r) { delete r; }
 
 int bbfmm_source_points(const bbfmm_handle *h, double *out, int64_t ld) {
     if (!h || !out) return BBFMM_BAD_ARGUMENT;

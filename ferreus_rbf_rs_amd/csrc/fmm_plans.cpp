@@ -294,10 +294,8 @@ int FmmTree::build_target_set(const double *x, int64_t m, int64_t ldx, TargetSet
     return build_target_set_host(x, m, ldx, ts, bad_point_index, leaves_out);
 }
 
-// points_to_leaves, the stable grouping by leaf and the coordinate gather as kernels (targets.hip); the
-// host keeps the per-leaf part (M2P jobs from the W lists).  Same target set as the host path.
-int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
-                                     std::vector<int32_t> *leaves_out) {
+// the tree's cell table on the device, for points_to_leaves (uploaded once)
+int FmmTree::ensure_leaf_lookup() {
     const HostTree &t = tree_;
     if (!lk_ready_) {
         CHK(dupload(&d_tab_keys_, t.table.raw_keys()));
@@ -313,12 +311,21 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
         for (int a = 0; a < d_; ++a) lk_.disp[a] = t.center[a] - t.radius;
         lk_ready_ = true;
     }
+    return BBFMM_OK;
+}
+
+// points_to_leaves, the stable grouping by leaf and the coordinate gather as kernels (targets.hip); the
+// host keeps the per-leaf part (M2P jobs from the W lists).  Same target set as the host path.
+int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
+                                     std::vector<int32_t> *leaves_out, const double *const *d_x) {
+    const HostTree &t = tree_;
+    CHK(ensure_leaf_lookup());
     const int64_t C = t.n_cells();
     int end_bit = 1;
     while ((int64_t(1) << end_bit) < C) ++end_bit;
     auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t sm = static_cast<size_t>(m);
-    const size_t o_x = 0, o_cell = o_x + up(sm * 8 * d_), o_sorted = o_cell + up(sm * 4), o_heads = o_sorted + up(sm * 4),
+    const size_t o_x = 0, o_cell = o_x + (d_x ? 0 : up(sm * 8 * d_)), o_sorted = o_cell + up(sm * 4), o_heads = o_sorted + up(sm * 4),
                  o_scal = o_heads + up(sm), o_temp = o_scal + 256;
     const size_t temp_bytes = group_targets_temp_bytes(m, end_bit);
     const size_t need = o_temp + temp_bytes;
@@ -329,6 +336,10 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
     uint8_t *base = d_tscratch_.p;
     double *xin[3] = {nullptr, nullptr, nullptr};
     for (int a = 0; a < d_; ++a) {
+        if (d_x) {
+            xin[a] = const_cast<double *>(d_x[a]);
+            continue;
+        }
         xin[a] = reinterpret_cast<double *>(base + o_x) + static_cast<size_t>(a) * sm;
         HIPCHK(hipMemcpyAsync(xin[a], x + a * ldx, sm * sizeof(double), hipMemcpyHostToDevice, stream_));
     }

@@ -1282,6 +1282,67 @@ int FmmTree::evaluate(const double *w, int64_t rows, int k, int64_t ldw, const d
     return rc;
 }
 
+int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
+                                    int64_t *bad_point_index) {
+    if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
+    if (d_ != 3) return fail(BBFMM_BAD_ARGUMENT, "device-resident targets need d = 3");
+    if (nrhs_ != 1 || !have_locals_) return fail(BBFMM_BAD_ARGUMENT, "set_local_coefficients (one column) must be called first");
+    if (multipoles_partial_) return fail(BBFMM_BAD_ARGUMENT, kPartialMultipoles);
+    if (m < 0 || (m > 0 && (!d_x0 || !d_x1 || !d_x2))) return fail(BBFMM_BAD_ARGUMENT, "bad device target arrays");
+    if (m >= (int64_t(1) << 31)) return fail(BBFMM_BAD_ARGUMENT, "more than 2^31-1 target points");
+    if (m == 0) return BBFMM_OK;
+    part_pending_k_ = 0;
+    last_eval_at_sources_ = last_eval_rows_of_sources_ = false;
+    if (!d_out) { // points_to_leaves alone
+        CHK(ensure_leaf_lookup());
+        arena_begin();
+        DevBuf<int32_t> cell;
+        DevBuf<unsigned long long> bad;
+        int rc = talloc(&cell, static_cast<size_t>(m));
+        if (rc == BBFMM_OK) rc = talloc(&bad, 1);
+        unsigned long long h_bad = ~0ull;
+        if (rc == BBFMM_OK) {
+            hipError_t e = hipMemsetAsync(bad.p, 0xFF, sizeof(unsigned long long), stream_);
+            if (e == hipSuccess) {
+                launch_points_to_leaves(lk_, d_x0, d_x1, d_x2, m, cell.p, bad.p, stream_);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, stream_);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+            if (e != hipSuccess) rc = hip_fail(e, "locate device targets");
+        }
+        dfree(&cell);
+        dfree(&bad);
+        const int arc = arena_end();
+        if (rc == BBFMM_OK) rc = arc;
+        if (rc == BBFMM_OK && h_bad != ~0ull) {
+            if (bad_point_index) *bad_point_index = static_cast<int64_t>(h_bad);
+            rc = fail(BBFMM_POINT_OUTSIDE_TREE, "FMM evaluation failed: target point at row " + std::to_string(h_bad) +
+                                                    " lies outside the tree extents");
+        }
+        return rc;
+    }
+    TargetSet ts;
+    arena_begin();
+    const double *dx[3] = {d_x0, d_x1, d_x2};
+    int rc = build_target_set_device(nullptr, m, m, &ts, bad_point_index, nullptr, dx);
+    if (rc == BBFMM_OK) rc = talloc(&ts.out, static_cast<size_t>(m));
+    if (rc == BBFMM_OK) rc = leaf_pass(ts, 1, false);
+    if (rc == BBFMM_OK) {
+        phase_begin();
+        launch_scatter_output(ts.out.p, m, 1, ts.perm.p, d_out, m, 0, stream_);
+        phase_end(kPhScatter);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_); // the target set's arena buffers are reused by the next call
+        if (e != hipSuccess) rc = hip_fail(e, "scatter device-target values");
+    } else if (stream_) {
+        (void)hipStreamSynchronize(stream_);
+    }
+    free_target_set(&ts);
+    const int arc = arena_end();
+    return rc == BBFMM_OK ? arc : rc;
+}
+
 int FmmTree::matvec_device(const double *d_w, int64_t ldw, int k, double *d_out, int64_t ldo, bool sync) {
     if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
     part_pending_k_ = 0; // M, the sorted weights or the partition's outputs are rewritten: a half-done partitioned matvec is void

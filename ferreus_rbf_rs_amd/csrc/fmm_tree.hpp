@@ -155,6 +155,12 @@ class FmmTree {
                uint32_t flags);
     int set_weights(const double *w, int64_t rows, int k, int64_t ldw);                 // bbfmm.rs:383-401
     int set_local_coefficients(const double *w, int64_t rows, int k, int64_t ldw);      // bbfmm.rs:518-524
+    // Leaves mode (after set_local_coefficients, one column) at m targets that are already on the device (SoA, d == 3):
+    // the target set, grouping and leaf pass of evaluate(..., leaves_only = true) with no host copy; values to d_out in
+    // row order, on the handle's stream (isosurface lattice nodes).  d_out == nullptr: only checks that every target
+    // lies in the tree (BBFMM_POINT_OUTSIDE_TREE, *bad_point_index the first row that does not).
+    int evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
+                               int64_t *bad_point_index);
     int evaluate(const double *w, int64_t rows, int k, int64_t ldw, const double *x, int64_t m, int64_t ldx,
                  double *out, int64_t ldo, double *grad, int64_t ldg, bool with_grads, bool leaves_only,
                  int64_t *bad_point_index);                                             // bbfmm.rs:444-616
@@ -257,8 +263,10 @@ class FmmTree {
     int build_target_set(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                          std::vector<int32_t> *leaves_out = nullptr);
     // the same on the device (targets.hip) for batches of at least device_targets_min_ rows
+    // d_x (3 device arrays): targets already on the device, x unused
     int build_target_set_device(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
-                                std::vector<int32_t> *leaves_out);
+                                std::vector<int32_t> *leaves_out, const double *const *d_x = nullptr);
+    int ensure_leaf_lookup();
     int build_target_set_host(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                               std::vector<int32_t> *leaves_out);
     int build_source_target_set();

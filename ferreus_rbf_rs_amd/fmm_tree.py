@@ -271,6 +271,32 @@ class FmmTree:
         return self._eval(self._lib.bbfmm_evaluate_leaves_with_gradients, weights, target_points,
                           True, True)
 
+    # -- isosurfaces (isosurface.py)
+    def build_isosurfaces(self, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes=0):
+        """RBFInterpolator::build_isosurfaces (ferreus_rbf/src/rbf.rs:980-) on the device, one field evaluation for all
+        isovalues: a list of (vertices (n, 3) f64, facets (m, 3) int64), the raw marching-tetrahedra mesh of
+        ferreus_rmt with ClusterMethod::None (isosurface.rs:489-) before clipping, cleaning and boundary closure, over
+        every sample point of the extraction domain.  Needs set_local_coefficients (one column) first, like
+        evaluate_leaves, and a tree whose extents hold the lattice (the reference pads its evaluator by 10 resolutions,
+        rbf.rs:992-998; a node outside raises PointOutsideTree before any work).  drift: None, [a, b0, b1, b2] or
+        (a, [b0, b1, b2]) added to the field as a + b . x (isosurface.affine_drift folds the reference's Constant /
+        Linear drift with its translation and scale).  return_field: also the lattice field, shape
+        isosurface.lattice_info(extents, resolution)["shape"], NaN off the evaluated nodes.  batch_bytes: device memory
+        for one batch of k-planes (0: the default); the meshes do not depend on it."""
+        from . import isosurface as I
+        return I.build_isosurfaces(self, extents, resolution, isovalues, drift=drift, return_field=return_field,
+                                   batch_bytes=batch_bytes)
+
+    def build_isosurface(self, extents, resolution, isovalue, *, drift=None, return_field=False, batch_bytes=0):
+        """RBFInterpolator::build_isosurface (rbf.rs:954-) at one isovalue: (vertices, facets), and the lattice field
+        when return_field; see build_isosurfaces."""
+        out = self.build_isosurfaces(extents, resolution, [isovalue], drift=drift, return_field=return_field,
+                                     batch_bytes=batch_bytes)
+        if return_field:
+            meshes, field = out
+            return meshes[0][0], meshes[0][1], field
+        return out[0]
+
     def source_points(self):
         out = np.zeros((self.n_points, self.dim), order="F")
         self._raise(self._lib.bbfmm_source_points(self._h, out.ctypes.data, self.n_points))

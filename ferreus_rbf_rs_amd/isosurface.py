@@ -1,0 +1,171 @@
+"""Isosurfaces on the regularised-marching-tetrahedra (RMT) sampling lattice, extracted on the device.
+
+The mesh is ferreus_rmt's raw marching-tetrahedra output (`build_isosurface` with `ClusterMethod::None`,
+ferreus_rmt/src/isosurface.rs:489-) before `clip_mesh_to_aabb`, `clean_mesh` and boundary closure, taken over every
+sample point of the extraction domain instead of the sample points a seeded wavefront reaches (DESIGN.md "Isosurfaces
+on the RMT lattice"):
+
+* lattice (lattice.rs:55-96): spacing [r/2, r*sqrt2/2, r/sqrt2], max_ijk = ceil((hi - lo) / spacing), max_ijk[0] += 1,
+  world(ijk) = lo + ijk * spacing;
+* keys: sample points (even i + j + k) with one of their 8 corners (get_edge_points::<8>, isosurface.rs:87-102) in
+  [-2, max_ijk + 2] (extraction_ijk_inbounds, lattice.rs:117-128); E: the corners of the keys, where the field is
+  evaluated; inside means f - isovalue < -1e-9 (isosurface.rs:286-289);
+* one vertex per lattice edge of E with finite ends on opposite sides, placed from the end that holds it under the
+  wavefront's t < 0.5 rule (isosurface.rs:588-610) with lerp_alpha (isosurface.rs:173-181);
+* facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order.
+
+Lattice fields are arrays of shape (nk, nj, ni) over the bounding box of E (`lattice_info(...)["shape"]`, entry
+[0, 0, 0] at ijk `lattice_info(...)["lo"]`); entries off E are ignored, and NaN in returned fields.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib as L
+
+
+def _ext(extents):
+    e = np.ascontiguousarray(np.asarray(extents, dtype=np.float64).reshape(-1))
+    if e.shape != (6,):
+        raise ValueError("extents must hold 6 values: min x, min y, min z, max x, max y, max z")
+    return e
+
+
+def _isovalues(isovalues):
+    v = np.ascontiguousarray(np.atleast_1d(np.asarray(isovalues, dtype=np.float64)).reshape(-1))
+    if v.size == 0:
+        raise ValueError("at least one isovalue is needed")
+    return v
+
+
+def _drift(drift):
+    """None, [a, b0, b1, b2] or (a, [b0, b1, b2]): the affine drift a + b . x."""
+    if drift is None:
+        return None
+    if len(drift) == 2 and np.ndim(drift[1]) == 1:
+        d = np.concatenate([[float(drift[0])], np.asarray(drift[1], dtype=np.float64).reshape(-1)])
+    else:
+        d = np.asarray(drift, dtype=np.float64).reshape(-1)
+    if d.shape != (4,):
+        raise ValueError("drift must be [a, b0, b1, b2] or (a, [b0, b1, b2])")
+    return np.ascontiguousarray(d)
+
+
+def affine_drift(coefficients, translation=None, scale=None):
+    """The drift of a Constant ([c0]) or Linear ([c0, c1, c2, c3] for [1, x0, x1, x2]) polynomial evaluated on (x - translation) / scale,
+    as the reference's interpolator evaluates its global trend (polynomials.rs:30-74), folded into (a, b)."""
+    c = np.asarray(coefficients, dtype=np.float64).reshape(-1)
+    if c.size == 1:
+        return (float(c[0]), np.zeros(3))
+    if c.size != 4:
+        raise ValueError("only Constant (1) and Linear (4 coefficients) drift is supported")
+    t = np.broadcast_to(np.asarray(0.0 if translation is None else translation, dtype=np.float64), (3,))
+    s = np.broadcast_to(np.asarray(1.0 if scale is None else scale, dtype=np.float64), (3,))
+    b = c[1:] / s
+    return (float(c[0] - np.dot(b, t)), b)
+
+
+def lattice_info(extents, resolution, tree=None) -> dict:
+    """max_ijk (SampleLattice::new), the number of keys and of nodes of E, and the layout of lattice fields."""
+    lib = L.load()
+    info = np.zeros(11, dtype=np.int64)
+    h = tree._h if tree is not None else None
+    rc = lib.bbfmm_isosurface_lattice(h, _ext(extents).ctypes.data, float(resolution), info.ctypes.data)
+    if rc != L.OK:
+        raise ValueError(lib.bbfmm_last_error(h).decode() if h else "bad isosurface lattice arguments")
+    return {"max_ijk": info[0:3].copy(), "n_keys": int(info[3]), "n_nodes": int(info[4]), "lo": info[5:8].copy(),
+            "shape": (int(info[10]), int(info[9]), int(info[8]))}
+
+
+def tables() -> dict:
+    """The marching-tetrahedra tables the library holds (ferreus_rmt/src/constants.rs)."""
+    lib = L.load()
+    ed, rev = np.zeros(42, np.int32), np.zeros(14, np.int32)
+    tets, pairs, mt = np.zeros(18, np.int32), np.zeros(12, np.int32), np.zeros(16 * 7, np.int32)
+    rc = lib.bbfmm_isosurface_tables(ed.ctypes.data, rev.ctypes.data, tets.ctypes.data, pairs.ctypes.data, mt.ctypes.data)
+    assert rc == L.OK
+    mt = mt.reshape(16, 7)
+    return {"EDGE_DELTAS": ed.reshape(14, 3).tolist(), "REVERSE_EDGE": rev.tolist(),
+            "OWNED_TET_EDGES": tets.reshape(6, 3).tolist(), "TET_EDGE_PAIRS": pairs.reshape(6, 2).tolist(),
+            "MT_TABLE": [mt[c, 1:1 + 3 * mt[c, 0]].reshape(-1, 3).tolist() for c in range(16)]}
+
+
+def _meshes(lib, res):
+    out = []
+    for i in range(lib.bbfmm_isosurface_count(res)):
+        nv, nf = ctypes.c_int64(), ctypes.c_int64()
+        lib.bbfmm_isosurface_size(res, i, ctypes.byref(nv), ctypes.byref(nf))
+        v = np.empty((nv.value, 3), dtype=np.float64)
+        f = np.empty((nf.value, 3), dtype=np.int64)
+        lib.bbfmm_isosurface_copy(res, i, v.ctypes.data, f.ctypes.data)
+        out.append((v, f))
+    return out
+
+
+def _raise(rc, msg, leaf=True):
+    from .fmm_tree import FmmError, PointOutsideTree
+    if rc == L.POINT_OUTSIDE_TREE:
+        e = PointOutsideTree(-1, leaf)
+        e.args = (msg,)
+        raise e
+    if rc == L.DEVICE_ERROR:
+        raise RuntimeError(msg)
+    raise FmmError(msg)
+
+
+def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0):
+    """Meshes of the tree's field (set_local_coefficients first, one column) at each isovalue, one field evaluation
+    for all of them; see FmmTree.build_isosurfaces."""
+    lib = L.load()
+    ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
+    field_t = None
+    if return_field:
+        import torch
+        info = lattice_info(ext, resolution, tree)
+        n = int(np.prod(info["shape"]))
+        field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
+        torch.cuda.synchronize(field_t.device)
+    res = ctypes.c_void_p()
+    rc = lib.bbfmm_build_isosurfaces(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
+                                     d.ctypes.data if d is not None else None,
+                                     field_t.data_ptr() if field_t is not None else None, int(batch_bytes),
+                                     ctypes.byref(res))
+    try:
+        if rc != L.OK:
+            _raise(rc, lib.bbfmm_last_error(tree._h).decode())
+        meshes = _meshes(lib, res)
+    finally:
+        if res:
+            lib.bbfmm_isosurface_destroy(res)
+    if return_field:
+        return meshes, field_t.cpu().numpy().reshape(info["shape"])
+    return meshes
+
+
+def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None):
+    """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
+    current device (or the tree's)."""
+    lib = L.load()
+    ext, iso = _ext(extents), _isovalues(isovalues)
+    vals = np.ascontiguousarray(np.asarray(lattice_values, dtype=np.float64))
+    info = lattice_info(ext, resolution, tree)
+    if vals.size != int(np.prod(info["shape"])):
+        raise ValueError(f"lattice_values must have shape {info['shape']}, got {vals.shape}")
+    res = ctypes.c_void_p()
+    h = tree._h if tree is not None else None
+    rc = lib.bbfmm_isosurfaces_from_values(h, vals.ctypes.data, ext.ctypes.data, float(resolution), iso.ctypes.data,
+                                           len(iso), int(batch_bytes), ctypes.byref(res))
+    try:
+        if rc != L.OK:
+            _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
+        return _meshes(lib, res)
+    finally:
+        if res:
+            lib.bbfmm_isosurface_destroy(res)
+
+
+def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None):
+    """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue."""
+    return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree)[0]

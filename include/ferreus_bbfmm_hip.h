@@ -222,6 +222,39 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
                                          double *out, int64_t ldo, double *grad, int64_t ldg,
                                          int64_t *bad_point_index);
 
+/* ---- Isosurfaces: dense marching tetrahedra on the RMT sampling lattice (ferreus_rmt build_isosurface with
+ * ClusterMethod::None, before clipping, cleaning and boundary closure; contract in DESIGN.md "Isosurfaces on the RMT
+ * lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
+ * nk x nj x ni doubles (i fastest) over the bounding box of the extraction nodes E; entries off E are ignored (NaN in
+ * returned fields).  Vertices are n x 3 doubles, facets m x 3 int64 vertex ids, both row-major. */
+typedef struct bbfmm_isosurface_result bbfmm_isosurface_result; /* the meshes of one call, one per isovalue */
+
+/* The reference's tables as the product holds them: EDGE_DELTAS (14 x 3), REVERSE_EDGE (14), OWNED_TET_EDGES (6 x 3),
+ * TET_EDGE_PAIRS (6 x 2), MT_TABLE (16 x 7: triangle count, then up to 2 triangles of 3 tet-edge ids, -1 padded). */
+int bbfmm_isosurface_tables(int32_t *edge_deltas, int32_t *reverse_edge, int32_t *owned_tet_edges,
+                            int32_t *tet_edge_pairs, int32_t *mt_table);
+/* Host only (any handle, also BBFMM_FLAG_HOST_ONLY; h may be NULL, then without a message).  info_out[11]: max_ijk[3],
+ * number of keys, number of nodes of E, ijk of field entry 0 (3), ni, nj, nk. */
+int bbfmm_isosurface_lattice(bbfmm_handle *h, const double *extents, double resolution, int64_t *info_out);
+/* Meshes of the handle's field (after bbfmm_set_local_coefficients with one column; d = 3) at n_isovalues isovalues
+ * that share one evaluation of the field, on the handle's stream (a device group: on its primary part).  drift: NULL or
+ * [a, b0, b1, b2], a + b . x added to the field.  d_field_out: NULL or a device array of nk x nj x ni doubles that
+ * receives the field.  batch_bytes: device memory for one batch of k-planes (<= 0: a default).  A node outside the tree:
+ * BBFMM_POINT_OUTSIDE_TREE before any work.  *out is set on success (free with bbfmm_isosurface_destroy). */
+int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                            int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                            bbfmm_isosurface_result **out);
+/* The same from a caller's host field (nk x nj x ni doubles).  h NULL: the current device and a stream of the call's
+ * own; the message of a failure is then in *out (bbfmm_isosurface_error), which is set whenever out is not NULL. */
+int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                  bbfmm_isosurface_result **out);
+int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r);
+int bbfmm_isosurface_size(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_vertices, int64_t *n_facets);
+int bbfmm_isosurface_copy(const bbfmm_isosurface_result *r, int32_t i, double *vertices, int64_t *facets);
+const char *bbfmm_isosurface_error(const bbfmm_isosurface_result *r);
+void bbfmm_isosurface_destroy(bbfmm_isosurface_result *r);
+
 /* FmmTree::source_points (utils.rs:489-493): copies the N x d points to out (ld). */
 int bbfmm_source_points(const bbfmm_handle *h, double *out, int64_t ld);
 
