@@ -72,6 +72,11 @@ SIGNATURES = {
     "bbfmm_isosurface_lattice": (ctypes.c_int, [c_p, c_p, c_f64, c_p]),
     "bbfmm_build_isosurfaces": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_i64, c_p]),
     "bbfmm_isosurfaces_from_values": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_i64, c_p]),
+    "bbfmm_build_isosurfaces_ex": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p]),
+    "bbfmm_isosurfaces_from_values_ex": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_i64, c_i32, c_p]),
+    "bbfmm_isosurface_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_topology": (ctypes.c_int, [ctypes.c_uint32, c_p, c_p, c_p]),
+    "bbfmm_isosurface_cluster_tables": (ctypes.c_int, [c_p, c_p, c_p]),
     "bbfmm_isosurface_count": (c_i32, [c_p]),
     "bbfmm_isosurface_size": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
     "bbfmm_isosurface_copy": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),

@@ -341,12 +341,41 @@ int bbfmm_isosurface_lattice(bbfmm_handle *h, const double *extents, double reso
     return BBFMM_OK;
 }
 
+int bbfmm_isosurface_cluster_tables(int32_t *neighbour_masks, int32_t *flat_hole_masks, int32_t *all14_mask) {
+    using namespace bbfmm::iso;
+    if (!neighbour_masks || !flat_hole_masks || !all14_mask) return BBFMM_BAD_ARGUMENT;
+    for (int e = 0; e < 14; ++e) neighbour_masks[e] = kNeighbourMasks[e];
+    for (int r = 0; r < 36; ++r)
+        for (int a = 0; a < 2; ++a) flat_hole_masks[2 * r + a] = kFlatHoleMasks[r][a];
+    *all14_mask = kAll14;
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_topology(uint32_t near_mask, const double *neighbour_values, int32_t *case_out, int32_t *cluster_of_edge) {
+    using namespace bbfmm::iso;
+    if (!case_out || !cluster_of_edge || near_mask > kAll14) return BBFMM_BAD_ARGUMENT;
+    int c = kSimple;
+    const uint64_t part = topology_partition(static_cast<uint16_t>(near_mask), neighbour_values, &c);
+    *case_out = c;
+    for (int e = 0; e < 14; ++e) cluster_of_edge[e] = part_label(part, e) == 15 ? -1 : part_label(part, e);
+    return BBFMM_OK;
+}
+
 int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                             int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
                             bbfmm_isosurface_result **out) {
+    return bbfmm_build_isosurfaces_ex(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch_bytes,
+                                      BBFMM_CLUSTER_NONE, out);
+}
+
+int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                               int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                               int32_t cluster_method, bbfmm_isosurface_result **out) {
     GUARD(h)
     if (out) *out = nullptr;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
+    if (cluster_method != BBFMM_CLUSTER_NONE && cluster_method != BBFMM_CLUSTER_AVERAGE)
+        return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: unknown cluster method " + std::to_string(cluster_method));
     if (h->tree.tree().d != 3) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: only supported for 3D (d = 3)");
     bbfmm::iso::Lattice lat;
     std::string err;
@@ -382,6 +411,7 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
     req.drift = drift;
     req.d_field_out = d_field_out;
     req.budget_bytes = batch_bytes;
+    req.cluster = cluster_method;
     std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
     const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);
     if (rc != BBFMM_OK) {
@@ -397,6 +427,13 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
 int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                   const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
                                   bbfmm_isosurface_result **out) {
+    return bbfmm_isosurfaces_from_values_ex(h, values, extents, resolution, isovalues, n_isovalues, batch_bytes,
+                                            BBFMM_CLUSTER_NONE, out);
+}
+
+int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                     const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                     int32_t cluster_method, bbfmm_isosurface_result **out) {
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     *out = nullptr;
     bbfmm_isosurface_result *r = nullptr;
@@ -411,6 +448,8 @@ int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const d
         std::string err;
         if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
         if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
+        if (cluster_method != BBFMM_CLUSTER_NONE && cluster_method != BBFMM_CLUSTER_AVERAGE)
+            return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: unknown cluster method " + std::to_string(cluster_method));
         if (h && h->tree.host_only()) return iso_fail(h, r, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
         if (h && h->group) {
             const int rc = group_rc(h, h->group->prepare_primary(true));
@@ -428,6 +467,7 @@ int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const d
         req.n_iso = n_isovalues;
         req.host_field = values;
         req.budget_bytes = batch_bytes;
+        req.cluster = cluster_method;
         const int rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
         if (own) (void)hipStreamDestroy(st);
         if (rc != BBFMM_OK) return iso_fail(h, r, rc, err);
@@ -454,6 +494,12 @@ int bbfmm_isosurface_copy(const bbfmm_isosurface_result *r, int32_t i, double *v
     if ((!vertices && !m.vertices.empty()) || (!facets && !m.facets.empty())) return BBFMM_BAD_ARGUMENT;
     if (!m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(double));
     if (!m.facets.empty()) std::memcpy(facets, m.facets.data(), m.facets.size() * sizeof(int64_t));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(stats_out, r->meshes[i].stats, sizeof(r->meshes[i].stats));
     return BBFMM_OK;
 }
 

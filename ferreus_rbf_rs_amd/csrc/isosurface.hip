@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <limits>
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "ferreus_bbfmm_hip.h"
@@ -233,6 +234,245 @@ __global__ __launch_bounds__(kThreads) void facets_kernel(Slab s, TetTables tt, 
     }
 }
 
+// ---- vertex clustering (Request::cluster == kClusterAverage).  The slab is the whole box: field plane s = k + 1 with a
+// NaN plane below and above, the per-node arrays (part, ccnt, vbase, fcnt) indexed by n = k * P + j * ni + i.
+
+__device__ __forceinline__ int64_t edge_step(const Slab &s, int e) {
+    return kEdgeDeltas[e][2] * s.P + int64_t(kEdgeDeltas[e][1]) * s.ni + kEdgeDeltas[e][0];
+}
+
+// lerp_alpha (isosurface.rs:173-181)
+__device__ __forceinline__ double lerp_alpha(double gu, double gw) {
+    const double den = gu - gw;
+    if (fabs(den) < 1e-30) return 0.5;
+    const double a = gu / den;
+    return a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
+}
+
+// Per node: the near mask N(p) of its 14 edges (isosurface.rs:588-610) and its partition by test_topology.
+__global__ __launch_bounds__(kThreads) void near_topology_kernel(Slab s, int64_t nk, const double *__restrict__ f, double iso,
+                                                                  uint64_t *__restrict__ part, int32_t *__restrict__ ccnt,
+                                                                  unsigned long long *__restrict__ stats) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        const int64_t k = n / s.P, r = n % s.P;
+        const int32_t j = static_cast<int32_t>(r / s.ni), i = static_cast<int32_t>(r % s.ni);
+        const double gp = f[s.P + n] - iso;
+        uint64_t p = kNoClusters;
+        if (isfinite(gp)) { // in E (NaN elsewhere), hence a sample point
+            const bool inp = inside(gp);
+            double v[14];
+            uint32_t m = 0;
+            bool complete = true;
+            for (int e = 0; e < 14; ++e) {
+                const int32_t qi = i + kEdgeDeltas[e][0], qj = j + kEdgeDeltas[e][1];
+                const int64_t qk = k + kEdgeDeltas[e][2];
+                v[e] = __builtin_nan("");
+                if (qi < 0 || qi >= s.ni || qj < 0 || qj >= s.nj || qk < 0 || qk >= nk || !in_range(s.e_rows, qk * s.nj + qj, qi)) {
+                    complete = false;
+                    continue;
+                }
+                const double gq = f[s.P + n + edge_step(s, e)] - iso;
+                v[e] = gq;
+                if (!isfinite(gq) || inside(gq) == inp) continue;
+                // t from the owner of the edge: p for e < 7, the neighbour otherwise
+                const bool near_p = e < 7 ? gp / (gp - gq) < 0.5 : !(gq / (gq - gp) < 0.5);
+                if (near_p) m |= 1u << e;
+            }
+            if (m) {
+                int c = kIncomplete;
+                p = complete ? topology_partition(static_cast<uint16_t>(m), v, &c) : part_singletons(static_cast<uint16_t>(m));
+                atomicAdd(&stats[c], 1ull); // a count only: nothing is placed by it
+            }
+        }
+        part[n] = p;
+        ccnt[n] = __popc(part_leaders(p));
+    }
+}
+
+// The candidate point of every cluster, at the vertex ids the scan gave (vbase) (isosurface.rs:738-796): the intersection of a single
+// edge, the mean of several (average_point, isosurface.rs:183-192).  vinfo: node << 5 | lowest edge << 1 | several edges.
+__global__ __launch_bounds__(kThreads) void candidates_kernel(Slab s, const double *__restrict__ f, double iso, const uint64_t *__restrict__ part,
+                                                               const int64_t *__restrict__ vbase, double *__restrict__ out,
+                                                               int64_t *__restrict__ vinfo) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        int64_t v = vbase[n];
+        const uint64_t p = part[n];
+        if (p == kNoClusters) continue;
+        const int64_t k = n / s.P, r = n % s.P;
+        const int64_t ijk[3] = {s.lo[0] + r % s.ni, s.lo[1] + r / s.ni, s.lo[2] + k};
+        const double gp = f[s.P + n] - iso;
+        for (int lead = 0; lead < 14; ++lead) {
+            if (part_label(p, lead) != lead) continue;
+            double sum[3] = {0.0, 0.0, 0.0}, one[3] = {0.0, 0.0, 0.0};
+            int cnt = 0;
+            for (int e = lead; e < 14; ++e) {
+                if (part_label(p, e) != lead) continue;
+                const double gq = f[s.P + n + edge_step(s, e)] - iso;
+                const double alpha = lerp_alpha(gp, gq);
+                for (int a = 0; a < 3; ++a) {
+                    const double wu = world(s, a, ijk[a]), ww = world(s, a, ijk[a] + kEdgeDeltas[e][a]);
+                    one[a] = wu + alpha * (ww - wu);
+                    sum[a] = sum[a] + one[a];
+                }
+                ++cnt;
+            }
+            const double inv = 1.0 / static_cast<double>(cnt);
+            for (int a = 0; a < 3; ++a) out[3 * v + a] = cnt == 1 ? one[a] : sum[a] * inv;
+            vinfo[v] = (n << 5) | (int64_t(lead) << 1) | (cnt > 1 ? 1 : 0);
+            ++v;
+        }
+    }
+}
+
+// The vertex of the cluster that holds the owned edge `lab` of node `on` at its near end; -1: none.
+__device__ __forceinline__ int64_t resolve_cluster(const Slab &s, const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase,
+                                                   int64_t on, int lab) {
+    uint64_t p = part[on];
+    int l = part_label(p, lab);
+    if (l == 15) {
+        on += edge_step(s, lab);
+        p = part[on];
+        l = part_label(p, kReverseEdge[lab]);
+        if (l == 15) return -1;
+    }
+    return vbase[on] + __popc(part_leaders(p) & ((1u << l) - 1u));
+}
+
+// march_tets (isosurface.rs:224-283) of the key at node n with clustered vertices; degenerate triangles are dropped.
+template <class Emit>
+__device__ __forceinline__ void march_key(const Slab &s, const TetTables &tt, const double *__restrict__ f, double iso,
+                                          const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase, int64_t n, Emit emit) {
+    const int64_t r = n % s.P;
+    const int32_t j = static_cast<int32_t>(r / s.ni), i = static_cast<int32_t>(r % s.ni);
+    for (int t = 0; t < 6; ++t) {
+        int c = 0;
+        bool ok = true;
+        for (int q = 0; q < 4; ++q) {
+            const int32_t qi = i + tt.corner[t][q][0], qj = j + tt.corner[t][q][1];
+            if (qi < 0 || qi >= s.ni || qj < 0 || qj >= s.nj) { ok = false; break; }
+            const double g = f[s.P + n + tt.corner[t][q][2] * s.P + int64_t(tt.corner[t][q][1]) * s.ni + tt.corner[t][q][0]] - iso;
+            if (!isfinite(g)) { ok = false; break; }
+            if (inside(g)) c |= 1 << q;
+        }
+        if (!ok) continue;
+        for (int row = 0; row < kMtCount[c]; ++row) {
+            int64_t id[3];
+            for (int e3 = 0; e3 < 3; ++e3) {
+                const int *ow = tt.own[t][kMtTable[c][row][e3]];
+                id[e3] = resolve_cluster(s, part, vbase, n + ow[2] * s.P + int64_t(ow[1]) * s.ni + ow[0], ow[3]);
+            }
+            if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] == id[1] || id[1] == id[2] || id[0] == id[2]) continue;
+            emit(id);
+        }
+    }
+}
+
+__device__ __forceinline__ bool is_key(const Slab &s, const double *__restrict__ f, int64_t n) {
+    if (!isfinite(f[s.P + n])) return false;
+    const int64_t r = n % s.P;
+    return in_range(s.key_rows, (n / s.P) * s.nj + r / s.ni, static_cast<int32_t>(r % s.ni));
+}
+
+__global__ __launch_bounds__(kThreads) void cluster_count_kernel(Slab s, TetTables tt, const double *__restrict__ f, double iso,
+                                                                  const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase,
+                                                                  int32_t *__restrict__ fcnt) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        int32_t c = 0;
+        if (is_key(s, f, n)) march_key(s, tt, f, iso, part, vbase, n, [&](const int64_t *) { ++c; });
+        fcnt[n] = c;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void cluster_facets_kernel(Slab s, TetTables tt, const double *__restrict__ f, double iso,
+                                                                   const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase,
+                                                                   const int32_t *__restrict__ fcnt, const int64_t *__restrict__ foff,
+                                                                   int64_t *__restrict__ out) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        if (!fcnt[n]) continue;
+        int64_t o = foff[n];
+        march_key(s, tt, f, iso, part, vbase, n, [&](const int64_t *id) {
+            for (int a = 0; a < 3; ++a) out[3 * o + a] = id[a];
+            ++o;
+        });
+    }
+}
+
+// The 3 undirected edges of every facet as keys min << 32 | max, the facet as their value.
+__global__ __launch_bounds__(kThreads) void facet_edges_kernel(int64_t nf, const int64_t *__restrict__ facets, uint64_t *__restrict__ keys,
+                                                                int64_t *__restrict__ vals) {
+    for (int64_t t = blockIdx.x * int64_t(kThreads) + threadIdx.x; t < nf; t += int64_t(gridDim.x) * kThreads) {
+        for (int a = 0; a < 3; ++a) {
+            const uint64_t u = static_cast<uint64_t>(facets[3 * t + a]), w = static_cast<uint64_t>(facets[3 * t + (a + 1) % 3]);
+            keys[3 * t + a] = u < w ? (u << 32 | w) : (w << 32 | u);
+            vals[3 * t + a] = t;
+        }
+    }
+}
+
+// Over the sorted edges: an entry of a run of more than 2 equal keys is a face on an over-used mesh edge.  Pass A
+// (isosurface.rs:840-851) flags the edge's two vertices, pass B (collect_invalid_topology_cluster_owners,
+// isosurface.rs:326-356) the three of the face; only clusters of several edges count.  Plain stores of one value.
+__global__ __launch_bounds__(kThreads) void flag_over_used_kernel(int64_t m, const uint64_t *__restrict__ keys, const int64_t *__restrict__ vals,
+                                                                   const int64_t *__restrict__ facets, const int64_t *__restrict__ vinfo,
+                                                                   bool pass_b, uint8_t *__restrict__ vflag, int32_t *__restrict__ found,
+                                                                   unsigned long long *__restrict__ n_over) {
+    for (int64_t i = blockIdx.x * int64_t(kThreads) + threadIdx.x; i < m; i += int64_t(gridDim.x) * kThreads) {
+        const uint64_t k = keys[i];
+        const bool lo1 = i >= 1 && keys[i - 1] == k, lo2 = i >= 2 && keys[i - 2] == k;
+        const bool hi1 = i + 1 < m && keys[i + 1] == k, hi2 = i + 2 < m && keys[i + 2] == k;
+        if (!(hi2 || (lo1 && hi1) || lo2)) continue;
+        if (!lo1) atomicAdd(n_over, 1ull); // a count only
+        int64_t v[3];
+        int nv = 2;
+        if (pass_b) {
+            nv = 3;
+            for (int a = 0; a < 3; ++a) v[a] = facets[3 * vals[i] + a];
+        } else {
+            v[0] = static_cast<int64_t>(k >> 32);
+            v[1] = static_cast<int64_t>(k & 0xffffffffull);
+        }
+        for (int a = 0; a < nv; ++a)
+            if (vinfo[v[a]] & 1) {
+                vflag[v[a]] = pass_b ? 2 : 1;
+                *found = 1;
+            }
+    }
+}
+
+// Pass A: a flagged cluster becomes singletons.  Pass B (rollback_cluster_owners, isosurface.rs:359-395): every cluster
+// of a sample point that owns a flagged one does.
+__global__ __launch_bounds__(kThreads) void split_clusters_kernel(Slab s, const int64_t *__restrict__ vbase, const uint8_t *__restrict__ vflag,
+                                                                   uint64_t *__restrict__ part, int32_t *__restrict__ ccnt,
+                                                                   unsigned long long *__restrict__ n_split, unsigned long long *__restrict__ n_rolled) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        if (!ccnt[n]) continue;
+        uint64_t p = part[n];
+        const uint64_t before = p;
+        int64_t v = vbase[n];
+        bool roll = false;
+        int split = 0;
+        for (int lead = 0; lead < 14; ++lead) {
+            if (part_label(before, lead) != lead) continue;
+            const uint8_t fl = vflag[v++];
+            if (fl == 2) roll = true;
+            if (fl != 1) continue;
+            ++split;
+            for (int e = lead + 1; e < 14; ++e)
+                if (part_label(before, e) == lead) p = part_set(p, e, e);
+        }
+        if (roll) {
+            p = part_singletons(part_mask(before));
+            atomicAdd(n_rolled, 1ull);
+        } else if (split) {
+            atomicAdd(n_split, static_cast<unsigned long long>(split));
+        }
+        if (p != before) {
+            part[n] = p;
+            ccnt[n] = __popc(part_leaders(p));
+        }
+    }
+}
+
 int grid_for(int64_t n) {
     return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 4096)));
 }
@@ -288,6 +528,137 @@ struct IsoState {
     Growing<double> v;
     Growing<int64_t> fc;
 };
+
+#define ISO_HIP(x)                                                                        \
+    do {                                                                                  \
+        hipError_t e_ = (x);                                                              \
+        if (e_ != hipSuccess) {                                                           \
+            *err = std::string("isosurface: ") + #x + ": " + hipGetErrorString(e_);      \
+            return BBFMM_DEVICE_ERROR;                                                    \
+        }                                                                                 \
+    } while (0)
+
+// Bytes per box node of the clustered extraction: the field (8), the partition (8), cluster and facet counts (4 + 4),
+// their scans (8 + 8).
+constexpr int64_t kClusterNodeBytes = 40;
+
+// The per-node state of the clustered extraction, shared by the isovalues of a call.
+struct ClusterState {
+    double *f = nullptr; // (nk + 2) planes: NaN below and above
+    uint64_t *part = nullptr;
+    int32_t *ccnt = nullptr, *fcnt = nullptr;
+    int64_t *vbase = nullptr, *foff = nullptr;
+    void *scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    unsigned long long *d_stats = nullptr; // 16 counters
+    int32_t *d_found = nullptr;
+};
+
+// The clustered mesh of one isovalue of the resident field (DESIGN.md "Isosurfaces on the RMT lattice", clustering).
+int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, Pool &pool, hipStream_t st,
+                    Mesh *mesh, std::string *err) {
+    const int g = grid_for(s.nodes);
+    const size_t nodes = static_cast<size_t>(s.nodes);
+    ISO_HIP(hipMemsetAsync(c.d_stats, 0, 16 * sizeof(unsigned long long), st));
+    near_topology_kernel<<<g, kThreads, 0, st>>>(s, nk, c.f, iso, c.part, c.ccnt, c.d_stats);
+    ISO_HIP(hipGetLastError());
+    double *verts = nullptr;
+    int64_t *vinfo = nullptr, *facets = nullptr;
+    uint8_t *vflag = nullptr;
+    int64_t nv = 0, nf = 0;
+    // candidates and facets of the current partition
+    auto march = [&]() -> int {
+        pool.put(verts);
+        pool.put(vinfo);
+        pool.put(facets);
+        pool.put(vflag);
+        size_t bytes = c.scan_bytes;
+        ISO_HIP(rocprim::exclusive_scan(c.scan_tmp, bytes, c.ccnt, c.vbase, int64_t(0), nodes, rocprim::plus<int64_t>(), st));
+        int64_t last = 0;
+        int32_t lastc = 0;
+        ISO_HIP(hipMemcpyAsync(&last, c.vbase + s.nodes - 1, 8, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipMemcpyAsync(&lastc, c.ccnt + s.nodes - 1, 4, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipStreamSynchronize(st));
+        nv = last + lastc;
+        if (nv >= (int64_t(1) << 32)) {
+            *err = "isosurface: " + std::to_string(nv) + " clusters, mesh edges are keyed by two 32-bit vertex ids (use a coarser resolution)";
+            return BBFMM_BAD_ARGUMENT;
+        }
+        ISO_HIP(pool.get(&verts, 3 * static_cast<size_t>(nv)));
+        ISO_HIP(pool.get(&vinfo, static_cast<size_t>(nv)));
+        ISO_HIP(pool.get(&vflag, static_cast<size_t>(nv)));
+        candidates_kernel<<<g, kThreads, 0, st>>>(s, c.f, iso, c.part, c.vbase, verts, vinfo);
+        ISO_HIP(hipGetLastError());
+        cluster_count_kernel<<<g, kThreads, 0, st>>>(s, tt, c.f, iso, c.part, c.vbase, c.fcnt);
+        ISO_HIP(hipGetLastError());
+        bytes = c.scan_bytes;
+        ISO_HIP(rocprim::exclusive_scan(c.scan_tmp, bytes, c.fcnt, c.foff, int64_t(0), nodes, rocprim::plus<int64_t>(), st));
+        ISO_HIP(hipMemcpyAsync(&last, c.foff + s.nodes - 1, 8, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipMemcpyAsync(&lastc, c.fcnt + s.nodes - 1, 4, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipStreamSynchronize(st));
+        nf = last + lastc;
+        ISO_HIP(pool.get(&facets, 3 * static_cast<size_t>(nf)));
+        cluster_facets_kernel<<<g, kThreads, 0, st>>>(s, tt, c.f, iso, c.part, c.vbase, c.fcnt, c.foff, facets);
+        ISO_HIP(hipGetLastError());
+        return BBFMM_OK;
+    };
+    int rc = march();
+    if (rc != BBFMM_OK) return rc;
+    // round 0: pass A (predicted edges); rounds 1..4: pass B (non-manifold rollback).  Both split clusters of the
+    // partition and march again; the host only learns whether a round flagged anything.
+    for (int round = 0; round <= kRoundsB && nf > 0; ++round) {
+        const size_t m = 3 * static_cast<size_t>(nf);
+        uint64_t *k_in = nullptr, *k_out = nullptr;
+        int64_t *v_in = nullptr, *v_out = nullptr;
+        uint8_t *tmp = nullptr;
+        ISO_HIP(pool.get(&k_in, m));
+        ISO_HIP(pool.get(&k_out, m));
+        ISO_HIP(pool.get(&v_in, m));
+        ISO_HIP(pool.get(&v_out, m));
+        size_t tmp_bytes = 0;
+        ISO_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, m, 0, 64, st));
+        ISO_HIP(pool.get(&tmp, tmp_bytes));
+        facet_edges_kernel<<<grid_for(nf), kThreads, 0, st>>>(nf, facets, k_in, v_in);
+        ISO_HIP(hipGetLastError());
+        ISO_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, k_in, k_out, v_in, v_out, m, 0, 64, st));
+        ISO_HIP(hipMemsetAsync(vflag, 0, static_cast<size_t>(std::max<int64_t>(nv, 1)), st));
+        ISO_HIP(hipMemsetAsync(c.d_found, 0, sizeof(int32_t), st));
+        const bool pass_b = round > 0;
+        flag_over_used_kernel<<<grid_for(static_cast<int64_t>(m)), kThreads, 0, st>>>(
+            static_cast<int64_t>(m), k_out, v_out, facets, vinfo, pass_b, vflag, c.d_found,
+            c.d_stats + (pass_b ? kStatOverB + round - 1 : kStatOverA));
+        ISO_HIP(hipGetLastError());
+        int32_t found = 0;
+        ISO_HIP(hipMemcpyAsync(&found, c.d_found, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipStreamSynchronize(st));
+        pool.put(k_in);
+        pool.put(k_out);
+        pool.put(v_in);
+        pool.put(v_out);
+        pool.put(tmp);
+        if (!found) {
+            if (pass_b) break;
+            continue;
+        }
+        split_clusters_kernel<<<g, kThreads, 0, st>>>(s, c.vbase, vflag, c.part, c.ccnt, c.d_stats + kStatSplitA,
+                                                      c.d_stats + kStatRolledB + (pass_b ? round - 1 : 0));
+        ISO_HIP(hipGetLastError());
+        if ((rc = march()) != BBFMM_OK) return rc;
+    }
+    unsigned long long h_stats[16];
+    ISO_HIP(hipMemcpyAsync(h_stats, c.d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+    mesh->vertices.resize(3 * static_cast<size_t>(nv));
+    mesh->facets.resize(3 * static_cast<size_t>(nf));
+    if (nv) ISO_HIP(hipMemcpyAsync(mesh->vertices.data(), verts, mesh->vertices.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (nf) ISO_HIP(hipMemcpyAsync(mesh->facets.data(), facets, mesh->facets.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ISO_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
+    pool.put(verts);
+    pool.put(vinfo);
+    pool.put(facets);
+    pool.put(vflag);
+    return BBFMM_OK;
+}
 
 } // namespace
 
@@ -412,14 +783,6 @@ bool make_lattice(const double *extents, double resolution, Lattice *out, std::s
 
 int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t st, std::vector<Mesh> *meshes,
             std::string *err) {
-#define ISO_HIP(x)                                                                        \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            *err = std::string("isosurface: ") + #x + ": " + hipGetErrorString(e_);      \
-            return BBFMM_DEVICE_ERROR;                                                    \
-        }                                                                                 \
-    } while (0)
     TetTables tt;
     if (!make_tet_tables(&tt)) {
         *err = "isosurface: internal error (a tetrahedron edge is not a lattice edge)";
@@ -427,6 +790,11 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     }
     const int64_t ni = lat.dims[0], nj = lat.dims[1], nk = lat.dims[2], P = ni * nj;
     const int n_iso = req.n_iso;
+    const bool cluster = req.cluster == kClusterAverage;
+    if (req.cluster != kClusterNone && !cluster) {
+        *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
+        return BBFMM_BAD_ARGUMENT;
+    }
     // bytes per k-plane: field, flags, indices, targets and the evaluator's per-target buffers; per isovalue masks,
     // vertex ids, counts and offsets
     const int64_t per_plane = P * (8 + 4 + 4 + 128 + 40 * static_cast<int64_t>(n_iso));
@@ -439,6 +807,21 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     int64_t nb = budget / std::max<int64_t>(per_plane, 1);
     nb = std::max<int64_t>(G, std::min<int64_t>(nb, std::min(nk, plane_cap)) / G * G);
 
+    // Clustering looks at the whole mesh, so the field of every batch is kept and the extraction runs once over the whole
+    // lattice: refused before any work where that state does not fit.
+    if (cluster) {
+        size_t free_b = 0, total_b = 0;
+        ISO_HIP(hipMemGetInfo(&free_b, &total_b));
+        const double need = static_cast<double>(kClusterNodeBytes) * static_cast<double>(nk + 2) * static_cast<double>(P) +
+                            static_cast<double>(per_plane) * static_cast<double>(nb);
+        if (need > static_cast<double>(free_b)) {
+            *err = "isosurface: cluster=average keeps " + std::to_string(kClusterNodeBytes) + " bytes per node of the " +
+                   std::to_string(ni) + " x " + std::to_string(nj) + " x " + std::to_string(nk) + " lattice box on the device, about " +
+                   std::to_string(static_cast<int64_t>(need / 1048576.0)) + " MiB with one batch; " +
+                   std::to_string(free_b / 1048576) + " MiB are free (use a coarser resolution or smaller extents)";
+            return BBFMM_BAD_ARGUMENT;
+        }
+    }
     Pool pool;
     int32_t *d_erows = nullptr, *d_krows = nullptr, *flag = nullptr, *idx = nullptr, *vcnt = nullptr, *fcnt = nullptr;
     double *f = nullptr, *xs[3] = {nullptr, nullptr, nullptr}, *vals = nullptr;
@@ -465,8 +848,22 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     scan_bytes = std::max(scan_bytes, b2);
     void *scan_tmp = nullptr;
     ISO_HIP(pool.get(reinterpret_cast<uint8_t **>(&scan_tmp), scan_bytes));
-    std::vector<IsoState> states(n_iso);
-    for (int q = 0; q < n_iso; ++q) {
+    ClusterState cs;
+    if (cluster) {
+        const size_t box = static_cast<size_t>(nk * P);
+        ISO_HIP(pool.get(&cs.f, box + 2 * P));
+        ISO_HIP(pool.get(&cs.part, box));
+        ISO_HIP(pool.get(&cs.ccnt, box));
+        ISO_HIP(pool.get(&cs.fcnt, box));
+        ISO_HIP(pool.get(&cs.vbase, box));
+        ISO_HIP(pool.get(&cs.foff, box));
+        ISO_HIP(pool.get(&cs.d_stats, 16));
+        ISO_HIP(pool.get(&cs.d_found, 1));
+        ISO_HIP(rocprim::exclusive_scan(nullptr, cs.scan_bytes, cs.ccnt, cs.vbase, int64_t(0), box, rocprim::plus<int64_t>(), st));
+        ISO_HIP(pool.get(reinterpret_cast<uint8_t **>(&cs.scan_tmp), cs.scan_bytes));
+    }
+    std::vector<IsoState> states(cluster ? 0 : n_iso);
+    for (int q = 0; q < static_cast<int>(states.size()); ++q) {
         states[q].iso = req.isovalues[q];
         ISO_HIP(pool.get(&states[q].mask, slab_nodes + P));
         ISO_HIP(pool.get(&states[q].vbase, slab_nodes + P));
@@ -477,6 +874,10 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     {
         std::vector<double> nan_plane(static_cast<size_t>(P), std::numeric_limits<double>::quiet_NaN());
         ISO_HIP(hipMemcpyAsync(f, nan_plane.data(), P * sizeof(double), hipMemcpyHostToDevice, st));
+        if (cluster) { // planes k = -1 and k = nk of the resident field
+            ISO_HIP(hipMemcpyAsync(cs.f, nan_plane.data(), P * sizeof(double), hipMemcpyHostToDevice, st));
+            ISO_HIP(hipMemcpyAsync(cs.f + (nk + 1) * P, nan_plane.data(), P * sizeof(double), hipMemcpyHostToDevice, st));
+        }
         ISO_HIP(hipStreamSynchronize(st)); // (pageable source)
     }
     int64_t *h_tot = nullptr;
@@ -560,6 +961,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         ISO_HIP(hipGetLastError());
         if (req.d_field_out)
             ISO_HIP(hipMemcpyAsync(req.d_field_out + k0 * P, f + P, s.nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if (cluster) ISO_HIP(hipMemcpyAsync(cs.f + (k0 + 1) * P, f + P, s.nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
         for (IsoState &is : states) {
             classify_kernel<<<g, kThreads, 0, st>>>(s, tt, f, is.iso, is.mask, vcnt, fcnt);
             ISO_HIP(hipGetLastError());
@@ -589,6 +991,14 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         ISO_HIP(hipMemcpyAsync(f, f + nbc * P, P * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     meshes->assign(n_iso, Mesh());
+    if (cluster) {
+        const Slab box = slab_for(0, nk);
+        for (int q = 0; q < n_iso; ++q) {
+            const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], pool, st, &(*meshes)[q], err);
+            if (rc != BBFMM_OK) return rc;
+        }
+        return BBFMM_OK;
+    }
     for (int q = 0; q < n_iso; ++q) {
         Mesh &mh = (*meshes)[q];
         mh.vertices.resize(3 * static_cast<size_t>(states[q].vtotal));

@@ -1,7 +1,9 @@
-// Dense marching tetrahedra on the regularised-marching-tetrahedra (RMT) sampling lattice: the raw triangles of
-// ferreus_rmt's build_isosurface with ClusterMethod::None, before clipping, cleaning and boundary closure, taken from
-// every sample point of the extraction domain in one device pass instead of a CPU wavefront.  Contract: DESIGN.md
-// "Isosurfaces on the RMT lattice"; numpy restatement: tests/isosurface_restatement.py.
+// Dense marching tetrahedra on the regularised-marching-tetrahedra (RMT) sampling lattice: the triangles of
+// ferreus_rmt's build_isosurface with ClusterMethod::None (raw, one vertex per crossed lattice edge) or
+// ClusterMethod::Average (the intersections near a sample point merged where the topology tests allow it, with the
+// predicted-edge and non-manifold rollbacks), before clipping, cleaning and boundary closure, taken from every sample
+// point of the extraction domain in device passes instead of a CPU wavefront.  Contract: DESIGN.md "Isosurfaces on the
+// RMT lattice"; numpy restatements: tests/isosurface_restatement.py and tests/isosurface_cluster_restatement.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +35,139 @@ constexpr int kMtTable[16][2][3] = {
 constexpr int kPad = 2;             // OPEN_CLIP_IJK_PADDING (lattice.rs:119)
 constexpr double kInsideEps = 1e-9; // is_inside (isosurface.rs:286-289)
 
+// ---- vertex clustering (ferreus_rmt/src/topology.rs; values checked against tests/golden/rmt_cluster_tables.json)
+constexpr uint16_t kAll14 = (1u << 14) - 1; // ALL14_MASK
+// Table 3: the edges of a sample point that neighbour each edge (NEIGHBOUR_MASKS)
+constexpr uint16_t kNeighbourMasks[14] = {0x321A, 0x2015, 0x24B2, 0x0251, 0x006F, 0x00D4, 0x03B8,
+                                          0x0D64, 0x0AC0, 0x1949, 0x2884, 0x3780, 0x2A01, 0x1C07};
+// Table 4: flat-hole rows, edges OA/OB without and OC/OD with a near intersection (FLAT_HOLE_MASKS)
+constexpr uint16_t kFlatHoleMasks[36][2] = {
+    {0x0003, 0x2010}, {0x0009, 0x0210}, {0x0011, 0x000A}, {0x0201, 0x1008}, {0x1001, 0x2200}, {0x2001, 0x1002},
+    {0x0006, 0x2010}, {0x0012, 0x0005}, {0x2002, 0x0005}, {0x0014, 0x0022}, {0x0024, 0x0090}, {0x0084, 0x0420},
+    {0x0404, 0x2080}, {0x2004, 0x0402}, {0x0018, 0x0041}, {0x0048, 0x0210}, {0x0208, 0x0041}, {0x0030, 0x0044},
+    {0x0050, 0x0028}, {0x0060, 0x0090}, {0x00A0, 0x0044}, {0x00C0, 0x0120}, {0x0140, 0x0280}, {0x0240, 0x0108},
+    {0x0180, 0x0840}, {0x0480, 0x0804}, {0x0880, 0x0500}, {0x0300, 0x0840}, {0x0900, 0x0280}, {0x0A00, 0x1100},
+    {0x1200, 0x0801}, {0x0C00, 0x2080}, {0x2400, 0x0804}, {0x1800, 0x2200}, {0x2800, 0x1400}, {0x3000, 0x0801}};
+
+// The cases of test_topology (topology.rs:232-314) in the order of the stats, and the case of a sample point whose 14
+// neighbours are not all in E (singletons; the reference evaluates the missing ones instead, isosurface.rs:668-697).
+enum TopologyCase : int { kClosed = 0, kMultiHole = 1, kFlatHole = 2, kMultiSurface = 3, kSimple = 4, kIncomplete = 5 };
+
+// A partition of a near mask into clusters: 4 bits per edge, the lowest edge of its cluster, 15 for an edge not in the
+// mask.
+constexpr uint64_t kNoClusters = ~uint64_t(0);
+__host__ __device__ inline int part_label(uint64_t part, int e) { return static_cast<int>((part >> (4 * e)) & 15u); }
+__host__ __device__ inline uint64_t part_set(uint64_t part, int e, int label) {
+    return (part & ~(uint64_t(15) << (4 * e))) | (uint64_t(label) << (4 * e));
+}
+__host__ __device__ inline uint16_t part_mask(uint64_t part) { // the edges it holds
+    uint16_t m = 0;
+    for (int e = 0; e < 14; ++e)
+        if (part_label(part, e) != 15) m |= uint16_t(1u << e);
+    return m;
+}
+__host__ __device__ inline uint16_t part_leaders(uint64_t part) { // the lowest edge of every cluster
+    uint16_t m = 0;
+    for (int e = 0; e < 14; ++e)
+        if (part_label(part, e) == e) m |= uint16_t(1u << e);
+    return m;
+}
+__host__ __device__ inline uint64_t part_singletons(uint16_t mask) { // do_not_cluster (topology.rs:224-228)
+    uint64_t p = kNoClusters;
+    for (int e = 0; e < 14; ++e)
+        if (mask & (1u << e)) p = part_set(p, e, e);
+    return p;
+}
+__host__ __device__ inline uint64_t part_one(uint64_t part, uint16_t comp) { // one cluster of the edges of comp
+    int lead = 0;
+    while (!(comp & (1u << lead))) ++lead;
+    for (int e = lead; e < 14; ++e)
+        if (comp & (1u << e)) part = part_set(part, e, lead);
+    return part;
+}
+
+// The component of `seed` (one bit) among the edges of `within` under kNeighbourMasks: a bit-parallel flood of at most
+// 14 steps (connected_components_masks, topology.rs:106-133; the components are the same sets whatever the order).
+__host__ __device__ inline uint16_t topology_component(uint16_t seed, uint16_t within) {
+    uint16_t comp = seed;
+    for (int step = 0; step < 14; ++step) {
+        uint16_t grow = comp;
+        for (int e = 0; e < 14; ++e)
+            if (comp & (1u << e)) grow |= kNeighbourMasks[e];
+        grow &= within;
+        if (grow == comp) break;
+        comp = grow;
+    }
+    return comp;
+}
+
+__host__ __device__ inline bool topology_inside(double g) { return g < -1e-9; } // is_inside (topology.rs:156-160)
+
+// crossing_alpha(a, b).is_some_and(|t| t < 0.5) (topology.rs:162-169 with lerp_alpha, isosurface.rs:173-181)
+__host__ __device__ inline bool topology_near(double a, double b) {
+    if (topology_inside(a) == topology_inside(b)) return false;
+    const double den = a - b;
+    double t = 0.5;
+    if (!((den < 0 ? -den : den) < 1e-30)) {
+        t = a / den;
+        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    }
+    return t < 0.5;
+}
+
+// is_flat_hole (topology.rs:180-221); v: g at the 14 neighbours, a row that reads a non-finite one is skipped
+__host__ __device__ inline bool topology_flat_hole(uint16_t m, const double *v) {
+    for (int r = 0; r < 36; ++r) {
+        const uint16_t em = kFlatHoleMasks[r][0], om = kFlatHoleMasks[r][1];
+        if ((m & em) != 0 || (m & om) != om) continue;
+        int ab[2] = {0, 0}, cd[2] = {0, 0}, na = 0, nc = 0;
+        for (int e = 0; e < 14; ++e) {
+            if ((em >> e) & 1) ab[na++ & 1] = e;
+            if ((om >> e) & 1) cd[nc++ & 1] = e;
+        }
+        if (na != 2 || nc != 2) continue;
+        const double a = v[ab[0]], b = v[ab[1]], c = v[cd[0]], d = v[cd[1]];
+        // finite: x - x == 0 fails for NaN and the infinities
+        if (!(a - a == 0.0) || !(b - b == 0.0) || !(c - c == 0.0) || !(d - d == 0.0)) continue;
+        if ((topology_near(a, d) && topology_near(a, c)) || (topology_near(b, d) && topology_near(b, c))) return true;
+    }
+    return false;
+}
+
+// test_topology (topology.rs:232-314) of a near mask with clustering on.  values: g at the 14 neighbours, or null to
+// leave out the flat-hole test.  An empty mask is a simple surface without clusters.
+__host__ __device__ inline uint64_t topology_partition(uint16_t mask, const double *values, int *case_out) {
+    const uint16_t m = mask & kAll14;
+    *case_out = kSimple;
+    if (m == 0) return kNoClusters;
+    if (m == kAll14) {
+        *case_out = kClosed;
+        return part_singletons(m);
+    }
+    const uint16_t first = topology_component(uint16_t(m & (~m + 1)), m);
+    if (first != m) {
+        *case_out = kMultiSurface;
+        uint64_t p = kNoClusters;
+        uint16_t rest = m;
+        while (rest) {
+            const uint16_t comp = topology_component(uint16_t(rest & (~rest + 1)), rest);
+            p = part_one(p, comp);
+            rest = uint16_t(rest & ~comp);
+        }
+        return p;
+    }
+    const uint16_t holes = uint16_t(kAll14 & ~m);
+    if (topology_component(uint16_t(holes & (~holes + 1)), holes) != holes) {
+        *case_out = kMultiHole;
+        return part_singletons(m);
+    }
+    if (values && topology_flat_hole(m, values)) {
+        *case_out = kFlatHole;
+        return part_singletons(m);
+    }
+    return part_one(kNoClusters, m);
+}
+
 // The extraction domain of (extents, resolution), host-side (SampleLattice::new, lattice.rs:55-96).
 struct Lattice {
     double lo_world[3] = {0, 0, 0}, spacing[3] = {0, 0, 0};
@@ -51,7 +186,15 @@ bool make_lattice(const double *extents, double resolution, Lattice *out, std::s
 struct Mesh {
     std::vector<double> vertices;
     std::vector<int64_t> facets;
+    int64_t stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // kStat*, all 0 without clustering
 };
+
+// Mesh::stats: [0, 6) sample points per TopologyCase; mesh edges with more than 2 faces before pass A and the clusters
+// pass A split (isosurface.rs:798-878); per round of pass B (isosurface.rs:888-930) the sample points rolled back and
+// the mesh edges with more than 2 faces it found.
+constexpr int kStatOverA = 6, kStatSplitA = 7, kStatRolledB = 8, kStatOverB = 12, kRoundsB = 4;
+
+enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1 };
 
 // Field values at m lattice nodes (SoA world coordinates on the device), written to d_vals[0..m) on the stream.
 // d_vals == nullptr: only check that every node can be evaluated (BBFMM_POINT_OUTSIDE_TREE otherwise).
@@ -64,9 +207,12 @@ struct Request {
     const double *host_field = nullptr; // caller's field over the box of E (then no FieldFn is used)
     double *d_field_out = nullptr;     // device array over the box of E receiving the field (NaN off E), or null
     int64_t budget_bytes = 0;          // device memory for one batch of k-planes (<= 0: the default)
+    int cluster = kClusterNone;        // kClusterAverage: the whole lattice field stays on the device (see extract)
 };
 
-// Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.
+// Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.  With kClusterAverage
+// the field is evaluated in the same batches but kept over the whole box (40 bytes of state per box node, refused before
+// any work where that does not fit), and each isovalue is then clustered and marched over the whole lattice.
 int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t stream, std::vector<Mesh> *out,
             std::string *err);
 

@@ -1,9 +1,12 @@
 """Isosurfaces on the regularised-marching-tetrahedra (RMT) sampling lattice, extracted on the device.
 
-The mesh is ferreus_rmt's raw marching-tetrahedra output (`build_isosurface` with `ClusterMethod::None`,
-ferreus_rmt/src/isosurface.rs:489-) before `clip_mesh_to_aabb`, `clean_mesh` and boundary closure, taken over every
-sample point of the extraction domain instead of the sample points a seeded wavefront reaches (DESIGN.md "Isosurfaces
-on the RMT lattice"):
+The mesh is ferreus_rmt's marching-tetrahedra output (`build_isosurface`, ferreus_rmt/src/isosurface.rs:489-) before
+`clip_mesh_to_aabb`, `clean_mesh` and boundary closure, taken over every sample point of the extraction domain instead
+of the sample points a seeded wavefront reaches (DESIGN.md "Isosurfaces on the RMT lattice").  `cluster="none"` (the
+default) is its `ClusterMethod::None`, one vertex per crossed lattice edge; `cluster="average"` its
+`ClusterMethod::Average`: the intersections near a sample point are merged into their mean where the topology tests
+allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 faces are split again
+(isosurface.rs:798-930); the reference's later self-intersection rollback is not run.
 
 * lattice (lattice.rs:55-96): spacing [r/2, r*sqrt2/2, r/sqrt2], max_ijk = ceil((hi - lo) / spacing), max_ijk[0] += 1,
   world(ijk) = lo + ijk * spacing;
@@ -12,7 +15,9 @@ on the RMT lattice"):
   evaluated; inside means f - isovalue < -1e-9 (isosurface.rs:286-289);
 * one vertex per lattice edge of E with finite ends on opposite sides, placed from the end that holds it under the
   wavefront's t < 0.5 rule (isosurface.rs:588-610) with lerp_alpha (isosurface.rs:173-181);
-* facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order.
+* facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order;
+* cluster="average": one vertex per cluster, ordered by sample point and lowest edge; triangles that two corners of
+  share a vertex are dropped; `return_stats=True` adds the counts of `STATS` per mesh.
 
 Lattice fields are arrays of shape (nk, nj, ni) over the bounding box of E (`lattice_info(...)["shape"]`, entry
 [0, 0, 0] at ijk `lattice_info(...)["lo"]`); entries off E are ignored, and NaN in returned fields.
@@ -92,7 +97,54 @@ def tables() -> dict:
             "MT_TABLE": [mt[c, 1:1 + 3 * mt[c, 0]].reshape(-1, 3).tolist() for c in range(16)]}
 
 
-def _meshes(lib, res):
+CLUSTER_METHODS = {"none": 0, "average": 1}
+# return_stats: sample points per topology case, then the two rollback passes (bbfmm_isosurface_stats)
+STATS = ("closed", "multi_hole", "flat_hole", "multi_surface", "simple", "incomplete")
+
+
+def _cluster(cluster):
+    if cluster not in CLUSTER_METHODS:
+        raise ValueError(f"cluster must be one of {sorted(CLUSTER_METHODS)}, got {cluster!r}")
+    return CLUSTER_METHODS[cluster]
+
+
+def cluster_tables() -> dict:
+    """The clustering tables the library holds (ferreus_rmt/src/constants.rs)."""
+    lib = L.load()
+    nb, fh, all14 = np.zeros(14, np.int32), np.zeros(72, np.int32), ctypes.c_int32()
+    rc = lib.bbfmm_isosurface_cluster_tables(nb.ctypes.data, fh.ctypes.data, ctypes.byref(all14))
+    assert rc == L.OK
+    return {"NEIGHBOUR_MASKS": nb.tolist(), "FLAT_HOLE_MASKS": fh.reshape(36, 2).tolist(), "ALL14_MASK": all14.value}
+
+
+def topology(near_mask, neighbour_values=None):
+    """(case, cluster_of_edge[14]) of a 14-bit near mask by the function the device runs (test_topology,
+    topology.rs:232-314): case 0 closed, 1 multi-hole, 2 flat-hole, 3 multi-surface, 4 simple; cluster_of_edge the lowest
+    edge of each edge's cluster, -1 off the mask.  neighbour_values: f - isovalue at the 14 neighbours, None to leave out
+    the flat-hole test."""
+    lib = L.load()
+    case, lab = ctypes.c_int32(), np.zeros(14, np.int32)
+    v = None
+    if neighbour_values is not None:
+        v = np.ascontiguousarray(np.asarray(neighbour_values, dtype=np.float64).reshape(-1))
+        if v.shape != (14,):
+            raise ValueError("neighbour_values must hold 14 values")
+    rc = lib.bbfmm_isosurface_topology(int(near_mask), v.ctypes.data if v is not None else None, ctypes.byref(case),
+                                       lab.ctypes.data)
+    if rc != L.OK:
+        raise ValueError("near_mask must be a 14-bit mask")
+    return case.value, lab
+
+
+def _stats(lib, res, i):
+    s = np.zeros(16, dtype=np.int64)
+    lib.bbfmm_isosurface_stats(res, i, s.ctypes.data)
+    out = {name: int(s[q]) for q, name in enumerate(STATS)}
+    out.update(over_used_a=int(s[6]), split_a=int(s[7]), rolled_b=s[8:12].tolist(), over_used_b=s[12:16].tolist())
+    return out
+
+
+def _meshes(lib, res, stats=False):
     out = []
     for i in range(lib.bbfmm_isosurface_count(res)):
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
@@ -100,7 +152,7 @@ def _meshes(lib, res):
         v = np.empty((nv.value, 3), dtype=np.float64)
         f = np.empty((nf.value, 3), dtype=np.int64)
         lib.bbfmm_isosurface_copy(res, i, v.ctypes.data, f.ctypes.data)
-        out.append((v, f))
+        out.append((v, f, _stats(lib, res, i)) if stats else (v, f))
     return out
 
 
@@ -115,10 +167,12 @@ def _raise(rc, msg, leaf=True):
     raise FmmError(msg)
 
 
-def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0):
+def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0,
+                      cluster="none", return_stats=False):
     """Meshes of the tree's field (set_local_coefficients first, one column) at each isovalue, one field evaluation
     for all of them; see FmmTree.build_isosurfaces."""
     lib = L.load()
+    method = _cluster(cluster)
     ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
     field_t = None
     if return_field:
@@ -128,14 +182,14 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
         field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
         torch.cuda.synchronize(field_t.device)
     res = ctypes.c_void_p()
-    rc = lib.bbfmm_build_isosurfaces(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
-                                     d.ctypes.data if d is not None else None,
-                                     field_t.data_ptr() if field_t is not None else None, int(batch_bytes),
-                                     ctypes.byref(res))
+    rc = lib.bbfmm_build_isosurfaces_ex(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
+                                        d.ctypes.data if d is not None else None,
+                                        field_t.data_ptr() if field_t is not None else None, int(batch_bytes), method,
+                                        ctypes.byref(res))
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_last_error(tree._h).decode())
-        meshes = _meshes(lib, res)
+        meshes = _meshes(lib, res, return_stats)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
@@ -144,10 +198,13 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
     return meshes
 
 
-def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None):
+def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None,
+                            cluster="none", return_stats=False):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
-    current device (or the tree's)."""
+    current device (or the tree's).  cluster: "none" or "average" (see the module); return_stats: (vertices, facets,
+    stats) per mesh, stats the clustering counts (all 0 with "none")."""
     lib = L.load()
+    method = _cluster(cluster)
     ext, iso = _ext(extents), _isovalues(isovalues)
     vals = np.ascontiguousarray(np.asarray(lattice_values, dtype=np.float64))
     info = lattice_info(ext, resolution, tree)
@@ -155,17 +212,20 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
         raise ValueError(f"lattice_values must have shape {info['shape']}, got {vals.shape}")
     res = ctypes.c_void_p()
     h = tree._h if tree is not None else None
-    rc = lib.bbfmm_isosurfaces_from_values(h, vals.ctypes.data, ext.ctypes.data, float(resolution), iso.ctypes.data,
-                                           len(iso), int(batch_bytes), ctypes.byref(res))
+    rc = lib.bbfmm_isosurfaces_from_values_ex(h, vals.ctypes.data, ext.ctypes.data, float(resolution), iso.ctypes.data,
+                                              len(iso), int(batch_bytes), method, ctypes.byref(res))
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
-        return _meshes(lib, res)
+        return _meshes(lib, res, return_stats)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
 
 
-def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None):
-    """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue."""
-    return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree)[0]
+def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None,
+                           cluster="none", return_stats=False):
+    """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue, and its stats when
+    return_stats."""
+    return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree,
+                                   cluster=cluster, return_stats=return_stats)[0]

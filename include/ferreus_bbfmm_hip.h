@@ -223,8 +223,8 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
                                          int64_t *bad_point_index);
 
 /* ---- Isosurfaces: dense marching tetrahedra on the RMT sampling lattice (ferreus_rmt build_isosurface with
- * ClusterMethod::None, before clipping, cleaning and boundary closure; contract in DESIGN.md "Isosurfaces on the RMT
- * lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
+ * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE its ClusterMethod::Average, before clipping,
+ * cleaning and boundary closure; contract in DESIGN.md "Isosurfaces on the RMT lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
  * nk x nj x ni doubles (i fastest) over the bounding box of the extraction nodes E; entries off E are ignored (NaN in
  * returned fields).  Vertices are n x 3 doubles, facets m x 3 int64 vertex ids, both row-major. */
 typedef struct bbfmm_isosurface_result bbfmm_isosurface_result; /* the meshes of one call, one per isovalue */
@@ -249,6 +249,32 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
 int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                   const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
                                   bbfmm_isosurface_result **out);
+/* Vertex clustering.  BBFMM_CLUSTER_NONE: one vertex per crossed lattice edge (the entries above).
+ * BBFMM_CLUSTER_AVERAGE: the intersections near a sample point are merged into their mean where the topology tests of
+ * ferreus_rmt allow it (topology.rs:232-314), then clusters that give a mesh edge more than 2 faces are split again
+ * (isosurface.rs:798-930); the self-intersection rollback of the reference is not run.  The whole lattice field then
+ * stays on the device (40 bytes per node of the nk x nj x ni box); a lattice that does not fit is refused before any
+ * work with BBFMM_BAD_ARGUMENT.  The meshes do not depend on batch_bytes. */
+#define BBFMM_CLUSTER_NONE 0
+#define BBFMM_CLUSTER_AVERAGE 1
+int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                               int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                               int32_t cluster_method, bbfmm_isosurface_result **out);
+int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                     const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                     int32_t cluster_method, bbfmm_isosurface_result **out);
+/* The clustering counts of mesh i, stats_out[16] (all 0 with BBFMM_CLUSTER_NONE): sample points per topology case
+ * [closed, multi-hole, flat-hole, multi-surface, simple, incomplete (a neighbour outside the extraction nodes: not
+ * clustered)]; [6] mesh edges with more than 2 faces before pass A, [7] clusters pass A split; [8..12) sample points
+ * rolled back in rounds 1..4 of pass B, [12..16) mesh edges with more than 2 faces those rounds found. */
+int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* Host only: the topology test the device runs, for one 14-bit near mask.  neighbour_values: f - isovalue at the 14
+ * neighbours (EDGE_DELTAS order), or NULL to leave out the flat-hole test.  case_out: 0 closed, 1 multi-hole, 2 flat-hole,
+ * 3 multi-surface, 4 simple.  cluster_of_edge[14]: the lowest edge of the cluster of each edge, -1 off the mask. */
+int bbfmm_isosurface_topology(uint32_t near_mask, const double *neighbour_values, int32_t *case_out,
+                              int32_t *cluster_of_edge);
+/* The clustering tables as the product holds them: NEIGHBOUR_MASKS (14), FLAT_HOLE_MASKS (36 x 2), ALL14_MASK. */
+int bbfmm_isosurface_cluster_tables(int32_t *neighbour_masks, int32_t *flat_hole_masks, int32_t *all14_mask);
 int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r);
 int bbfmm_isosurface_size(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_vertices, int64_t *n_facets);
 int bbfmm_isosurface_copy(const bbfmm_isosurface_result *r, int32_t i, double *vertices, int64_t *facets);

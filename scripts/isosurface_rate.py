@@ -1,9 +1,11 @@
 """Rate of the device isosurface extraction (FmmTree.build_isosurface): the albatite Spheroidal example at resolution
 5 (examples/isosurface_spheroidal.rs) and a 1M-point cloud.  Reports the field pass alone (return_field off, one
 isovalue; measured as the extraction of an isovalue that no node crosses), the whole call, the extraction share
-(whole minus field) and triangles per second: one JSON line per case, and the list to --out when given.
+(whole minus field) and triangles per second: one JSON line per case, and the list to --out when given.  With
+--clusters none,average every case is timed with each method in the same run on the same tree (the field pass is the
+same work for both), and the clustering counts are recorded.
 
-    python scripts/isosurface_rate.py [--repeats 3] [--out FILE]
+    python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--out FILE]
 """
 import argparse
 import json
@@ -27,15 +29,19 @@ def timed(fn, repeats):
     return min(ts) * 1e3, out
 
 
-def measure(te, ext, res, iso, repeats, label):
+def measure(te, ext, res, iso, repeats, label, cluster="none"):
     from ferreus_rbf_rs_amd import isosurface as I
     info = I.lattice_info(ext, res)
-    t_all, (v, f) = timed(lambda: te.build_isosurface(ext, res, iso), repeats)
-    t_field, _ = timed(lambda: te.build_isosurface(ext, res, 1e300), repeats)   # nothing crosses: field + classify
-    rec = {"case": label, "resolution": res, "lattice_shape": list(info["shape"]), "nodes_evaluated": info["n_nodes"],
+    kw = {"cluster": cluster, "return_stats": True}
+    t_all, (v, f, stats) = timed(lambda: te.build_isosurface(ext, res, iso, **kw), repeats)
+    t_field, _ = timed(lambda: te.build_isosurface(ext, res, 1e300, **kw), repeats)   # nothing crosses: field + classify
+    rec = {"case": label, "cluster": cluster, "resolution": res, "lattice_shape": list(info["shape"]),
+           "nodes_evaluated": info["n_nodes"],
            "keys": info["n_keys"], "vertices": int(len(v)), "facets": int(len(f)), "call_ms": t_all,
            "field_ms": t_field, "extraction_ms": t_all - t_field, "triangles_per_s": len(f) / (t_all * 1e-3),
            "nodes_per_s": info["n_nodes"] / (t_all * 1e-3)}
+    if cluster != "none":
+        rec["stats"] = stats
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -43,6 +49,7 @@ def measure(te, ext, res, iso, repeats, label):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--clusters", default="none", help="comma-separated cluster methods, each timed on every case")
     ap.add_argument("--out", default=None, help="JSON file for the list of results")
     a = ap.parse_args()
     import ferreus_rbf_rs_amd as F
@@ -64,7 +71,8 @@ def main():
     te = F.FmmTree(pts, 7, kp, True, False, extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
     te.set_weights(x[:, None].copy())
     te.set_local_coefficients(x[:, None].copy())
-    recs.append(measure(te, ext, res, 0.0, a.repeats, "albatite_spheroidal_r5"))
+    for method in a.clusters.split(","):
+        recs.append(measure(te, ext, res, 0.0, a.repeats, "albatite_spheroidal_r5", method))
     del te, tree, pre
     # 1M points on and around a sphere of radius 1, Linear kernel, random weights (a smooth field, not a fit)
     rng = np.random.default_rng(1)
@@ -79,7 +87,8 @@ def main():
     t1.set_weights(w)
     t1.set_local_coefficients(w)
     fmid = float(np.median(t1.evaluate_leaves(None, p[:2000])))
-    recs.append(measure(t1, ext, res, fmid, a.repeats, "cloud_1M_linear"))
+    for method in a.clusters.split(","):
+        recs.append(measure(t1, ext, res, fmid, a.repeats, "cloud_1M_linear", method))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
