@@ -17,8 +17,9 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libferreus_bbfmm_hip.so")
 
 HOST_SOURCES = ["tree.cpp", "operators.cpp", "fmm_tree.cpp", "fmm_m2l_tables.cpp", "fmm_plans.cpp", "device_group.cpp", "capi.cpp", "solver.cpp", "ddm.cpp", "ddm_solver.cpp", "schwarz.cpp"]
-HIP_SOURCES = ["device.hip", "ddm_kernels.hip", "targets.hip", "schwarz_kernels.hip", "tree_device.hip", "tree_lists_device.hip", "isosurface.hip"]
-HEADERS = ["morton.hpp", "tree.hpp", "parallel.hpp", "kernels.hpp", "operators.hpp", "device.hpp",
+HIP_SOURCES = ["device_l2p.hip", "device_p2p.hip", "device_wx.hip", "device_p2m.hip", "device_m2l.hip", "device_transfer.hip", "device_gather.hip", "device_selftest.hip",  # longest first
+               "ddm_kernels.hip", "targets.hip", "schwarz_kernels.hip", "tree_device.hip", "tree_lists_device.hip", "isosurface.hip"]
+HEADERS = ["morton.hpp", "tree.hpp", "parallel.hpp", "kernels.hpp", "operators.hpp", "device.hpp", "device_common.hpp", "device_direct.hpp",
            "fmm_tree.hpp", "fmm_tree_impl.hpp", "device_group.hpp", "targets.hpp", "ddm.hpp", "ddm_solver.hpp", "ddm_monomials.hpp", "schwarz_kernels.hpp", "tree_device.hpp", "isosurface.hpp", os.path.join(ROOT, "include", "ferreus_bbfmm_hip.h")]
 
 
@@ -134,9 +135,10 @@ def _build(hipcc: str, OBJ: str, LIB: str, force: bool, verbose: bool, sanitize:
         subprocess.check_call(cmd)
         _write_stamp(obj, stamp, digest)
 
-    if todo:  # independent translation units: compile side by side (device.hip alone takes over a minute)
+    if todo:  # independent translation units: compile side by side (the longest one sets the wall time: DESIGN.md section 5)
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(todo), max(1, (os.cpu_count() or 2) // 2))) as pool:
+        workers = int(os.environ.get("MAX_JOBS") or min(16, max(1, (os.cpu_count() or 2) // 2)))  # a shared machine reports more CPUs than a job may use
+        with ThreadPoolExecutor(max_workers=max(1, min(len(todo), workers))) as pool:
             list(pool.map(compile_one, todo))
     lib_digest = hashlib.sha256("".join(digests).encode()).hexdigest()
     lib_stamp = os.path.join(OBJ, "lib.sha256")

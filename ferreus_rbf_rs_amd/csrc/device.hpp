@@ -1,4 +1,4 @@
-// Device-side data structures and kernel launchers (implemented in device.hip).
+// Device-side data structures and kernel launchers (implemented in the device_*.hip files, one per pass family).
 //
 // HBM layout (all f64 unless noted; "sorted" = hierarchical Morton order in which
 // every tree cell owns a contiguous range of points):
@@ -116,7 +116,7 @@ void launch_m2l_basis(const M2lClass *classes, const M2lTileDesc *tiles, int n_t
 void launch_small_gemm(bool trans_a, int M, int N, int Kd, const double *A, int64_t lda, const double *B, int64_t ldb,
                        double *Cm, int64_t ldc, hipStream_t s);
 
-// Assembly of one class's stacked operators on the device (device.hip "stacked M2L operators").
+// Assembly of one class's stacked operators on the device (device_m2l.hip "stacked M2L operators").
 struct M2lAssembleTv { // one transfer vector of a class list
     int32_t perm;    // symmetry permutation (row of invperm)
     int32_t rank;

@@ -1,0 +1,636 @@
+// M2L: the streamed-operator GEMM kernel of both stages, its chunk and split plans, and the operators' assembly in HBM.
+#include "device_common.hpp"
+
+#include <cmath>
+
+namespace bbfmm {
+
+// ------------------------------------------------------------------ M2L (MFMA FP64)
+// multipole_to_local (bbfmm.rs:864-986) regrouped for the matrix cores.  The reference
+// permutes each V cell's multipoles onto one of 16 reference operators, multiplies by
+// Vt then U, and permutes back.  Here the permutations are folded into per-transfer-
+// vector operators stacked per octant class (host side, fmm_m2l_tables.cpp), which turns the
+// whole level into two dense streamed-operator GEMMs with no data permutation:
+//   stage 1:  Cbuf[target(V,t)][(t,kk)] = sum_m VtAll[(t,kk)][m] * M_V[m]   (X-stationary)
+//   stage 2:  L_B[i]                    = sum_k UAll[i][k] * Cbuf[B][k]     (accumulator-stationary)
+// ------------------------------------------------------------------ M2L on v_mfma_f64_4x4x4_4b
+// Measured on MI355X (scripts/fp64_microbench.hip): v_mfma_f64_16x16x4 sustains ~46 TFLOP/s
+// chip-wide (~100-144 cycles per instruction), v_mfma_f64_4x4x4 (4 blocks) ~70 TFLOP/s (17
+// cycles per 512-flop instruction).  The kernels below are the same two streamed-operator
+// GEMMs as above on the faster instruction.  Lane layout (probed, scripts/mfma4_probe.hip):
+//   A[b][i][k]: lane = 16k + 4b + i    B[b][k][j]: lane = 16k + 4b + j    D[b][i][j]: lane = 16i + 4b + j
+// with D_b = A_b * B_b for the four independent blocks b.
+//
+// Stage 1 uses the blocks as four slices of the contraction index (t = lane>>2 = 4k + b selects
+// the m values a lane owns), so one operator fragment feeds four cell groups and each D register
+// holds four partial sums that are added across lanes (xor 4, xor 8) once per tile.
+// Operator tiles are staged with the asynchronous global->LDS DMA (global_load_lds_dwordx4,
+// no VGPR round trip) into two LDS buffers: the tile for step i+1 streams in while step i is
+// multiplied.  The LDS image is in MFMA-fragment order, so every fragment read is a lane-linear,
+// conflict-free ds_read, and the per-lane DMA source address performs the permutation from the
+// operator's row-major HBM layout.  The DMA is issued from inline asm: through the builtin the
+// compiler must assume the in-flight LDS write may alias every later ds_read and drains it
+// (s_waitcnt vmcnt(0)) before each fragment read, which serialises the whole pipeline.
+typedef __attribute__((address_space(3))) void *lptr_t;
+
+__device__ inline unsigned lds_offset(const double *p) {
+    return static_cast<unsigned>(reinterpret_cast<uintptr_t>((lptr_t)p));
+}
+// Wave-uniform values the compiler cannot prove uniform (derived from threadIdx.x >> 6).
+__device__ inline unsigned uniform_u32(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ inline const double *uniform_ptr(const double *p) {
+    const uintptr_t v = reinterpret_cast<uintptr_t>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
+    const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
+    return reinterpret_cast<const double *>((static_cast<uintptr_t>(hi) << 32) | lo);
+}
+// 64 lanes x 16 B land at LDS byte offset m0 + lane * 16 (destination = wave-uniform base + lane*16).
+__device__ inline void dma16(const double *g, unsigned lds_wave_byte_offset) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g),
+                 "s"(uniform_u32(lds_wave_byte_offset))
+                 : "memory");
+}
+// 64 lanes x 4 B (a gather of table entries) land at LDS byte offset m0 + lane * 4.
+__device__ inline void dma4(const int32_t *g, unsigned lds_wave_byte_offset) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g),
+                 "s"(uniform_u32(lds_wave_byte_offset))
+                 : "memory");
+}
+__device__ inline void wait_dma_and_barrier() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+// Same, but lets the N most recent vector-memory operations of the wave stay in flight.  gfx9
+// retires loads and stores in issue order on one counter, so when N stores were issued after the
+// DMA the DMA has landed once at most N operations are outstanding (the field holds 0..63).
+template <int N> __device__ inline void wait_dma_keep_stores_and_barrier() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N < 63 ? N : 63) : "memory");
+    __syncthreads();
+}
+// v + (v rotated right by N lanes inside each row of 16 lanes), via DPP row_ror
+template <int N> __device__ inline double add_row_ror(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const int rlo = __builtin_amdgcn_update_dpp(0, lo, 0x120 + N, 0xf, 0xf, false);
+    const int rhi = __builtin_amdgcn_update_dpp(0, hi, 0x120 + N, 0xf, 0xf, false);
+    return v + __hiloint2double(rhi, rlo);
+}
+
+// Same with a uniform (SGPR) base and a 32-bit per-lane byte offset: saves address VGPRs.
+__device__ inline void dma16s(const double *sbase, unsigned voff_bytes, unsigned lds_wave_byte_offset) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes),
+                 "s"(uniform_ptr(sbase)), "s"(uniform_u32(lds_wave_byte_offset))
+                 : "memory");
+}
+
+// One kernel serves both stages: OUT[cell][col] = sum_k IN[cell][k] * OP[k][col] for the 128
+// cells of a workgroup and a block of 16*NG16 output columns.
+//   stage 1: IN = multipoles M (k = Chebyshev node m, n_pad of them), OP = VtAll (n_pad x r_pad),
+//            col = stacked operator row (t, kk); the result is scattered into the target slots.
+//   stage 2: IN = slot contents (k over the slot, k_pad), OP = UAll (k_pad x n_pad), col = node;
+//            the result is the local expansion L.
+//   stage 3: a plain product per cell, IN = rows of in_len values per cell (like M), OP = cls.u_all
+//            (in_len x n_pad), OUT = rows of n_pad values per cell (like L): the change of basis of the
+//            shared-basis extension (multipoles -> coordinates in the level's basis, and back for the locals).
+// The four MFMA blocks are four groups of four output columns: A_b = operator fragment
+// OP[k][col 4b + i] (one lane-linear ds_read_b64 per 16 columns, feeding four MFMAs), B_b = the
+// IN values of four cells (the same for every block), D_b[i][j] = OUT[cell j][col 4b + i].  A wave
+// owns 16 cells (four groups tg) and keeps 4 x NG16 accumulators; the operator tile and the
+// cells' IN values of step q+1 stream into LDS by DMA while step q is multiplied.
+template <int NG16, int STAGE, int MINW>
+__global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restrict__ classes,
+                                                  const M2lTileDesc *__restrict__ tiles, int n_pad, int g16_0,
+                                                  int64_t C, const double *__restrict__ in, int64_t in_len,
+                                                  double *__restrict__ out, int64_t out_len,
+                                                  const uint16_t *__restrict__ qlist, int slot_t,
+                                                  const int32_t *__restrict__ tile_idx) {
+    // 2 x { operator [e][ng][k*16 + col], IN tile [wave][tg][eh][k][j] x 2 }; stage 1 adds the slot
+    // lookups of the current column block, [wave][cell 0..15][slot_t] int32
+    extern __shared__ double lds[];
+    const M2lTileDesc tile = tiles[blockIdx.x];
+    const M2lClass cls = classes[tile.level_class];
+    const int kr = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // stage 1: the workgroup walks the column blocks zb0 .. zb1 of kM2lS1Block stacked rows (g16_0
+    // selects a chunk inside a block); stage 2: one block, g16_0 selects the nodes
+    const int n_zb = STAGE == 1 ? cls.r_pad16 / kM2lS1Block : 1;
+    // (a tile of a sparse plan, pad == 2, names its own column blocks: q_first, q_count)
+    const bool own_blocks = STAGE == 1 && tile.pad == 2;
+    const int zb0 = STAGE == 1 ? (own_blocks ? tile.q_first : (int)((int64_t)n_zb * blockIdx.z / gridDim.z)) : 0;
+    const int zb1 = STAGE == 1 ? (own_blocks ? tile.q_first + tile.q_count : (int)((int64_t)n_zb * (blockIdx.z + 1) / gridDim.z)) : 1;
+    const int ld = STAGE == 1 ? cls.r_pad16 : n_pad;            // operator leading dimension
+    // contraction steps of 16: all of them in stage 1; in stage 2 only those for which some cell
+    // of the tile has a V-list entry (tile.q_first/q_count index the compact list qlist)
+    // Stage 2 of a launch with few tiles is split over the contraction as well (slot_t = number of parts, the
+    // parameter is stage 1's otherwise): a tile's chain of ~290 steps is what a small tree's matvec waits for.
+    // blockIdx.z = part * column chunks + column chunk; the parts add their results to the zeroed L with atomics.
+    const int ksplit = STAGE == 2 && slot_t > 1 ? slot_t : 1;
+    const int zcols = STAGE == 2 ? (int)gridDim.z / ksplit : 1;
+    const int zk = STAGE == 2 ? (int)blockIdx.z / zcols : 0, zc = STAGE == 2 ? (int)blockIdx.z - zk * zcols : (int)blockIdx.z;
+    const int q_lo = STAGE == 2 ? tile.q_count * zk / ksplit : 0;
+    const int nq = STAGE == 1 ? n_pad / 16 : STAGE == 2 ? tile.q_count * (zk + 1) / ksplit - q_lo : (int)(in_len / 16);
+    const uint16_t *ql = qlist + tile.q_first + q_lo;
+    if (zb0 >= zb1) return;
+    // stage 2 with gridDim.z > 1: the z workgroups of a tile take adjacent chunks of NG16 column groups
+    const int g16 = g16_0 + (STAGE >= 2 ? zc * NG16 : 0);
+    const double *opbase = (STAGE == 1 ? cls.vt_all : cls.u_all) + 16 * g16;
+
+    constexpr int OP_CHUNKS = 2 * NG16;
+    constexpr int NCH = (OP_CHUNKS + 7) / 8;
+    constexpr int OP_DOUBLES = OP_CHUNKS * 128;
+    constexpr int BUF = OP_DOUBLES + 2048;
+
+    // Operator image in LDS.  The NG16 column groups are taken as NP pairs (+ one single group when
+    // NG16 is odd).  A pair chunk (e, pr) is [k][p = 4b + i][2]: lane 16k + p holds columns
+    // 32 pr + 2p and + 1 of row 4k + e, fetched as one 16-byte DMA granule and read back with one
+    // ds_read_b128 feeding the MFMAs of groups 2 pr and 2 pr + 1.  An accumulator pair of a lane is
+    // thus two ADJACENT output columns, which the epilogues store as 16 bytes (the stage-1 scatter
+    // is bound by the number of store instructions).  The single group keeps [e][k][16 columns].
+    constexpr int NP = NG16 / 2, NS = NG16 & 1;
+    unsigned voff[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = wave + 8 * i;
+        if (c < 4 * NP) {
+            const int e = c / NP, pr = c - e * NP, k = lane >> 4, p = lane & 15;
+            voff[i] = (unsigned)(((4 * k + e) * ld + 32 * pr + 2 * p) * 8);
+        } else {
+            const int e = 2 * (c - 4 * NP) + (lane >> 5), r = lane & 31, k = r >> 3, pair = r & 7;
+            voff[i] = (unsigned)(((4 * k + e) * ld + 32 * NP + 2 * pair) * 8);
+        }
+    }
+    // position of the tile's cell `pos` in its class list (a partition's source tiles are compact
+    // lists of class positions, tile.pad != 0)
+    auto cell_p = [&](int pos) {
+        const int q = pos < tile.count ? pos : 0;
+        return tile.pad ? tile_idx[tile.first + q] : tile.first + q;
+    };
+    // IN tile: chunk h of this wave covers tg = 2h + (lane>>5), eh = (lane>>4)&1, k = (lane>>2)&3, j = lane&3
+    const double *cptr[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int tg = 2 * h + (lane >> 5), eh = (lane >> 4) & 1, k = (lane >> 2) & 3, j = lane & 3;
+        const int pos = wave * 16 + 4 * tg + j;
+        const int p = cell_p(pos);
+        const int64_t base = STAGE == 2 ? (int64_t)kr * in_len + cls.cbase[p]
+                                        : ((int64_t)kr * C + cls.cells[p]) * (STAGE == 1 ? (int64_t)n_pad : in_len);
+        cptr[h] = in + base + 4 * k + 2 * eh;
+    }
+    const unsigned lds0 = lds_offset(lds);
+    const int64_t qstride = (int64_t)16 * ld;
+    // step s of the flattened (column block, contraction step) loop
+    auto stage = [&](int sidx, int buf) {
+        const int zb = zb0 + sidx / nq, qi = sidx - (sidx / nq) * nq;
+        const int q = STAGE == 2 ? (int)ql[qi] : qi;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+            if (wave + 8 * i < OP_CHUNKS)
+                dma16s(opbase + (int64_t)zb * kM2lS1Block + q * qstride, voff[i],
+                       lds0 + (unsigned)(buf * BUF + (wave + 8 * i) * 128) * 8u);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            dma16(cptr[h] + 16 * q, lds0 + (unsigned)(buf * BUF + OP_DOUBLES + (2 * wave + h) * 128) * 8u);
+    };
+
+    double acc[4][NG16];
+#pragma unroll
+    for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+        for (int g = 0; g < NG16; ++g) acc[tg][g] = 0.0;
+
+    const int bk = lane >> 4, bj = lane & 3; // B layout (k, j); the block index is broadcast
+    const bool wave_live = wave * 16 < tile.count;
+    const int n_steps = (zb1 - zb0) * nq;
+    // epilogue coordinates: D[b][i][j] at lane 16 i + 4 b + j = OUT[cell 4 tg + j][col0 + 16 g + 4 b + i]
+    const int di = lane >> 4, db = (lane >> 2) & 3, dj = lane & 3;
+    // Stage-1 scatter tables.  gfx9 retires vector-memory operations in issue order on one counter,
+    // and the compiler cannot see the DMA in its wait counting: a wait for any ordinary load in this
+    // loop would be vmcnt(0) and drain the DMA in flight and the scatter stores with it.  The loop
+    // therefore issues no ordinary loads at all.  All lookups come in by DMA and are read from LDS:
+    //   aux[parity][0 .. 16 NG16)  packed row entries of a column block, aux[parity][16 NG16] its first
+    //                              transfer-vector position (requested during the previous block)
+    //   slots[wave][cell][slot_t]  slot bases of the wave's 16 cells for the block's transfer vectors
+    //                              (requested two steps before the block ends)
+    // and the stores of a block leave together and drain under the next block.
+    constexpr int AUX = 192;
+    const int32_t *aux = reinterpret_cast<const int32_t *>(lds + 2 * BUF);
+    int32_t *ptab = reinterpret_cast<int32_t *>(lds + 2 * BUF) + 2 * AUX; // class positions of the 128 cells
+    const int32_t *slds = aux + 2 * AUX + 128 + wave * 16 * slot_t;
+    if (STAGE == 1 && lane < 16) ptab[wave * 16 + lane] = cell_p(wave * 16 + lane); // read by this wave only
+    const unsigned aux0 = lds0 + (unsigned)(2 * BUF) * 8u;
+    auto stage_cols = [&](int zb_, int par) {
+        if (STAGE == 1 && 64 * wave <= 16 * NG16) {
+            const int e = 64 * wave + lane;
+            const int32_t *src = e < 16 * NG16 ? cls.row_dst + zb_ * kM2lS1Block + 16 * g16 + e : cls.blk_t0 + zb_;
+            dma4(src, aux0 + (unsigned)(par * AUX + 64 * wave) * 4u);
+        }
+    };
+    const int slot_sh = 31 - __builtin_clz(slot_t | 1); // slot_t is a power of two >= 16 in stage 1
+    auto stage_slots = [&](int par) {
+        const int t0 = __builtin_amdgcn_readfirstlane(aux[par * AUX + 16 * NG16]);
+        const unsigned dst0 = aux0 + (unsigned)(2 * AUX + 128 + wave * 16 * slot_t) * 4u;
+        for (int i = 0; i < slot_t / 4; ++i) {
+            const int e = i * 64 + lane, cl = e >> slot_sh, tl = e & (slot_t - 1);
+            const int32_t *src = cls.cslot + (int64_t)ptab[wave * 16 + cl] * cls.n_t + min(t0 + tl, cls.n_t - 1);
+            dma4(src, dst0 + (unsigned)i * 256u);
+        }
+    };
+    if (n_steps > 0) {
+        stage(0, 0);
+        stage_cols(zb0, 0);
+    }
+    wait_dma_and_barrier();
+    int qcnt = 0, zb = zb0;
+    for (int sidx = 0; sidx < n_steps; ++sidx) {
+        const double *op = lds + (sidx & 1) * BUF + lane;
+        const double2 *op2 = reinterpret_cast<const double2 *>(lds + (sidx & 1) * BUF) + lane;
+        const double *ct = lds + (sidx & 1) * BUF + OP_DOUBLES + wave * 256 + (bk * 4 + bj) * 2;
+        if (sidx + 1 < n_steps) stage(sidx + 1, (sidx + 1) & 1); // streams in under the MFMAs below
+        if (STAGE == 1) {
+            if (qcnt == 0 && zb + 1 < zb1) stage_cols(zb + 1, (zb + 1 - zb0) & 1);
+            if (qcnt == nq - 2) stage_slots((zb - zb0) & 1);
+        }
+        if (wave_live) { // a wave without cells (short tile) only helps with the DMA and the barriers
+            double bq[4][4];
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                for (int eh = 0; eh < 2; ++eh) {
+                    const double2 v = *reinterpret_cast<const double2 *>(ct + ((tg * 2 + eh) * 16) * 2);
+                    bq[tg][2 * eh] = v.x;
+                    bq[tg][2 * eh + 1] = v.y;
+                }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                for (int pr = 0; pr < NP; ++pr) {
+                    const double2 a = op2[(e * NP + pr) * 64];
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg) {
+                        acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, bq[tg][e], acc[tg][2 * pr], 0, 0, 0);
+                        acc[tg][2 * pr + 1] =
+                            __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, bq[tg][e], acc[tg][2 * pr + 1], 0, 0, 0);
+                    }
+                }
+                if (NS) {
+                    const double a = op[4 * NP * 128 + e * 64];
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg)
+                        acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bq[tg][e], acc[tg][NG16 - 1], 0, 0, 0);
+                }
+            }
+        }
+        if (++qcnt == nq) { // a column block is complete: write it out, start the next one
+            qcnt = 0;
+            const int col0 = zb * kM2lS1Block + 16 * g16;
+            ++zb;
+            if (STAGE == 1 && wave_live) {
+                // Scatter into the target slots, branch-free: entries without a destination (padding
+                // rows, absent targets, cells beyond the tile) go to a dump area behind the slot buffer.
+                // Measured: the epilogue is store-issue bound (about 75 cycles per store instruction
+                // and CU whatever its width, the address pattern or the wait after it): adjacent
+                // column pairs leave as 16-byte stores, half the instructions of 8-byte ones.
+                double *cb = out + (int64_t)kr * out_len;
+                double *dump = cb + (out_len - 128) + 2 * lane; // 16-byte aligned (out_len is even)
+                const int32_t *auxb = aux + ((zb - 1 - zb0) & 1) * AUX;
+                int pk[NP + NS];
+#pragma unroll
+                for (int pr = 0; pr < NP; ++pr) pk[pr] = auxb[32 * pr + 2 * (4 * db + di)]; // the even column
+                if (NS) pk[NP] = auxb[32 * NP + 4 * db + di];
+#pragma unroll
+                for (int tg = 0; tg < 4; ++tg) {
+                    const bool spv = wave * 16 + 4 * tg + dj < tile.count;
+                    const int32_t *srow = slds + (4 * tg + dj) * slot_t;
+#pragma unroll
+                    for (int pr = 0; pr < NP; ++pr) {
+                        const int sl = srow[max(pk[pr] >> 24, 0)];
+                        const int okm = (spv ? -1 : 0) & ~(pk[pr] | sl); // sign bit set: valid cell, row, slot
+                        double *dst = okm < 0 ? cb + (int64_t)sl * 2 + (pk[pr] & 0xffffff) : dump;
+                        *reinterpret_cast<double2 *>(dst) = make_double2(acc[tg][2 * pr], acc[tg][2 * pr + 1]);
+                    }
+                    if (NS) {
+                        const int sl = srow[max(pk[NP] >> 24, 0)];
+                        const int okm = (spv ? -1 : 0) & ~(pk[NP] | sl);
+                        double *dst = okm < 0 ? cb + (int64_t)sl * 2 + (pk[NP] & 0xffffff) : dump;
+                        *dst = acc[tg][NG16 - 1];
+                    }
+                }
+            } else if (STAGE >= 2) {
+#pragma unroll
+                for (int tg = 0; tg < 4; ++tg) {
+                    const int tp = wave * 16 + 4 * tg + dj;
+                    if (tp < tile.count) {
+                        const int cell = cls.cells[cell_p(tp)];
+                        double *Lc = out + ((int64_t)kr * C + cell) * n_pad + col0;
+                        if (ksplit > 1) { // one of several parts of the contraction
+#pragma unroll
+                            for (int pr = 0; pr < NP; ++pr) {
+                                unsafeAtomicAdd(Lc + 32 * pr + 2 * (4 * db + di), acc[tg][2 * pr]);
+                                unsafeAtomicAdd(Lc + 32 * pr + 2 * (4 * db + di) + 1, acc[tg][2 * pr + 1]);
+                            }
+                            if (NS) unsafeAtomicAdd(Lc + 32 * NP + 4 * db + di, acc[tg][NG16 - 1]);
+                        } else {
+#pragma unroll
+                            for (int pr = 0; pr < NP; ++pr)
+                                *reinterpret_cast<double2 *>(Lc + 32 * pr + 2 * (4 * db + di)) =
+                                    make_double2(acc[tg][2 * pr], acc[tg][2 * pr + 1]);
+                            if (NS) Lc[32 * NP + 4 * db + di] = acc[tg][NG16 - 1];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                for (int g = 0; g < NG16; ++g) acc[tg][g] = 0.0;
+            // the 4 * (NP + NS) scatter stores issued after this step's DMA drain under the next block
+            // (a wave without cells stored nothing: it waits for its DMA as usual)
+            if (STAGE == 1) {
+                if (wave_live) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NP + NS) < 63 ? 4 * (NP + NS) : 63) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                continue;
+            }
+        }
+        wait_dma_and_barrier();
+    }
+}
+
+template <int NG16, int STAGE, int MINW>
+static void m2l_gemm_launch(const M2lClass *classes, const M2lTileDesc *tiles, int n_tiles, int n_pad, int g16_0,
+                            int n_colblocks, int K, int64_t C, const double *in, int64_t in_len, double *out,
+                            int64_t out_len, const uint16_t *qlist, int slot_t, const int32_t *tile_idx, hipStream_t s) {
+    const size_t lds = 2 * sizeof(double) * (size_t)(2 * NG16 * 128 + 2048) + (STAGE == 1 ? (size_t)(2 * 192 + 128 + 8 * 16 * (slot_t & 0xffff)) * 4 : 0); // + aux, cell and slot tables
+    // one flag word per template instance; a refused attribute shows up as the failed launch
+    static std::atomic<uint64_t> attr_set[4] = {{0}, {0}, {0}, {0}};
+    (void)allow_large_dynamic_lds(reinterpret_cast<const void *>(&m2l_gemm_k4<NG16, STAGE, MINW>), lds, attr_set);
+    const int zdim = STAGE == 2 && slot_t > 1 ? n_colblocks * slot_t : n_colblocks; // stage 2: slot_t = parts of the contraction
+    hipLaunchKernelGGL((m2l_gemm_k4<NG16, STAGE, MINW>), dim3(n_tiles, K, zdim), dim3(512), lds, s, classes,
+                       tiles, n_pad, g16_0, C, in, in_len, out, out_len, qlist, slot_t, tile_idx);
+}
+
+// Column-chunk plan: 16-column groups per workgroup.  Stage 1 walks column blocks of kM2lS1Block =
+// 11 groups (44 accumulators per lane; 22 spills in the persistent walk).  Stage 2 covers the n_pad
+// output nodes with 22-group chunks (88 accumulators, one workgroup per CU), measured faster there
+// than 11 or 8.
+
+template <int STAGE> constexpr int m2l_chunk_pref() { return STAGE == 1 ? kM2lS1Block / 16 : 22; }
+constexpr int kM2lS2KsplitFill = 4; // workgroups per CU up to which stage 2 keeps splitting the contraction
+
+template <int STAGE>
+static void m2l_dispatch_chunks(int total_groups, const M2lClass *classes, const M2lTileDesc *tiles, int n_tiles,
+                                int n_pad, int n_colblocks, int K, int64_t C, const double *in, int64_t in_len,
+                                double *out, int64_t out_len, const uint16_t *qlist, int slot_t,
+                                const int32_t *tile_idx, hipStream_t s) {
+    int done = 0;
+    const int pref = m2l_chunk_pref<STAGE>();
+    while (done < total_groups) {
+        const int left = total_groups - done;
+        int take;
+#define M2L_GO(NG, MW)                                                                                              \
+    {                                                                                                               \
+        take = NG;                                                                                                  \
+        m2l_gemm_launch<NG, STAGE, MW>(classes, tiles, n_tiles, n_pad, done,                                        \
+                                       STAGE >= 2 ? 1 : n_colblocks, K, C, in, in_len,                            \
+                                       out, out_len, qlist, slot_t, tile_idx, s);                                   \
+    }
+        if (STAGE >= 2 && !(n_colblocks == 1 && left >= 16)) { // (one workgroup per tile and a wide chunk: the plan below)
+            // stage 2 / 3 with several workgroups per tile (gridDim.z = zc): the largest NG x zc <= left from the
+            // kernels without spills, at most 2 x 11 or 3 x (8, 7, 6, 4, 2) -- 22 = 2 x 11, 46 = 3 x 8 + 2 x 11,
+            // 18 = 3 x 6, 16 = 2 x 8, 7 = 1 x 7
+            int best_ng = 2, best_z = 1;
+            for (int ng : {11, 8, 7, 6, 4, 2})
+                for (int zc = 1; zc <= (n_colblocks == 1 ? 1 : ng == 11 ? 2 : 3); ++zc)
+                    if (ng * zc <= left && ((left - ng * zc) % 2 == 0 || left - ng * zc == 7) && // what remains must be coverable
+                        (ng * zc > best_ng * best_z || (ng * zc == best_ng * best_z && ng > best_ng))) {
+                        best_ng = ng;
+                        best_z = zc;
+                    }
+            take = best_ng * best_z;
+#define M2L_ZGO(NG, MW)                                                                                             \
+    m2l_gemm_launch<NG, STAGE, MW>(classes, tiles, n_tiles, n_pad, done, best_z, K, C, in, in_len, out, out_len,    \
+                                   qlist, slot_t, tile_idx, s);
+            if constexpr (STAGE >= 2) {
+                switch (best_ng) {
+                case 11: M2L_ZGO(11, 1) break;
+                case 8: M2L_ZGO(8, 4) break;
+                case 7: M2L_ZGO(7, 2) break;
+                case 6: M2L_ZGO(6, 4) break;
+                case 4: M2L_ZGO(4, 4) break;
+                default: M2L_ZGO(2, 4) break;
+                }
+            }
+#undef M2L_ZGO
+        } else if (pref == 22 && left >= 22) M2L_GO(22, 1)
+        else if (pref == 22 && left >= 16) M2L_GO(16, 1)
+        else if (pref == 11 && left >= 11) M2L_GO(11, 1)
+        else if (left >= 8) M2L_GO(8, 4)
+        else if (left >= 6) M2L_GO(6, 4)
+        else if (left >= 4) M2L_GO(4, 4)
+        else M2L_GO(2, 4)
+#undef M2L_GO
+        done += take;
+    }
+}
+
+// Stage 1: every class's stacked operator is padded to a whole number of kM2lS1Block columns;
+// blockIdx.z walks the column blocks, the chunk plan splits a block.
+void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                       int n_pad, int max_slot_t, int K, int64_t C, const double *M, double *cbuf, int64_t cbuf_len,
+                       hipStream_t s, bool own_blocks, int max_blocks) {
+    if (n_tiles == 0) return;
+    int slot_t = 16; // LDS slot-table width: power of two covering the transfer vectors of any block
+    while (slot_t < max_slot_t) slot_t *= 2;
+    // every workgroup walks its share of the column blocks; splitting the walk over gridDim.z
+    // workgroups shortens the last, partially filled round of the launch
+    const int n_cu = device_cu_count();
+    // One workgroup per CU at a time: n_tiles * z workgroups take ceil(n_tiles * z / CUs) rounds of 1/z of the
+    // column-block walk each; z is chosen so that the last, partially filled round is short (a per-workgroup
+    // overhead of about half a percent of a walk keeps z small).  Measured at 10M points (2,336 tiles): z = 2 18.2 ms,
+    // 3 18.0, 4 17.75, 7 18.0, 13 18.3.
+    // A launch that does not fill the chip even at z = 8 (a small tree: 16 tiles at 36k points, where a workgroup's walk of
+    // four column blocks WAS the stage: 0.155 ms of a 0.46 ms matvec) may split the walk down to one block per workgroup.
+    const int zmax = n_tiles * 8 < n_cu ? std::max(8, std::min(max_blocks, 32)) : 8;
+    int zsplit = 1;
+    double best = 1e300;
+    for (int z = 1; z <= zmax; ++z) {
+        const double rounds = std::ceil(static_cast<double>(n_tiles) * z / n_cu);
+        const double cost = rounds / z * (1.0 + 0.005 * z);
+        if (cost < best - 1e-12) {
+            best = cost;
+            zsplit = z;
+        }
+    }
+    const int n_colblocks = own_blocks ? 1 : zsplit; // tiles that name their own blocks are not split further
+    m2l_dispatch_chunks<1>(kM2lS1Block / 16, classes, tiles, n_tiles, n_pad, n_colblocks, K, C, M, 0, cbuf, cbuf_len, nullptr,
+                           slot_t, tile_idx, s);
+}
+
+// Stage 2: the output nodes (n_pad, in groups of 16; n_pad is a multiple of 32) in column chunks.
+void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                       int n_pad, int K, int64_t C, const double *cbuf, int64_t cbuf_len, const uint16_t *qlist,
+                       double *L, hipStream_t s, bool allow_ksplit) {
+    if (n_tiles == 0) return;
+    // Two workgroups per tile, each with half of a 22-group chunk of the output nodes (gridDim.z = 2, 11 groups,
+    // 78 KB of LDS: two fit a CU).  The halves of a tile read the same slot contents at about the same time (L2
+    // hits) and twice as many, shorter workgroups balance tiles of unequal length (per-tile active steps) and fill
+    // the CUs of launches with few tiles.  Measured, stage 2 per matvec: 10M points 16.2 -> 15.8 ms, p = 9 55.1 ->
+    // 53.6 (52.5 with the remainder as 3 x 8 instead of 22 + 2), 1M points (about 200 tiles) 2.10 -> 1.54 and 1.12 -> 0.71,
+    // one rank of an 8-way partition 2.81 -> 2.28.  (Two separate launches of 11 groups were slower than one of 22.)
+    // BBFMM_M2L_S2_ZSPLIT=1 turns it off.
+    static const int z = env_int("BBFMM_M2L_S2_ZSPLIT", 2) == 1 ? 1 : 2;
+    // Few tiles (a small tree, a thin slice of a partition): also split the contraction, so that no workgroup walks a
+    // tile's chain of ~290 dependent steps alone.  The parts add to L (zeroed by the caller before every downward pass) with
+    // f64 atomics; launches that fill the chip keep plain stores.
+    // Stage 2 per matvec: 50k points 0.50 -> 0.11 ms (the whole matvec 0.79 -> 0.39 ms), 200k 0.52 -> 0.43, 1M 0.95 -> 0.78;
+    // from 3M points on the launch fills the chip and nothing changes.  BBFMM_M2L_S2_KSPLIT=<n> overrides (1: off).
+    // Round 6: the number of parts from what was measured instead of a power of two -- a CU works its workgroups off one after
+    // the other (two resident ones share its matrix pipe), a part costs a fixed 4-5 % of a whole chain plus its share of it,
+    // so the launch takes ceil(workgroups * parts / CUs) * (0.05 + 1 / parts) chains: 585 cells (32 workgroups) 16 -> 8 parts,
+    // 0.105 -> 0.085 ms; 4,681 cells (158 workgroups) 4 -> 3 parts, 0.419 -> 0.368 ms (5 parts: 0.462, 8: 0.411, 2: 0.511).
+    static const int ks_env = [] {
+        const int v = env_int("BBFMM_M2L_S2_KSPLIT", 0);
+        return v >= 1 && v <= 32 ? v : 0;
+    }();
+    int ksplit = allow_ksplit ? ks_env : 1; // (the parts add atomically: not for BBFMM_FLAG_DETERMINISTIC handles)
+    if (ksplit == 0) {
+        const int n_cu = device_cu_count();
+        const int64_t wgs = static_cast<int64_t>(n_tiles) * z * K;
+        ksplit = 1;
+        if (wgs * 2 <= static_cast<int64_t>(kM2lS2KsplitFill) * n_cu) { // (launches of at most two workgroups per CU, as before)
+            double best = 1e300;
+            for (int ks = 1; ks <= 16; ++ks) {
+                const double cost = std::ceil(static_cast<double>(wgs * ks) / n_cu) * (0.05 + 1.0 / ks);
+                if (cost < best - 1e-12) {
+                    best = cost;
+                    ksplit = ks;
+                }
+            }
+        }
+    }
+    m2l_dispatch_chunks<2>(n_pad / 16, classes, tiles, n_tiles, n_pad, z, K, C, cbuf, cbuf_len, L, 0, qlist, ksplit > 1 ? ksplit : 0, tile_idx, s);
+}
+
+// Slot segments of absent pairs: 16 lanes per segment, 16 bytes per lane and round.
+__global__ __launch_bounds__(256) void m2l_zero_segments_kernel(const int32_t *__restrict__ segs, int64_t n_segs,
+                                                                double *__restrict__ cbuf, int64_t cbuf_len) {
+    const int64_t sg = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) >> 4;
+    const int l = threadIdx.x & 15;
+    if (sg >= n_segs) return;
+    const int2 e = reinterpret_cast<const int2 *>(segs)[sg];
+    double2 *dst = reinterpret_cast<double2 *>(cbuf + static_cast<int64_t>(blockIdx.y) * cbuf_len) + e.x;
+    for (int i = l; i < e.y; i += 16) dst[i] = make_double2(0.0, 0.0);
+}
+
+void launch_m2l_zero_segments(const int32_t *segs, int64_t n_segs, int K, double *cbuf, int64_t cbuf_len, hipStream_t s) {
+    if (n_segs <= 0) return;
+    hipLaunchKernelGGL(m2l_zero_segments_kernel, dim3(static_cast<unsigned>((n_segs * 16 + 255) / 256), K), dim3(256), 0, s, segs,
+                       n_segs, cbuf, cbuf_len);
+}
+
+// Shared-basis extension: change of basis of every cell of a level (stage 3 of the GEMM kernel), OUT[cell][0..out_ld) =
+// sum_k IN[cell][k] * OP_level[k][0..out_ld).  classes[].cells / u_all: the level's cells and its in_ld x out_ld operator.
+void launch_m2l_basis(const M2lClass *classes, const M2lTileDesc *tiles, int n_tiles, int in_ld, int out_ld, int K,
+                      int64_t C, const double *in, double *out, hipStream_t s) {
+    if (n_tiles == 0) return;
+    m2l_dispatch_chunks<3>(out_ld / 16, classes, tiles, n_tiles, out_ld, 2, K, C, in, in_ld, out, 0, nullptr, 0, nullptr, s);
+}
+
+// Setup-time product for the projected operators: C[i][j] = sum_k A(i, k) * B[k][j], A(i, k) = A[k * lda + i] (TA) or
+// A[i * lda + k]; 64 x 64 tiles, 4 x 4 per thread, 16 contraction indices per LDS round.
+template <bool TA>
+__global__ __launch_bounds__(256) void small_gemm_kernel(int M, int N, int Kd, const double *__restrict__ A, int64_t lda,
+                                                         const double *__restrict__ B, int64_t ldb, double *__restrict__ Cm,
+                                                         int64_t ldc) {
+    __shared__ double sa[16][64 + 1], sb[16][64 + 1];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+    double acc[4][4] = {};
+    for (int k0 = 0; k0 < Kd; k0 += 16) {
+        for (int e = threadIdx.x; e < 16 * 64; e += 256) {
+            const int kk = TA ? e >> 6 : e & 15, ii = TA ? e & 63 : e >> 4;
+            const int k = k0 + kk, i = i0 + ii;
+            sa[kk][ii] = (k < Kd && i < M) ? (TA ? A[(int64_t)k * lda + i] : A[(int64_t)i * lda + k]) : 0.0;
+        }
+        for (int e = threadIdx.x; e < 16 * 64; e += 256) {
+            const int kk = e >> 6, jj = e & 63;
+            const int k = k0 + kk, j = j0 + jj;
+            sb[kk][jj] = (k < Kd && j < N) ? B[(int64_t)k * ldb + j] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            double a[4], b[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = sa[kk][ty + 16 * r];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) b[c] = sb[kk][tx + 16 * c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] += a[r] * b[c];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int i = i0 + ty + 16 * r, j = j0 + tx + 16 * c;
+            if (i < M && j < N) Cm[(int64_t)i * ldc + j] = acc[r][c];
+        }
+}
+
+void launch_small_gemm(bool trans_a, int M, int N, int Kd, const double *A, int64_t lda, const double *B, int64_t ldb,
+                       double *Cm, int64_t ldc, hipStream_t s) {
+    if (M <= 0 || N <= 0) return;
+    const dim3 grid((N + 63) / 64, (M + 63) / 64);
+    if (trans_a) hipLaunchKernelGGL(small_gemm_kernel<true>, grid, dim3(256), 0, s, M, N, Kd, A, lda, B, ldb, Cm, ldc);
+    else hipLaunchKernelGGL(small_gemm_kernel<false>, grid, dim3(256), 0, s, M, N, Kd, A, lda, B, ldb, Cm, ldc);
+}
+
+// ------------------------------------------------------------------ stacked M2L operators, assembled in HBM
+// fmm_m2l_tables.cpp fill_m2l_operator_arrays on the device: the reference operators of a level (16 in 3-D) and the
+// symmetry tables go up once (MBs), the stacked per-class operators (GBs) are gathered from them here instead
+// of being filled on the host and sent over PCIe.  VtAll[m][first_row(t) + kk] = Vt_ref(t)[kk][invperm_t[m]]
+// (identity rows when uncompressed); UAll[tgt_off(t) + kk][i] = U_ref(t)[invperm_t[i]][kk].
+__global__ __launch_bounds__(256) void assemble_vt_kernel(M2lAssembleClass c, int n, int n_pad, int compressed,
+                                                          const double *__restrict__ ops, const int32_t *__restrict__ invperm,
+                                                          double *__restrict__ vt_all) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(c.n_src) * n) return;
+    const int pos = static_cast<int>(t / n), m = static_cast<int>(t % n);
+    const M2lAssembleTv tv = c.src[pos];
+    const int im = invperm[static_cast<int64_t>(tv.perm) * n + m];
+    double *dst = vt_all + static_cast<int64_t>(m) * c.r_pad16 + tv.row;
+    if (compressed) {
+        const double *src = ops + tv.vt_off + static_cast<int64_t>(im) * tv.rank;
+        for (int kk = 0; kk < tv.rank; ++kk) dst[kk] = src[kk];
+    } else {
+        dst[im] = 1.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void assemble_u_kernel(M2lAssembleClass c, int n, int n_pad, const double *__restrict__ ops,
+                                                         const int32_t *__restrict__ invperm, double *__restrict__ u_all) {
+    const int pos = blockIdx.y;
+    const M2lAssembleTv tv = c.tgt[pos];
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(tv.rank) * n) return;
+    const int kk = static_cast<int>(t / n), i = static_cast<int>(t % n);
+    u_all[static_cast<int64_t>(tv.row + kk) * n_pad + i] = ops[tv.u_off + static_cast<int64_t>(kk) * n + invperm[static_cast<int64_t>(tv.perm) * n + i]];
+}
+
+void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
+                         const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s) {
+    (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(n_pad) * c.r_pad16 * sizeof(double), s);
+    (void)hipMemsetAsync(u_all, 0, static_cast<size_t>(c.k_pad) * n_pad * sizeof(double), s);
+    if (c.n_src > 0)
+        // (one thread per entry, no grid-stride loop: the exact block count, not grid_for's capped one)
+        hipLaunchKernelGGL(assemble_vt_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * n + 255) / 256)), dim3(256), 0, s, c, n, n_pad,
+                           compressed ? 1 : 0, ops, invperm, vt_all);
+    if (c.n_tgt > 0 && c.max_rank > 0)
+        hipLaunchKernelGGL(assemble_u_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.max_rank) * n + 255) / 256), c.n_tgt), dim3(256), 0, s, c,
+                           n, n_pad, ops, invperm, u_all);
+}
+
+} // namespace bbfmm

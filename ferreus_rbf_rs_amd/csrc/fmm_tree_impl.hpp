@@ -99,7 +99,7 @@ template <class T> void FmmTree::dfree(DevBuf<T> *b) {
 
 // ------------------------------------------------------------------ M2L tables
 // Folds the reference's symmetry permutations (bbfmm.rs:910-931,964-982) into stacked
-// per-octant-class operators; see device.hip "M2L".
+// per-octant-class operators; see device_m2l.hip "M2L".
 // One workgroup per CU runs at a time, so a launch of T equal tiles takes ceil(T / CUs) rounds.
 // When the last round is at most half full its tiles are halved (a workgroup whose upper four
 // waves hold no cells runs one wave per SIMD and takes about half the time): the tail costs half a

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Near-field phases of the matvec against the number of right-hand sides (one kernel evaluation per unordered pair
-feeds all rhs of a pass: device.hip p2p_sym2_kernel / p2p_sym_kernel / wx_sym_kernel, instances for 1, 2, 4, 8).
+feeds all rhs of a pass: device_p2p.hip p2p_sym2_kernel / p2p_sym_kernel, device_wx.hip wx_sym_kernel, instances for 1, 2, 4, 8).
 
   python scripts/p2p_rhs_sweep.py [points=10000000] [kernel=LinearRbf] [rhs list=1,2,3,4,5,8]   -> one JSON line per K
 
