@@ -8,9 +8,9 @@ from .fmm_tree import (FmmError, FmmKernelType, FmmParams, FmmTree, KernelDoesNo
                        SpheroidalOrder, mfma_f64_selftest, fp64_valu_selftest)
 
 from . import solvers  # noqa: E402  (FGMRES / Schwarz drivers, iterative_solvers.rs)
-from .isosurface import isosurface_from_values, isosurfaces_from_values  # noqa: E402
+from .isosurface import clip_mesh, isosurface_from_values, isosurfaces_from_values  # noqa: E402
 
 __all__ = ["solvers", "FmmTree", "FmmParams", "KernelParams", "KernelType", "FmmKernelType",
            "SpheroidalOrder", "M2LCompressionType", "FmmError", "PointOutsideTree",
            "KernelDoesNotSupportGradients", "mfma_f64_selftest", "fp64_valu_selftest",
-           "isosurface_from_values", "isosurfaces_from_values"]
+           "isosurface_from_values", "isosurfaces_from_values", "clip_mesh"]

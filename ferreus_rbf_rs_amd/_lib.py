@@ -75,6 +75,11 @@ SIGNATURES = {
     "bbfmm_build_isosurfaces_ex": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p]),
     "bbfmm_isosurfaces_from_values_ex": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_i64, c_i32, c_p]),
     "bbfmm_isosurface_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_build_isosurfaces_opts": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_p, c_p]),
+    "bbfmm_isosurfaces_from_values_opts": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_p, c_p]),
+    "bbfmm_isosurface_finish_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "bbfmm_isosurface_finish_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_clip_triangle": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_isosurface_topology": (ctypes.c_int, [ctypes.c_uint32, c_p, c_p, c_p]),
     "bbfmm_isosurface_cluster_tables": (ctypes.c_int, [c_p, c_p, c_p]),
     "bbfmm_isosurface_count": (c_i32, [c_p]),
@@ -168,6 +173,11 @@ class Interpolant(ctypes.Structure):
 
 
 FLAG_GLOBAL_SCALING = 1
+
+
+class IsosurfaceOptions(ctypes.Structure):
+    """bbfmm_isosurface_options"""
+    _fields_ = [("size", c_i64), ("cluster_method", c_i32), ("finish", c_i32), ("batch_bytes", c_i64)]
 
 
 class DdmParams(ctypes.Structure):

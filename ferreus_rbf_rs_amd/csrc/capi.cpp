@@ -1,5 +1,6 @@
 // extern "C" boundary: include/ferreus_bbfmm_hip.h over bbfmm::FmmTree.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <string>
@@ -293,6 +294,34 @@ static bool iso_args(const double *extents, double resolution, const double *iso
     return true;
 }
 
+// The fields of *o that its size covers; defaults for the rest and for o == nullptr.
+static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int32_t *finish, int64_t *batch_bytes, std::string *err) {
+    *cluster = BBFMM_CLUSTER_NONE;
+    *finish = BBFMM_FINISH_RAW;
+    *batch_bytes = 0;
+    if (!o) return true;
+    if (o->size < static_cast<int64_t>(sizeof(int64_t))) {
+        *err = "isosurface: options->size must be sizeof(bbfmm_isosurface_options)";
+        return false;
+    }
+    if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, cluster_method) + sizeof(int32_t))) *cluster = o->cluster_method;
+    if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, finish) + sizeof(int32_t))) *finish = o->finish;
+    if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, batch_bytes) + sizeof(int64_t))) *batch_bytes = o->batch_bytes;
+    return true;
+}
+
+static bool iso_methods_ok(int32_t cluster, int32_t finish, std::string *err) {
+    if (cluster != BBFMM_CLUSTER_NONE && cluster != BBFMM_CLUSTER_AVERAGE) {
+        *err = "isosurface: unknown cluster method " + std::to_string(cluster);
+        return false;
+    }
+    if (finish != BBFMM_FINISH_RAW && finish != BBFMM_FINISH_CLIPPED) {
+        *err = "isosurface: unknown finish " + std::to_string(finish);
+        return false;
+    }
+    return true;
+}
+
 static int iso_fail(bbfmm_handle *h, bbfmm_isosurface_result *r, int rc, const std::string &msg) {
     if (h) h->err = msg;
     if (r) r->err = msg;
@@ -368,14 +397,18 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
                                       BBFMM_CLUSTER_NONE, out);
 }
 
-int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
-                               int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
-                               int32_t cluster_method, bbfmm_isosurface_result **out) {
+} // extern "C"
+
+static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                                  int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                                  int32_t cluster_method, int32_t finish, bbfmm_isosurface_result **out) {
     GUARD(h)
     if (out) *out = nullptr;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
-    if (cluster_method != BBFMM_CLUSTER_NONE && cluster_method != BBFMM_CLUSTER_AVERAGE)
-        return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: unknown cluster method " + std::to_string(cluster_method));
+    {
+        std::string bad;
+        if (!iso_methods_ok(cluster_method, finish, &bad)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, bad);
+    }
     if (h->tree.tree().d != 3) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: only supported for 3D (d = 3)");
     bbfmm::iso::Lattice lat;
     std::string err;
@@ -412,6 +445,8 @@ int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double re
     req.d_field_out = d_field_out;
     req.budget_bytes = batch_bytes;
     req.cluster = cluster_method;
+    req.finish = finish;
+    req.extents = extents;
     std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
     const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);
     if (rc != BBFMM_OK) {
@@ -424,16 +459,11 @@ int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double re
     END_GUARD(h)
 }
 
-int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
-                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
-                                  bbfmm_isosurface_result **out) {
-    return bbfmm_isosurfaces_from_values_ex(h, values, extents, resolution, isovalues, n_isovalues, batch_bytes,
-                                            BBFMM_CLUSTER_NONE, out);
-}
-
-int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, const double *extents, double resolution,
-                                     const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
-                                     int32_t cluster_method, bbfmm_isosurface_result **out) {
+// A host mesh (one_mesh) or a host field through extract(), on the handle's stream or one of the call's own.
+static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                 const double *isovalues, int32_t n_isovalues, int64_t batch_bytes, int32_t cluster_method,
+                                 int32_t finish, const double *vertices, int64_t n_vertices, const int64_t *facets, int64_t n_facets,
+                                 bool one_mesh, bbfmm_isosurface_result **out) {
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     *out = nullptr;
     bbfmm_isosurface_result *r = nullptr;
@@ -445,11 +475,23 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
             h->tree.bind_device();
         }
         bbfmm::iso::Lattice lat;
+        bbfmm::iso::ClipBox box;
         std::string err;
-        if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
-        if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
-        if (cluster_method != BBFMM_CLUSTER_NONE && cluster_method != BBFMM_CLUSTER_AVERAGE)
-            return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: unknown cluster method " + std::to_string(cluster_method));
+        if (one_mesh) {
+            // everything is checked before any work: the box, the sizes the id packing holds, the ids
+            if (!bbfmm::iso::make_clip_box(extents, &box, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if (!bbfmm::iso::finish_fits(n_vertices, n_facets, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if ((n_vertices > 0 && !vertices) || (n_facets > 0 && !facets))
+                return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: vertices and facets must not be null");
+            for (int64_t q = 0; q < 3 * n_facets; ++q)
+                if (facets[q] < 0 || facets[q] >= n_vertices)
+                    return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: facet " + std::to_string(q / 3) + " names vertex " +
+                                                                  std::to_string(facets[q]) + " of " + std::to_string(n_vertices));
+        } else {
+            if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
+            if (!iso_methods_ok(cluster_method, finish, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+        }
         if (h && h->tree.host_only()) return iso_fail(h, r, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
         if (h && h->group) {
             const int rc = group_rc(h, h->group->prepare_primary(true));
@@ -462,13 +504,38 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
             if (e != hipSuccess) return iso_fail(h, r, BBFMM_DEVICE_ERROR, std::string("isosurface: hipStreamCreate: ") + hipGetErrorString(e));
             own = true;
         }
-        bbfmm::iso::Request req;
-        req.isovalues = isovalues;
-        req.n_iso = n_isovalues;
-        req.host_field = values;
-        req.budget_bytes = batch_bytes;
-        req.cluster = cluster_method;
-        const int rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
+        int rc = BBFMM_OK;
+        if (one_mesh) {
+            r->meshes.assign(1, bbfmm::iso::Mesh());
+            double *d_v = nullptr;
+            int64_t *d_f = nullptr;
+            hipError_t e = hipSuccess;
+            if (n_facets > 0) {
+                e = hipMalloc(reinterpret_cast<void **>(&d_v), 3 * static_cast<size_t>(n_vertices) * sizeof(double));
+                if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_f), 3 * static_cast<size_t>(n_facets) * sizeof(int64_t));
+                if (e == hipSuccess) e = hipMemcpyAsync(d_v, vertices, 3 * static_cast<size_t>(n_vertices) * sizeof(double), hipMemcpyHostToDevice, st);
+                if (e == hipSuccess) e = hipMemcpyAsync(d_f, facets, 3 * static_cast<size_t>(n_facets) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+                if (e == hipSuccess) e = hipStreamSynchronize(st); // (pageable sources)
+            }
+            if (e != hipSuccess) {
+                rc = BBFMM_DEVICE_ERROR;
+                err = std::string("isosurface: upload of the mesh: ") + hipGetErrorString(e);
+            } else {
+                rc = bbfmm::iso::finish_device(d_v, n_vertices, d_f, n_facets, box, st, &r->meshes[0], &err);
+            }
+            (void)hipFree(d_v);
+            (void)hipFree(d_f);
+        } else {
+            bbfmm::iso::Request req;
+            req.isovalues = isovalues;
+            req.n_iso = n_isovalues;
+            req.host_field = values;
+            req.budget_bytes = batch_bytes;
+            req.cluster = cluster_method;
+            req.finish = finish;
+            req.extents = extents;
+            rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
+        }
         if (own) (void)hipStreamDestroy(st);
         if (rc != BBFMM_OK) return iso_fail(h, r, rc, err);
         return BBFMM_OK;
@@ -477,6 +544,88 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
     } catch (const std::exception &e) {
         return iso_fail(h, r, BBFMM_BAD_ARGUMENT, std::string("exception: ") + e.what());
     }
+}
+
+extern "C" {
+
+int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                               int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
+                               int32_t cluster_method, bbfmm_isosurface_result **out) {
+    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch_bytes, cluster_method,
+                                  BBFMM_FINISH_RAW, out);
+}
+
+int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                                 int32_t n_isovalues, const double *drift, double *d_field_out,
+                                 const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out) {
+    int32_t cluster, finish;
+    int64_t batch;
+    std::string err;
+    if (!iso_options(options, &cluster, &finish, &batch, &err)) {
+        if (out) *out = nullptr;
+        return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
+    }
+    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch, cluster, finish, out);
+}
+
+int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                       const double *isovalues, int32_t n_isovalues,
+                                       const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out) {
+    int32_t cluster, finish;
+    int64_t batch;
+    std::string err;
+    if (!iso_options(options, &cluster, &finish, &batch, &err)) {
+        if (out) *out = nullptr;
+        return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
+    }
+    return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch, cluster, finish, nullptr, 0, nullptr, 0,
+                                 false, out);
+}
+
+int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                 int64_t n_facets, const double *extents, bbfmm_isosurface_result **out) {
+    return isosurfaces_from_host(h, nullptr, extents, 0.0, nullptr, 0, 0, BBFMM_CLUSTER_NONE, BBFMM_FINISH_CLIPPED, vertices, n_vertices,
+                                 facets, n_facets, true, out);
+}
+
+int bbfmm_isosurface_finish_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(stats_out, r->meshes[i].finish_stats, sizeof(r->meshes[i].finish_stats));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_clip_triangle(const double *triangle, const double *extents, double *points_out, int32_t *corner_out,
+                                   int32_t *n_points_out) {
+    using namespace bbfmm::iso;
+    if (!triangle || !points_out || !n_points_out) return BBFMM_BAD_ARGUMENT;
+    ClipBox box;
+    std::string err;
+    if (!make_clip_box(extents, &box, &err)) return BBFMM_BAD_ARGUMENT;
+    double tri[3][3], pts[kClipMaxPoints][3];
+    int corner[kClipMaxPoints];
+    for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) tri[k][a] = triangle[3 * k + a];
+    const int n = clip_triangle(tri, box, pts, corner);
+    *n_points_out = n;
+    for (int k = 0; k < n; ++k) {
+        for (int a = 0; a < 3; ++a) points_out[3 * k + a] = pts[k][a];
+        if (corner_out) corner_out[k] = corner[k];
+    }
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                  bbfmm_isosurface_result **out) {
+    return bbfmm_isosurfaces_from_values_ex(h, values, extents, resolution, isovalues, n_isovalues, batch_bytes,
+                                            BBFMM_CLUSTER_NONE, out);
+}
+
+int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                     const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
+                                     int32_t cluster_method, bbfmm_isosurface_result **out) {
+    return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch_bytes, cluster_method, BBFMM_FINISH_RAW,
+                                 nullptr, 0, nullptr, 0, false, out);
 }
 
 int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r) { return r ? static_cast<int32_t>(r->meshes.size()) : -1; }

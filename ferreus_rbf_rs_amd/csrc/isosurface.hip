@@ -555,8 +555,8 @@ struct ClusterState {
 };
 
 // The clustered mesh of one isovalue of the resident field (DESIGN.md "Isosurfaces on the RMT lattice", clustering).
-int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, Pool &pool, hipStream_t st,
-                    Mesh *mesh, std::string *err) {
+int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, const ClipBox *clip, Pool &pool,
+                    hipStream_t st, Mesh *mesh, std::string *err) {
     const int g = grid_for(s.nodes);
     const size_t nodes = static_cast<size_t>(s.nodes);
     ISO_HIP(hipMemsetAsync(c.d_stats, 0, 16 * sizeof(unsigned long long), st));
@@ -647,6 +647,16 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
     }
     unsigned long long h_stats[16];
     ISO_HIP(hipMemcpyAsync(h_stats, c.d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+    if (clip) { // clipped and cleaned while still on the device
+        ISO_HIP(hipStreamSynchronize(st));
+        for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
+        pool.put(vinfo);
+        pool.put(vflag);
+        rc = finish_device(verts, nv, facets, nf, *clip, st, mesh, err);
+        pool.put(verts);
+        pool.put(facets);
+        return rc;
+    }
     mesh->vertices.resize(3 * static_cast<size_t>(nv));
     mesh->facets.resize(3 * static_cast<size_t>(nf));
     if (nv) ISO_HIP(hipMemcpyAsync(mesh->vertices.data(), verts, mesh->vertices.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -795,6 +805,13 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
         return BBFMM_BAD_ARGUMENT;
     }
+    const bool clipped = req.finish == kFinishClipped;
+    if (req.finish != kFinishRaw && !clipped) {
+        *err = "isosurface: unknown finish " + std::to_string(req.finish);
+        return BBFMM_BAD_ARGUMENT;
+    }
+    ClipBox clip_box;
+    if (clipped && !make_clip_box(req.extents, &clip_box, err)) return BBFMM_BAD_ARGUMENT;
     // bytes per k-plane: field, flags, indices, targets and the evaluator's per-target buffers; per isovalue masks,
     // vertex ids, counts and offsets
     const int64_t per_plane = P * (8 + 4 + 4 + 128 + 40 * static_cast<int64_t>(n_iso));
@@ -994,7 +1011,14 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     if (cluster) {
         const Slab box = slab_for(0, nk);
         for (int q = 0; q < n_iso; ++q) {
-            const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], pool, st, &(*meshes)[q], err);
+            const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], clipped ? &clip_box : nullptr, pool, st, &(*meshes)[q], err);
+            if (rc != BBFMM_OK) return rc;
+        }
+        return BBFMM_OK;
+    }
+    if (clipped) { // clipped and cleaned while still on the device
+        for (int q = 0; q < n_iso; ++q) {
+            const int rc = finish_device(states[q].v.p, states[q].vtotal, states[q].fc.p, states[q].ftotal, clip_box, st, &(*meshes)[q], err);
             if (rc != BBFMM_OK) return rc;
         }
         return BBFMM_OK;

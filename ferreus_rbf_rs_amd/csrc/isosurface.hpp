@@ -1,9 +1,11 @@
 // Dense marching tetrahedra on the regularised-marching-tetrahedra (RMT) sampling lattice: the triangles of
 // ferreus_rmt's build_isosurface with ClusterMethod::None (raw, one vertex per crossed lattice edge) or
 // ClusterMethod::Average (the intersections near a sample point merged where the topology tests allow it, with the
-// predicted-edge and non-manifold rollbacks), before clipping, cleaning and boundary closure, taken from every sample
-// point of the extraction domain in device passes instead of a CPU wavefront.  Contract: DESIGN.md "Isosurfaces on the
-// RMT lattice"; numpy restatements: tests/isosurface_restatement.py and tests/isosurface_cluster_restatement.py.
+// predicted-edge and non-manifold rollbacks), taken from every sample point of the extraction domain in device passes
+// instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
+// finished mesh of BoundaryClosure::None; boundary closure is not run).  Contract: DESIGN.md "Isosurfaces on the RMT
+// lattice"; numpy restatements: tests/isosurface_restatement.py, tests/isosurface_cluster_restatement.py and
+// tests/isosurface_finish_restatement.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -182,11 +184,113 @@ struct Lattice {
 // Validates (finite extents with lo <= hi, finite resolution > 0, a lattice of at most 2^36 box nodes) and fills *out.
 bool make_lattice(const double *extents, double resolution, Lattice *out, std::string *err);
 
+// ---- clip and clean (ferreus_rmt/src/aabb_clipping.rs, mesh_cleanup.rs; DESIGN.md "Clip and clean")
+struct ClipBox {
+    double lo[3], hi[3];
+    double eps; // bbox_eps (aabb_clipping.rs:40-48)
+};
+// Points a clipped triangle can hold: a convex polygon gains at most one point per plane (9); the slack covers polygons
+// that the snapping leaves non-convex by eps.  Points beyond it are not stored.
+constexpr int kClipMaxPoints = 12;
+
+__host__ __device__ inline double clip_abs(double x) { return x < 0 ? -x : x; }
+
+// snap_near_bbox (aabb_clipping.rs:148-168)
+__host__ __device__ inline void clip_snap_near(double *p, const ClipBox &b) {
+    for (int a = 0; a < 3; ++a) {
+        if (clip_abs(p[a] - b.lo[a]) <= b.eps) p[a] = b.lo[a];
+        if (clip_abs(p[a] - b.hi[a]) <= b.eps) p[a] = b.hi[a];
+    }
+}
+
+// point_inside_plane (aabb_clipping.rs:216-225); planes XMin, XMax, YMin, YMax, ZMin, ZMax
+__host__ __device__ inline bool clip_inside_plane(const double *p, int plane, const ClipBox &b) {
+    const int a = plane >> 1;
+    return (plane & 1) ? p[a] <= b.hi[a] + b.eps : p[a] >= b.lo[a] - b.eps;
+}
+
+// One triangle through clip_polygon_to_plane (aabb_clipping.rs:238-274) for the six planes in order.  Returns the
+// number of points of the polygon (0: dropped, fewer than 3 were left); corner[k]: the corner of the triangle that
+// point k is a kept copy of, -1 for a point made on a plane.
+__host__ __device__ inline int clip_triangle(const double tri[3][3], const ClipBox &b, double out[kClipMaxPoints][3],
+                                             int corner[kClipMaxPoints]) {
+#pragma clang fp contract(off)
+    double buf[2][kClipMaxPoints][3];
+    int src[2][kClipMaxPoints];
+    int n = 3, cur = 0;
+    for (int k = 0; k < 3; ++k) {
+        for (int a = 0; a < 3; ++a) buf[0][k][a] = tri[k][a];
+        src[0][k] = k;
+    }
+    for (int plane = 0; plane < 6 && n >= 3; ++plane) {
+        const int ax = plane >> 1;
+        const double c = (plane & 1) ? b.hi[ax] : b.lo[ax];
+        int m = 0;
+        const double *prev = buf[cur][n - 1];
+        bool prev_in = clip_inside_plane(prev, plane, b);
+        for (int i = 0; i < n; ++i) {
+            const double *curr = buf[cur][i];
+            const bool curr_in = clip_inside_plane(curr, plane, b);
+            if (curr_in != prev_in) {
+                // segment_plane_t (aabb_clipping.rs:186-213)
+                const double da = prev[ax] - c, db = curr[ax] - c;
+                bool has = true;
+                double t = 0.0;
+                if (clip_abs(da) <= b.eps) t = 0.0;
+                else if (clip_abs(db) <= b.eps) t = 1.0;
+                else if ((da < 0.0) == (db < 0.0)) has = false;
+                else t = (c - prev[ax]) / (curr[ax] - prev[ax]);
+                if (has && m < kClipMaxPoints) {
+                    double *q = buf[cur ^ 1][m];
+                    for (int a = 0; a < 3; ++a) q[a] = prev[a] + t * (curr[a] - prev[a]);
+                    q[ax] = c; // snap_to_plane
+                    clip_snap_near(q, b);
+                    src[cur ^ 1][m] = -1;
+                    ++m;
+                }
+            }
+            if (curr_in && m < kClipMaxPoints) {
+                double *q = buf[cur ^ 1][m];
+                for (int a = 0; a < 3; ++a) q[a] = curr[a];
+                clip_snap_near(q, b);
+                src[cur ^ 1][m] = src[cur][i];
+                ++m;
+            }
+            prev = curr;
+            prev_in = curr_in;
+        }
+        cur ^= 1;
+        n = m;
+    }
+    if (n < 3) return 0;
+    for (int k = 0; k < n; ++k) {
+        for (int a = 0; a < 3; ++a) out[k][a] = buf[cur][k][a];
+        corner[k] = src[cur][k];
+    }
+    return n;
+}
+
+// Mesh::finish_stats
+enum FinishStat : int {
+    kFinFacetsIn = 0,   // facets of the mesh that was clipped
+    kFinStraddling = 1, // kept by the clip with a corner outside the extents
+    kFinOutside = 2,    // dropped by the clip
+    kFinEmitted = 3,    // vertices the clip emitted (unwelded)
+    kFinWelded = 4,     // of those, welded into another
+    kFinLoose = 5,      // vertices further than eps from their representative (weld_loose)
+    kFinCollapsed = 6,
+    kFinTiny = 7,
+    kFinDuplicate = 8,
+    kFinLone = 9,
+    kFinStats = 10
+};
+
 // One mesh: row-major vertices (n x 3) and facets (m x 3).
 struct Mesh {
     std::vector<double> vertices;
     std::vector<int64_t> facets;
     int64_t stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // kStat*, all 0 without clustering
+    int64_t finish_stats[kFinStats] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // FinishStat, all 0 with kFinishRaw
 };
 
 // Mesh::stats: [0, 6) sample points per TopologyCase; mesh edges with more than 2 faces before pass A and the clusters
@@ -195,6 +299,20 @@ struct Mesh {
 constexpr int kStatOverA = 6, kStatSplitA = 7, kStatRolledB = 8, kStatOverB = 12, kRoundsB = 4;
 
 enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1 };
+enum Finish : int { kFinishRaw = 0, kFinishClipped = 1 };
+
+// Finite extents with lo <= hi as a ClipBox with its eps; false with *err set otherwise.
+bool make_clip_box(const double *extents, ClipBox *out, std::string *err);
+
+// The largest mesh finish_device takes: its vertex and corner ids are packed in 32 bits.
+constexpr int64_t kFinishMaxFacets = int64_t(1) << 26, kFinishMaxVertices = (int64_t(1) << 31) - 1;
+// false with *err set for a mesh over those limits (checked before any work).
+bool finish_fits(int64_t n_vertices, int64_t n_facets, std::string *err);
+
+// clean_mesh(clip_mesh_to_aabb(mesh)) of a mesh on the device (facet ids in [0, n_vertices)), on `stream`; the finished
+// mesh and its finish_stats go to *mesh on the host.  Returns a bbfmm_status.
+int finish_device(const double *d_vertices, int64_t n_vertices, const int64_t *d_facets, int64_t n_facets, const ClipBox &box,
+                  hipStream_t stream, Mesh *mesh, std::string *err);
 
 // Field values at m lattice nodes (SoA world coordinates on the device), written to d_vals[0..m) on the stream.
 // d_vals == nullptr: only check that every node can be evaluated (BBFMM_POINT_OUTSIDE_TREE otherwise).
@@ -208,6 +326,8 @@ struct Request {
     double *d_field_out = nullptr;     // device array over the box of E receiving the field (NaN off E), or null
     int64_t budget_bytes = 0;          // device memory for one batch of k-planes (<= 0: the default)
     int cluster = kClusterNone;        // kClusterAverage: the whole lattice field stays on the device (see extract)
+    int finish = kFinishRaw;           // kFinishClipped: every mesh goes through finish_device before its download
+    const double *extents = nullptr;   // the 6 extents of the lattice, needed with kFinishClipped
 };
 
 // Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.  With kClusterAverage

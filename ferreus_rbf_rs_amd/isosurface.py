@@ -1,8 +1,12 @@
 """Isosurfaces on the regularised-marching-tetrahedra (RMT) sampling lattice, extracted on the device.
 
-The mesh is ferreus_rmt's marching-tetrahedra output (`build_isosurface`, ferreus_rmt/src/isosurface.rs:489-) before
-`clip_mesh_to_aabb`, `clean_mesh` and boundary closure, taken over every sample point of the extraction domain instead
-of the sample points a seeded wavefront reaches (DESIGN.md "Isosurfaces on the RMT lattice").  `cluster="none"` (the
+The mesh is ferreus_rmt's marching-tetrahedra output (`build_isosurface`, ferreus_rmt/src/isosurface.rs:489-), taken
+over every sample point of the extraction domain instead of the sample points a seeded wavefront reaches (DESIGN.md
+"Isosurfaces on the RMT lattice").  `finish="raw"` (the default) is that mesh as it is, before `clip_mesh_to_aabb` and
+`clean_mesh`: it reaches two lattice cells past the extents.  `finish="clipped"` runs both on the device before the
+download (isosurface.rs:1009-1021): the reference's finished mesh for `BoundaryClosure::None`.  Boundary closure
+(`ClosePositive` / `CloseNegative`), the self-intersection rollback, `CurvatureWeighted` clustering and vertex
+gradients are not implemented.  `cluster="none"` (the
 default) is its `ClusterMethod::None`, one vertex per crossed lattice edge; `cluster="average"` its
 `ClusterMethod::Average`: the intersections near a sample point are merged into their mean where the topology tests
 allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 faces are split again
@@ -17,7 +21,11 @@ allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 f
   wavefront's t < 0.5 rule (isosurface.rs:588-610) with lerp_alpha (isosurface.rs:173-181);
 * facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order;
 * cluster="average": one vertex per cluster, ordered by sample point and lowest edge; triangles that two corners of
-  share a vertex are dropped; `return_stats=True` adds the counts of `STATS` per mesh.
+  share a vertex are dropped; `return_stats=True` adds the counts of `STATS` per mesh;
+* finish="clipped" (aabb_clipping.rs:55-105, mesh_cleanup.rs:32-96), with eps = 1e-10 * max(|hi - lo|, 1): every facet
+  clipped against the six planes of the extents in turn and fanned; vertices within eps welded, the lowest-index
+  vertex of a group its representative; collapsed, zero-area (|ab x ac|^2 <= eps^4), repeated and lone facets dropped;
+  vertices renumbered in order of first use.  `return_stats=True` then also holds the counts of `FINISH_STATS`.
 
 Lattice fields are arrays of shape (nk, nj, ni) over the bounding box of E (`lattice_info(...)["shape"]`, entry
 [0, 0, 0] at ijk `lattice_info(...)["lo"]`); entries off E are ignored, and NaN in returned fields.
@@ -102,6 +110,22 @@ CLUSTER_METHODS = {"none": 0, "average": 1}
 STATS = ("closed", "multi_hole", "flat_hole", "multi_surface", "simple", "incomplete")
 
 
+FINISH = {"raw": 0, "clipped": 1}
+# return_stats with finish="clipped" (bbfmm_isosurface_finish_stats)
+FINISH_STATS = ("facets_in", "straddling", "outside", "vertices_emitted", "welded", "weld_loose", "collapsed", "tiny",
+                "duplicate", "lone")
+
+
+def _finish(finish):
+    if finish not in FINISH:
+        raise ValueError(f"finish must be one of {sorted(FINISH)}, got {finish!r}")
+    return FINISH[finish]
+
+
+def _options(method, finish, batch_bytes):
+    return L.IsosurfaceOptions(ctypes.sizeof(L.IsosurfaceOptions), method, finish, int(batch_bytes))
+
+
 def _cluster(cluster):
     if cluster not in CLUSTER_METHODS:
         raise ValueError(f"cluster must be one of {sorted(CLUSTER_METHODS)}, got {cluster!r}")
@@ -144,7 +168,13 @@ def _stats(lib, res, i):
     return out
 
 
-def _meshes(lib, res, stats=False):
+def _finish_stats(lib, res, i):
+    s = np.zeros(len(FINISH_STATS), dtype=np.int64)
+    lib.bbfmm_isosurface_finish_stats(res, i, s.ctypes.data)
+    return {name: int(s[q]) for q, name in enumerate(FINISH_STATS)}
+
+
+def _meshes(lib, res, stats=False, finish=0):
     out = []
     for i in range(lib.bbfmm_isosurface_count(res)):
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
@@ -152,7 +182,13 @@ def _meshes(lib, res, stats=False):
         v = np.empty((nv.value, 3), dtype=np.float64)
         f = np.empty((nf.value, 3), dtype=np.int64)
         lib.bbfmm_isosurface_copy(res, i, v.ctypes.data, f.ctypes.data)
-        out.append((v, f, _stats(lib, res, i)) if stats else (v, f))
+        if stats:
+            st = _stats(lib, res, i)
+            if finish:
+                st["finish"] = _finish_stats(lib, res, i)
+            out.append((v, f, st))
+        else:
+            out.append((v, f))
     return out
 
 
@@ -168,11 +204,11 @@ def _raise(rc, msg, leaf=True):
 
 
 def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0,
-                      cluster="none", return_stats=False):
+                      cluster="none", return_stats=False, finish="raw"):
     """Meshes of the tree's field (set_local_coefficients first, one column) at each isovalue, one field evaluation
     for all of them; see FmmTree.build_isosurfaces."""
     lib = L.load()
-    method = _cluster(cluster)
+    method, fin = _cluster(cluster), _finish(finish)
     ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
     field_t = None
     if return_field:
@@ -182,14 +218,21 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
         field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
         torch.cuda.synchronize(field_t.device)
     res = ctypes.c_void_p()
-    rc = lib.bbfmm_build_isosurfaces_ex(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
-                                        d.ctypes.data if d is not None else None,
-                                        field_t.data_ptr() if field_t is not None else None, int(batch_bytes), method,
-                                        ctypes.byref(res))
+    if fin:
+        opts = _options(method, fin, batch_bytes)
+        rc = lib.bbfmm_build_isosurfaces_opts(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
+                                              d.ctypes.data if d is not None else None,
+                                              field_t.data_ptr() if field_t is not None else None, ctypes.addressof(opts),
+                                              ctypes.byref(res))
+    else:
+        rc = lib.bbfmm_build_isosurfaces_ex(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
+                                            d.ctypes.data if d is not None else None,
+                                            field_t.data_ptr() if field_t is not None else None, int(batch_bytes), method,
+                                            ctypes.byref(res))
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_last_error(tree._h).decode())
-        meshes = _meshes(lib, res, return_stats)
+        meshes = _meshes(lib, res, return_stats, fin)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
@@ -199,12 +242,13 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
 
 
 def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None,
-                            cluster="none", return_stats=False):
+                            cluster="none", return_stats=False, finish="raw"):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
-    current device (or the tree's).  cluster: "none" or "average" (see the module); return_stats: (vertices, facets,
-    stats) per mesh, stats the clustering counts (all 0 with "none")."""
+    current device (or the tree's).  cluster: "none" or "average", finish: "raw" or "clipped" (see the module);
+    return_stats: (vertices, facets, stats) per mesh, stats the clustering counts (all 0 with "none") and with
+    finish="clipped" under "finish" the counts of FINISH_STATS."""
     lib = L.load()
-    method = _cluster(cluster)
+    method, fin = _cluster(cluster), _finish(finish)
     ext, iso = _ext(extents), _isovalues(isovalues)
     vals = np.ascontiguousarray(np.asarray(lattice_values, dtype=np.float64))
     info = lattice_info(ext, resolution, tree)
@@ -212,20 +256,62 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
         raise ValueError(f"lattice_values must have shape {info['shape']}, got {vals.shape}")
     res = ctypes.c_void_p()
     h = tree._h if tree is not None else None
-    rc = lib.bbfmm_isosurfaces_from_values_ex(h, vals.ctypes.data, ext.ctypes.data, float(resolution), iso.ctypes.data,
-                                              len(iso), int(batch_bytes), method, ctypes.byref(res))
+    if fin:
+        opts = _options(method, fin, batch_bytes)
+        rc = lib.bbfmm_isosurfaces_from_values_opts(h, vals.ctypes.data, ext.ctypes.data, float(resolution),
+                                                    iso.ctypes.data, len(iso), ctypes.addressof(opts), ctypes.byref(res))
+    else:
+        rc = lib.bbfmm_isosurfaces_from_values_ex(h, vals.ctypes.data, ext.ctypes.data, float(resolution), iso.ctypes.data,
+                                                  len(iso), int(batch_bytes), method, ctypes.byref(res))
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
-        return _meshes(lib, res, return_stats)
+        return _meshes(lib, res, return_stats, fin)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
 
 
 def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None,
-                           cluster="none", return_stats=False):
+                           cluster="none", return_stats=False, finish="raw"):
     """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue, and its stats when
     return_stats."""
     return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree,
-                                   cluster=cluster, return_stats=return_stats)[0]
+                                   cluster=cluster, return_stats=return_stats, finish=finish)[0]
+
+
+def clip_mesh(vertices, facets, extents, return_stats=False, *, tree=None):
+    """finish="clipped" of a caller's own mesh on the current device (or the tree's): (vertices (n, 3) f64, facets
+    (m, 3) int64) clipped to the extents and cleaned, and the counts of FINISH_STATS when return_stats.  A mesh wholly
+    outside the extents gives (0, 3) arrays."""
+    lib = L.load()
+    ext = _ext(extents)
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(facets, dtype=np.int64).reshape(-1, 3))
+    res = ctypes.c_void_p()
+    h = tree._h if tree is not None else None
+    rc = lib.bbfmm_isosurface_finish_mesh(h, v.ctypes.data, len(v), f.ctypes.data, len(f), ext.ctypes.data,
+                                          ctypes.byref(res))
+    try:
+        if rc != L.OK:
+            _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface finish failed")
+        vo, fo = _meshes(lib, res)[0]
+        return (vo, fo, _finish_stats(lib, res, 0)) if return_stats else (vo, fo)
+    finally:
+        if res:
+            lib.bbfmm_isosurface_destroy(res)
+
+
+def clip_triangle(triangle, extents):
+    """(points (n, 3), corners (n,)) of one triangle clipped to the extents by the function the device runs (host only):
+    n = 0 when it is dropped; corners: the corner a point is a kept copy of, -1 for a point made on a plane."""
+    lib = L.load()
+    tri = np.ascontiguousarray(np.asarray(triangle, dtype=np.float64).reshape(-1))
+    if tri.shape != (9,):
+        raise ValueError("triangle must hold 3 points")
+    pts, corner, n = np.zeros((12, 3)), np.zeros(12, np.int32), ctypes.c_int32()
+    rc = lib.bbfmm_isosurface_clip_triangle(tri.ctypes.data, _ext(extents).ctypes.data, pts.ctypes.data, corner.ctypes.data,
+                                            ctypes.byref(n))
+    if rc != L.OK:
+        raise ValueError("extents must be finite with min <= max")
+    return pts[:n.value].copy(), corner[:n.value].copy()

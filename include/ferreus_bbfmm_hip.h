@@ -223,8 +223,11 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
                                          int64_t *bad_point_index);
 
 /* ---- Isosurfaces: dense marching tetrahedra on the RMT sampling lattice (ferreus_rmt build_isosurface with
- * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE its ClusterMethod::Average, before clipping,
- * cleaning and boundary closure; contract in DESIGN.md "Isosurfaces on the RMT lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
+ * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE its ClusterMethod::Average; the raw mesh
+ * before clipping and cleaning, or with the *_opts entries and BBFMM_FINISH_CLIPPED the mesh clipped to the extents and
+ * cleaned on the device, which is the reference's finished mesh for BoundaryClosure::None.  Boundary closure
+ * (ClosePositive / CloseNegative) and the self-intersection rollback are not implemented; contract in DESIGN.md
+ * "Isosurfaces on the RMT lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
  * nk x nj x ni doubles (i fastest) over the bounding box of the extraction nodes E; entries off E are ignored (NaN in
  * returned fields).  Vertices are n x 3 doubles, facets m x 3 int64 vertex ids, both row-major. */
 typedef struct bbfmm_isosurface_result bbfmm_isosurface_result; /* the meshes of one call, one per isovalue */
@@ -268,6 +271,44 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
  * clustered)]; [6] mesh edges with more than 2 faces before pass A, [7] clusters pass A split; [8..12) sample points
  * rolled back in rounds 1..4 of pass B, [12..16) mesh edges with more than 2 faces those rounds found. */
 int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* Finishing.  BBFMM_FINISH_RAW: the marching-tetrahedra mesh as it is (the entries above): it reaches two lattice cells
+ * past the extents and ends in open triangles there.  BBFMM_FINISH_CLIPPED: clip_mesh_to_aabb (aabb_clipping.rs:55-105)
+ * and clean_mesh (mesh_cleanup.rs:32-96) of ferreus_rmt run on the device before the one download, with
+ * eps = 1e-10 * max(|hi - lo|, 1): every facet clipped against the six planes of the extents and fanned, then vertices
+ * within eps welded (the representative of a group is its lowest-index vertex), collapsed, zero-area, repeated and
+ * lone facets dropped, and vertices renumbered in order of first use.  A mesh of more than 2^26 facets is refused
+ * before any work (ids are packed in 32 bits). */
+#define BBFMM_FINISH_RAW 0
+#define BBFMM_FINISH_CLIPPED 1
+/* Options of the *_opts entries.  size: sizeof(bbfmm_isosurface_options) as the caller was compiled; fields beyond it
+ * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0), as does every field with options == NULL. */
+typedef struct bbfmm_isosurface_options {
+    int64_t size;
+    int32_t cluster_method; /* BBFMM_CLUSTER_* */
+    int32_t finish;         /* BBFMM_FINISH_* */
+    int64_t batch_bytes;    /* device memory for one batch of k-planes (<= 0: a default) */
+} bbfmm_isosurface_options;
+int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
+                                 int32_t n_isovalues, const double *drift, double *d_field_out,
+                                 const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out);
+int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, const double *extents, double resolution,
+                                       const double *isovalues, int32_t n_isovalues,
+                                       const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out);
+/* BBFMM_FINISH_CLIPPED of a caller's own mesh (host arrays: n_vertices x 3 doubles, n_facets x 3 int64 ids) on the
+ * current device, or the handle's when h is not NULL: *out holds one mesh.  Messages as for
+ * bbfmm_isosurfaces_from_values. */
+int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                 int64_t n_facets, const double *extents, bbfmm_isosurface_result **out);
+/* The finishing counts of mesh i, stats_out[10] (all 0 with BBFMM_FINISH_RAW): [0] facets clipped, [1] of those kept
+ * with a corner outside the extents, [2] dropped by the clip; [3] vertices the clip emitted, [4] of those welded into
+ * another, [5] vertices further than eps from their representative (weld_loose; 0 where the weld is the reference's
+ * greedy one); facets dropped as [6] collapsed, [7] zero-area, [8] repeated, [9] lone. */
+int bbfmm_isosurface_finish_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* Host only: the clip of one triangle (9 doubles) by the function the device runs.  points_out: up to 12 x 3 doubles,
+ * corner_out (may be NULL): per point the corner of the triangle it is a kept copy of, -1 for a point made on a plane;
+ * n_points_out: 0 when the triangle is dropped. */
+int bbfmm_isosurface_clip_triangle(const double *triangle, const double *extents, double *points_out,
+                                   int32_t *corner_out, int32_t *n_points_out);
 /* Host only: the topology test the device runs, for one 14-bit near mask.  neighbour_values: f - isovalue at the 14
  * neighbours (EDGE_DELTAS order), or NULL to leave out the flat-hole test.  case_out: 0 closed, 1 multi-hole, 2 flat-hole,
  * 3 multi-surface, 4 simple.  cluster_of_edge[14]: the lowest edge of the cluster of each edge, -1 off the mask. */

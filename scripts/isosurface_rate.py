@@ -3,9 +3,12 @@
 isovalue; measured as the extraction of an isovalue that no node crosses), the whole call, the extraction share
 (whole minus field) and triangles per second: one JSON line per case, and the list to --out when given.  With
 --clusters none,average every case is timed with each method in the same run on the same tree (the field pass is the
-same work for both), and the clustering counts are recorded.
+same work for both), and the clustering counts are recorded.  With --finish raw,clipped every method is also timed
+with the mesh clipped to the extents and cleaned on the device: finish_ms is what "clipped" adds to the whole call of
+"raw" in the same run, clip_mesh_ms the same stage alone on the raw mesh (clip_mesh: with the upload of the mesh), and
+the finish counts are recorded.
 
-    python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--out FILE]
+    python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--finish raw,clipped] [--out FILE]
 """
 import argparse
 import json
@@ -29,27 +32,48 @@ def timed(fn, repeats):
     return min(ts) * 1e3, out
 
 
-def measure(te, ext, res, iso, repeats, label, cluster="none"):
+def measure(te, ext, res, iso, repeats, label, cluster="none", finish="raw", raw=None):
     from ferreus_rbf_rs_amd import isosurface as I
     info = I.lattice_info(ext, res)
     kw = {"cluster": cluster, "return_stats": True}
+    if finish != "raw":
+        kw["finish"] = finish
     t_all, (v, f, stats) = timed(lambda: te.build_isosurface(ext, res, iso, **kw), repeats)
     t_field, _ = timed(lambda: te.build_isosurface(ext, res, 1e300, **kw), repeats)   # nothing crosses: field + classify
-    rec = {"case": label, "cluster": cluster, "resolution": res, "lattice_shape": list(info["shape"]),
+    rec = {"case": label, "cluster": cluster, "finish": finish, "resolution": res, "lattice_shape": list(info["shape"]),
            "nodes_evaluated": info["n_nodes"],
            "keys": info["n_keys"], "vertices": int(len(v)), "facets": int(len(f)), "call_ms": t_all,
            "field_ms": t_field, "extraction_ms": t_all - t_field, "triangles_per_s": len(f) / (t_all * 1e-3),
            "nodes_per_s": info["n_nodes"] / (t_all * 1e-3)}
     if cluster != "none":
-        rec["stats"] = stats
+        rec["stats"] = {k: x for k, x in stats.items() if k != "finish"}
+    if finish != "raw":
+        rec["finish_stats"] = stats["finish"]
+        if raw is not None:                         # the raw record of the same run and its mesh
+            rec["finish_ms"] = t_all - raw[0]["call_ms"]
+            rec["clip_mesh_ms"], _ = timed(lambda: I.clip_mesh(raw[1], raw[2], ext, tree=te), repeats)
     print(json.dumps(rec), flush=True)
-    return rec
+    return (rec, v, f) if finish == "raw" else rec
+
+
+def measure_all(te, ext, res, iso, a, label):
+    recs = []
+    for method in a.clusters.split(","):
+        raw = None
+        for finish in a.finish.split(","):
+            if finish == "raw":
+                raw = measure(te, ext, res, iso, a.repeats, label, method)
+                recs.append(raw[0])
+            else:
+                recs.append(measure(te, ext, res, iso, a.repeats, label, method, finish, raw))
+    return recs
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--clusters", default="none", help="comma-separated cluster methods, each timed on every case")
+    ap.add_argument("--finish", default="raw", help="comma-separated finishes (raw first), each timed with every method")
     ap.add_argument("--out", default=None, help="JSON file for the list of results")
     a = ap.parse_args()
     import ferreus_rbf_rs_amd as F
@@ -71,8 +95,7 @@ def main():
     te = F.FmmTree(pts, 7, kp, True, False, extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
     te.set_weights(x[:, None].copy())
     te.set_local_coefficients(x[:, None].copy())
-    for method in a.clusters.split(","):
-        recs.append(measure(te, ext, res, 0.0, a.repeats, "albatite_spheroidal_r5", method))
+    recs += measure_all(te, ext, res, 0.0, a, "albatite_spheroidal_r5")
     del te, tree, pre
     # 1M points on and around a sphere of radius 1, Linear kernel, random weights (a smooth field, not a fit)
     rng = np.random.default_rng(1)
@@ -87,8 +110,7 @@ def main():
     t1.set_weights(w)
     t1.set_local_coefficients(w)
     fmid = float(np.median(t1.evaluate_leaves(None, p[:2000])))
-    for method in a.clusters.split(","):
-        recs.append(measure(t1, ext, res, fmid, a.repeats, "cloud_1M_linear", method))
+    recs += measure_all(t1, ext, res, fmid, a, "cloud_1M_linear")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
