@@ -5,12 +5,13 @@ as HIP kernels behind the C ABI in include/ferreus_bbfmm_hip.h.
 """
 from .fmm_tree import (FmmError, FmmKernelType, FmmParams, FmmTree, KernelDoesNotSupportGradients,
                        KernelParams, KernelType, M2LCompressionType, PointOutsideTree,
-                       SpheroidalOrder, mfma_f64_selftest, fp64_valu_selftest)
+                       SpheroidalOrder, mfma_f64_selftest, fp64_valu_selftest,
+                       debug_kernel_values, debug_math)
 
 from . import solvers  # noqa: E402  (FGMRES / Schwarz drivers, iterative_solvers.rs)
 from .isosurface import clip_mesh, isosurface_from_values, isosurfaces_from_values  # noqa: E402
 
 __all__ = ["solvers", "FmmTree", "FmmParams", "KernelParams", "KernelType", "FmmKernelType",
            "SpheroidalOrder", "M2LCompressionType", "FmmError", "PointOutsideTree",
-           "KernelDoesNotSupportGradients", "mfma_f64_selftest", "fp64_valu_selftest",
+           "KernelDoesNotSupportGradients", "mfma_f64_selftest", "fp64_valu_selftest", "debug_kernel_values", "debug_math",
            "isosurface_from_values", "isosurfaces_from_values", "clip_mesh"]

@@ -546,6 +546,17 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
     }
 }
 
+// The host loop of bbfmm_debug_kernel_values (a template: outside the extern "C" block).
+namespace {
+template <int ID>
+void debug_kernel_values_host(const bbfmm::KernelSpec &ks, const double *r2, int64_t n, double *value, double *value_g, double *factor) {
+    for (int64_t i = 0; i < n; ++i) {
+        value[i] = bbfmm::kernel_value_r2<ID>(ks, r2[i]);
+        value_g[i] = bbfmm::kernel_value_grad_r2<ID>(ks, r2[i], &factor[i]);
+    }
+}
+} // namespace
+
 extern "C" {
 
 int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
@@ -1015,6 +1026,50 @@ int bbfmm_debug_host_copy_rates(int64_t n, double *out4) {
     } catch (...) {
         return BBFMM_BAD_ARGUMENT;
     }
+}
+
+// Test hooks: the kernel functions and the arithmetic primitives of kernels.hpp, element by element.  where = 0 runs the
+// host branch in a plain loop (no device needed), where = 1 the device branch, one thread per element.
+int bbfmm_debug_kernel_values(int32_t where, int32_t kernel_id, double base_range, double total_sill, const double *r2, int64_t n,
+                              double *value_out, double *value_g_out, double *factor_out) {
+    if ((where != 0 && where != 1) || !bbfmm::kernel_id_valid(kernel_id) || n < 0 || !r2 || !value_out || !value_g_out || !factor_out)
+        return BBFMM_BAD_ARGUMENT;
+    const bbfmm::KernelSpec ks = bbfmm::make_kernel_spec(kernel_id, base_range, total_sill);
+    if (where == 0) {
+        switch (kernel_id) {
+#define BBFMM_DEBUG_CASE(ID) case bbfmm::ID: debug_kernel_values_host<bbfmm::ID>(ks, r2, n, value_out, value_g_out, factor_out); break;
+        BBFMM_DEBUG_CASE(kLinear) BBFMM_DEBUG_CASE(kThinPlateSpline) BBFMM_DEBUG_CASE(kCubic) BBFMM_DEBUG_CASE(kSpheroidal3)
+        BBFMM_DEBUG_CASE(kSpheroidal5) BBFMM_DEBUG_CASE(kSpheroidal7) BBFMM_DEBUG_CASE(kSpheroidal9) BBFMM_DEBUG_CASE(kLaplacian)
+        BBFMM_DEBUG_CASE(kOneOverR2) BBFMM_DEBUG_CASE(kOneOverR4) BBFMM_DEBUG_CASE(kGaussianExt) BBFMM_DEBUG_CASE(kMultiquadricExt)
+#undef BBFMM_DEBUG_CASE
+        default: return BBFMM_BAD_ARGUMENT;
+        }
+        return BBFMM_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BBFMM_DEVICE_ERROR;
+    return bbfmm::debug_kernel_values_device(ks, r2, n, value_out, value_g_out, factor_out) == 0 ? BBFMM_OK : BBFMM_DEVICE_ERROR;
+}
+
+int bbfmm_debug_math(int32_t where, int32_t which, const double *x, int64_t n, double *out, double *out2) {
+    if ((where != 0 && where != 1) || which < 0 || which > 3 || n < 0 || !x || !out) return BBFMM_BAD_ARGUMENT;
+    if (where == 0) {
+        for (int64_t i = 0; i < n; ++i) {
+            double a = 0.0, b = 0.0;
+            switch (which) {
+            case 0: a = bbfmm::bb_sqrt(x[i]); break;
+            case 1: bbfmm::bb_sqrt_rsqrt(x[i], &a, &b); break;
+            case 2: a = bbfmm::bb_rcp(x[i]); break;
+            default: a = bbfmm::bb_log(x[i]); break;
+            }
+            out[i] = a;
+            if (out2) out2[i] = b;
+        }
+        return BBFMM_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return BBFMM_DEVICE_ERROR;
+    return bbfmm::debug_math_device(which, x, n, out, out2) == 0 ? BBFMM_OK : BBFMM_DEVICE_ERROR;
 }
 
 // Test hooks (host only): dense M2M matrix of the reference and the stacked-table M2L.

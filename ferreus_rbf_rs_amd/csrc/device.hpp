@@ -206,5 +206,9 @@ bool l2p_order_supported(int p, int d);
 int mfma_f64_selftest(double *tflops, int *layout_errors, double *info);
 // FP64 vector-ALU peak: chip-wide v_fma_f64 rate (TFLOP/s) and the shader clock it runs at (MHz).
 int valu_f64_selftest(double *tflops, double *mhz);
+// Element-wise test hooks: kernel_value_r2 / kernel_value_grad_r2 of ks.id, and bb_sqrt (which = 0), bb_sqrt_rsqrt (1: out
+// and out2), bb_rcp (2), bb_log (3), one thread per element of a host array through the device branch of kernels.hpp.
+int debug_kernel_values_device(const KernelSpec &ks, const double *r2, int64_t n, double *value, double *value_g, double *factor);
+int debug_math_device(int which, const double *x, int64_t n, double *out, double *out2);
 
 } // namespace bbfmm

@@ -10,7 +10,7 @@
 //   device_m2l.hip         M2L             two batched small-GEMM stages on v_mfma_f64_4x4x4_f64; operator assembly
 //   device_p2p.hip         P2P             direct kernel evaluation, LDS-tiled sources, lanes = target x slice
 //   device_wx.hip          M2P / P2L       the same against Chebyshev nodes (pieces shared with P2P: device_direct.hpp)
-//   device_selftest.hip    FP64 matrix- and vector-pipe peaks
+//   device_selftest.hip    FP64 matrix- and vector-pipe peaks; the element-wise test hooks on kernels.hpp
 //
 // This header is internal to those files: what more than one of them uses.
 #pragma once

@@ -1,7 +1,8 @@
-// Peak self-tests of the FP64 matrix and vector pipes (what bench.py quotes its roofs from).
+// Peak self-tests of the FP64 matrix and vector pipes (what bench.py quotes its roofs from), and the element-wise test
+// hooks that run the kernel functions of kernels.hpp on the device.
 #include <vector>
 
-#include "device.hpp"
+#include "device_common.hpp"
 
 namespace bbfmm {
 
@@ -177,6 +178,77 @@ int valu_f64_selftest(double *tflops, double *mhz) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return 0;
+}
+
+// ------------------------------------------------------------------ element-wise test hooks (bbfmm_debug_kernel_values / _math)
+// One thread per element through the device branch of kernels.hpp: the very functions the pair kernels inline.
+template <int ID>
+__global__ __launch_bounds__(256) void debug_kernel_values_kernel(KernelSpec ks, const double *__restrict__ r2, int64_t n,
+                                                                  double *__restrict__ value, double *__restrict__ value_g,
+                                                                  double *__restrict__ factor) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = r2[i];
+    value[i] = kernel_value_r2<ID>(ks, x);
+    double f;
+    value_g[i] = kernel_value_grad_r2<ID>(ks, x, &f);
+    factor[i] = f;
+}
+
+__global__ __launch_bounds__(256) void debug_math_kernel(int which, const double *__restrict__ x, int64_t n,
+                                                         double *__restrict__ out, double *__restrict__ out2) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double a = 0.0, b = 0.0;
+    switch (which) {
+    case 0: a = bb_sqrt(x[i]); break;
+    case 1: bb_sqrt_rsqrt(x[i], &a, &b); break;
+    case 2: a = bb_rcp(x[i]); break;
+    default: a = bb_log(x[i]); break;
+    }
+    out[i] = a;
+    if (out2) out2[i] = b;
+}
+
+namespace {
+// n_in host doubles up, n_out arrays of n doubles down; `launch` gets the device pointers (input first).
+template <class Launch> int debug_elementwise(const double *in, int64_t n, double *const *outs, int n_out, Launch &&launch) {
+    if (n == 0) return 0;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    double *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    for (int q = 0; q <= n_out && rc == 0; ++q)
+        if (hipMalloc(&d[q], bytes) != hipSuccess) rc = 1;
+    if (rc == 0 && hipMemcpy(d[0], in, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
+    if (rc == 0) {
+        launch(d);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
+    }
+    for (int q = 0; q < n_out && rc == 0; ++q)
+        if (outs[q] && hipMemcpy(outs[q], d[q + 1], bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = 1;
+    for (double *p : d)
+        if (p) (void)hipFree(p);
+    return rc;
+}
+} // namespace
+
+int debug_kernel_values_device(const KernelSpec &ks, const double *r2, int64_t n, double *value, double *value_g, double *factor) {
+    double *outs[3] = {value, value_g, factor};
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    return debug_elementwise(r2, n, outs, 3, [&](double **d) {
+        dispatch_kernel_id(ks.id, [&](auto idc) {
+            hipLaunchKernelGGL((debug_kernel_values_kernel<decltype(idc)::value>), dim3(blocks), dim3(256), 0, 0, ks, d[0], n, d[1],
+                               d[2], d[3]);
+        });
+    });
+}
+
+int debug_math_device(int which, const double *x, int64_t n, double *out, double *out2) {
+    double *outs[2] = {out, out2};
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    return debug_elementwise(x, n, outs, 2, [&](double **d) {
+        hipLaunchKernelGGL(debug_math_kernel, dim3(blocks), dim3(256), 0, 0, which, d[0], n, d[1], out2 ? d[2] : nullptr);
+    });
 }
 
 } // namespace bbfmm

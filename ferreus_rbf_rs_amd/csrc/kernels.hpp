@@ -71,7 +71,8 @@ inline KernelSpec make_kernel_spec(int id, double base_range, double total_sill)
 // FMAs.  x >= 0 always (sums of squares).
 // Round 6: ONE cubic step instead of the two-stage Goldschmidt refinement of rounds 1-5.  The seed y = v_rsq_f64(x) is good to
 // 5.2e-8 (scripts/rsq_accuracy.hip), e = 1 - x y^2 is twice that, and 1 / sqrt(1 - e) = 1 + e/2 + 3 e^2/8 + O(e^3) leaves a
-// truncation of 3e-22: the result is within 2 ulp of the correctly rounded root (measured: rsq_accuracy.hip), for five
+// truncation of 3e-22: the result is within 2 ulp of the correctly rounded root (tests/test_gpu_kernel_pointwise.py holds that bound against
+// extended precision over 2^-200..2^200; the measured maximum is in profiles/kernel_function_accuracy.json), for five
 // instructions behind the seed where the two-stage form took seven (sqrt) and ten (sqrt and 1/sqrt) -- 17 -> 15 FP64
 // instructions per LinearRbf pair, 28 -> 24 per Spheroidal3 pair, in kernels that run at the FP64 issue roof.  The reference's
 // own sqrt is the correctly rounded one; two ulp per kernel value sit five orders below the 1e-11 the parity tests hold.
@@ -188,9 +189,11 @@ template <int ID> BBFMM_HD inline double kernel_value_r2(const KernelSpec &k, do
 #endif
     } else if constexpr (ID == kLaplacian) { // non_rbf_kernels.rs:20-37: 0 if |r| < eps, else 1 / r
 #if defined(__HIP_DEVICE_COMPILE__)
+        // |r| < eps  <=>  r2 < eps^2 for the reference's correctly rounded root; the refined root below is up to 2 ulp off
+        // and would put r2 = eps^2 (1 + k 2^-52), k = 0..2, on the zero side (tests/test_gpu_kernel_pointwise.py)
         double sq, rs;
         bb_sqrt_rsqrt(r2, &sq, &rs);
-        return (sq < DBL_EPSILON) ? 0.0 : rs;
+        return (r2 < DBL_EPSILON * DBL_EPSILON) ? 0.0 : rs;
 #else
         const double r = sqrt(r2);
         return (fabs(r) < DBL_EPSILON) ? 0.0 : 1.0 / r;

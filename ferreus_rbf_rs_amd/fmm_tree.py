@@ -596,3 +596,30 @@ def mfma_f64_selftest():
                                        "cycles_per_mfma_per_simd_busy", "clock_mhz_busy",
                                        "tflops_1wave_per_simd", "tflops_2waves_per_simd"], list(info)))
     return tf.value, errs.value
+
+
+def debug_kernel_values(where: int, kernel_id: int, base_range: float, total_sill: float, r2):
+    """(value, value of the gradient path, gradient factor) of kernel `kernel_id` at each squared distance of r2, through
+    the functions of csrc/kernels.hpp: where = 0 the host branch (no device needed), where = 1 the device branch."""
+    x = np.ascontiguousarray(r2, dtype=np.float64).ravel()
+    v, vg, f = np.empty_like(x), np.empty_like(x), np.empty_like(x)
+    rc = L.load().bbfmm_debug_kernel_values(where, kernel_id, float(base_range), float(total_sill), x.ctypes.data, x.size,
+                                            v.ctypes.data, vg.ctypes.data, f.ctypes.data)
+    if rc != L.OK:
+        raise RuntimeError(f"bbfmm_debug_kernel_values failed with status {rc}")
+    return v, vg, f
+
+
+DEBUG_MATH = {"sqrt": 0, "sqrt_rsqrt": 1, "rcp": 2, "log": 3}
+
+
+def debug_math(where: int, which: str, x):
+    """bb_sqrt / bb_sqrt_rsqrt / bb_rcp / bb_log of csrc/kernels.hpp element by element (where as in debug_kernel_values);
+    "sqrt_rsqrt" returns the pair (sqrt, 1 / sqrt)."""
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out, out2 = np.empty_like(x), np.empty_like(x)
+    rc = L.load().bbfmm_debug_math(where, DEBUG_MATH[which], x.ctypes.data, x.size, out.ctypes.data,
+                                   out2.ctypes.data if which == "sqrt_rsqrt" else None)
+    if rc != L.OK:
+        raise RuntimeError(f"bbfmm_debug_math failed with status {rc}")
+    return (out, out2) if which == "sqrt_rsqrt" else out

@@ -512,7 +512,7 @@ int bbfmm_get_phase_ms(bbfmm_handle *h, double *ms_out, int64_t *count_out);
 int bbfmm_reset_phase_ms(bbfmm_handle *h);
 
 /* FP64 MFMA self-test + peak microbenchmark (device): returns measured TFLOP/s of
- * back-to-back v_mfma_f64_16x16x4 in *tflops and 0 mismatches in *layout_errors when
+ * back-to-back v_mfma_f64_4x4x4 in *tflops and 0 mismatches in *layout_errors when
  * the lane layout assumed by the M2L kernels holds on this device.  info6 (optional, 6 doubles):
  * cycles/MFMA of a lone wave, its clock (MHz), cycles/MFMA/SIMD and clock with every CU busy at
  * 1 wave/SIMD, TFLOP/s at 1 and at 2 waves/SIMD. */
@@ -522,7 +522,19 @@ int bbfmm_mfma_f64_selftest(double *tflops, int32_t *layout_errors, double *info
  * 2.4 GHz. */
 int bbfmm_fp64_valu_selftest(double *tflops, double *clock_mhz);
 
-/* ---- test hooks (host loops, no device; never reached from a compute entry point) ----
+/* ---- test hooks (never reached from a compute entry point) ----
+ * The kernel functions of csrc/kernels.hpp, element by element: for each r2[i] (a squared distance) value_out[i] is the
+ * kernel value as the value passes compute it, value_g_out[i] / factor_out[i] the value and the scalar `factor`
+ * (gradient = factor * (target - source)) as the gradient passes compute them.  where = 0: the host branch (libm and
+ * IEEE division: what assembles the M2L operators) in a plain loop, no device needed; where = 1: the device branch (what
+ * every P2P / M2P / P2L pair is evaluated with), one thread per element.  Arrays are host memory, n doubles each. */
+int bbfmm_debug_kernel_values(int32_t where, int32_t kernel_id, double base_range, double total_sill, const double *r2,
+                              int64_t n, double *value_out, double *value_g_out, double *factor_out);
+/* The arithmetic primitives under them: which = 0 bb_sqrt, 1 bb_sqrt_rsqrt (sqrt in out, 1/sqrt in out2), 2 bb_rcp
+ * (x > 0, finite), 3 bb_log (x > 0, normal).  out2 may be NULL.  where as above. */
+int bbfmm_debug_math(int32_t where, int32_t which, const double *x, int64_t n, double *out, double *out2);
+
+/* ---- test hooks (host loops, no device) ----
  * Dense n x n (column-major) M2M matrix of child `child_index` exactly as the reference
  * stores it (chebyshev.rs:216-240); the device applies the same operator sum-factorised. */
 int bbfmm_debug_dense_m2m(const bbfmm_handle *h, int32_t child_index, double *out);

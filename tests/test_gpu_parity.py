@@ -65,8 +65,9 @@ def test_fp64_valu_microbenchmark():
 
 def test_get_distance_doctest_through_the_device_near_field():
     """ferreus_rbf_utils/src/utils.rs:263-280: the distance from (1, 2) to (4, 6) is 5.  Two points, linear kernel
-    phi(r) = -r (rbf_kernels.rs:25-36), unit weights: both potentials are -5 -- exactly, the device square root
-    (v_rsq_f64 + Goldschmidt, kernels.hpp) being correctly rounded; through evaluate (ordered pairs) and through the
+    phi(r) = -r (rbf_kernels.rs:25-36), unit weights: both potentials are -5 -- exactly: the device square root
+    (v_rsq_f64 + one cubic step, kernels.hpp) is within 2 ulp of the correctly rounded root in general
+    (tests/test_gpu_kernel_pointwise.py) and exact at this argument; through evaluate (ordered pairs) and through the
     matvec entry point (unordered pairs)."""
     pts = np.array([[1.0, 2.0], [4.0, 6.0]])
     w = np.ones((2, 1))
