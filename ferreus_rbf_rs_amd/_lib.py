@@ -79,6 +79,10 @@ SIGNATURES = {
     "bbfmm_isosurfaces_from_values_opts": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_p, c_p]),
     "bbfmm_isosurface_finish_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_intersection_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_self_intersections": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "bbfmm_isosurface_intersection_ids": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
+    "bbfmm_isosurface_triangle_pair": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_isosurface_clip_triangle": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_isosurface_topology": (ctypes.c_int, [ctypes.c_uint32, c_p, c_p, c_p]),
     "bbfmm_isosurface_cluster_tables": (ctypes.c_int, [c_p, c_p, c_p]),
@@ -179,7 +183,8 @@ FLAG_GLOBAL_SCALING = 1
 
 class IsosurfaceOptions(ctypes.Structure):
     """bbfmm_isosurface_options"""
-    _fields_ = [("size", c_i64), ("cluster_method", c_i32), ("finish", c_i32), ("batch_bytes", c_i64)]
+    _fields_ = [("size", c_i64), ("cluster_method", c_i32), ("finish", c_i32), ("batch_bytes", c_i64),
+                ("self_intersections", c_i32)]
 
 
 class DdmParams(ctypes.Structure):

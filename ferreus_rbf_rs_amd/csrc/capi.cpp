@@ -15,6 +15,7 @@
 #include "ferreus_bbfmm_hip.h"
 #include "fmm_tree.hpp"
 #include "isosurface.hpp"
+#include "isosurface_intersect.hpp"
 #include "morton.hpp"
 
 struct bbfmm_handle {
@@ -295,10 +296,12 @@ static bool iso_args(const double *extents, double resolution, const double *iso
 }
 
 // The fields of *o that its size covers; defaults for the rest and for o == nullptr.
-static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int32_t *finish, int64_t *batch_bytes, std::string *err) {
+static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int32_t *finish, int64_t *batch_bytes,
+                        int32_t *self_intersections, std::string *err) {
     *cluster = BBFMM_CLUSTER_NONE;
     *finish = BBFMM_FINISH_RAW;
     *batch_bytes = 0;
+    *self_intersections = BBFMM_SELF_INTERSECTIONS_IGNORE;
     if (!o) return true;
     if (o->size < static_cast<int64_t>(sizeof(int64_t))) {
         *err = "isosurface: options->size must be sizeof(bbfmm_isosurface_options)";
@@ -307,10 +310,16 @@ static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int
     if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, cluster_method) + sizeof(int32_t))) *cluster = o->cluster_method;
     if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, finish) + sizeof(int32_t))) *finish = o->finish;
     if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, batch_bytes) + sizeof(int64_t))) *batch_bytes = o->batch_bytes;
+    if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, self_intersections) + sizeof(int32_t)))
+        *self_intersections = o->self_intersections;
     return true;
 }
 
-static bool iso_methods_ok(int32_t cluster, int32_t finish, std::string *err) {
+static bool iso_methods_ok(int32_t cluster, int32_t finish, int32_t self_intersections, std::string *err) {
+    if (self_intersections != BBFMM_SELF_INTERSECTIONS_IGNORE && self_intersections != BBFMM_SELF_INTERSECTIONS_ROLLBACK) {
+        *err = "isosurface: unknown self-intersection handling " + std::to_string(self_intersections);
+        return false;
+    }
     if (cluster != BBFMM_CLUSTER_NONE && cluster != BBFMM_CLUSTER_AVERAGE) {
         *err = "isosurface: unknown cluster method " + std::to_string(cluster);
         return false;
@@ -401,13 +410,14 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
 
 static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                   int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
-                                  int32_t cluster_method, int32_t finish, bbfmm_isosurface_result **out) {
+                                  int32_t cluster_method, int32_t finish, int32_t self_intersections,
+                                  bbfmm_isosurface_result **out) {
     GUARD(h)
     if (out) *out = nullptr;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     {
         std::string bad;
-        if (!iso_methods_ok(cluster_method, finish, &bad)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, bad);
+        if (!iso_methods_ok(cluster_method, finish, self_intersections, &bad)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, bad);
     }
     if (h->tree.tree().d != 3) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: only supported for 3D (d = 3)");
     bbfmm::iso::Lattice lat;
@@ -447,6 +457,7 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
     req.cluster = cluster_method;
     req.finish = finish;
     req.extents = extents;
+    req.self_intersections = self_intersections;
     std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
     const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);
     if (rc != BBFMM_OK) {
@@ -459,11 +470,14 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
     END_GUARD(h)
 }
 
-// A host mesh (one_mesh) or a host field through extract(), on the handle's stream or one of the call's own.
+// A host mesh (mesh_op: clip and clean, or the self-intersection detector) or a host field through extract(), on the
+// handle's stream or one of the call's own.
+enum IsoMeshOp : int { kIsoField = 0, kIsoFinishMesh = 1, kIsoDetectMesh = 2 };
 static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes, int32_t cluster_method,
-                                 int32_t finish, const double *vertices, int64_t n_vertices, const int64_t *facets, int64_t n_facets,
-                                 bool one_mesh, bbfmm_isosurface_result **out) {
+                                 int32_t finish, int32_t self_intersections, const double *vertices, int64_t n_vertices,
+                                 const int64_t *facets, int64_t n_facets, int mesh_op, bbfmm_isosurface_result **out) {
+    const bool one_mesh = mesh_op != kIsoField, detect = mesh_op == kIsoDetectMesh;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     *out = nullptr;
     bbfmm_isosurface_result *r = nullptr;
@@ -479,18 +493,22 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
         std::string err;
         if (one_mesh) {
             // everything is checked before any work: the box, the sizes the id packing holds, the ids
-            if (!bbfmm::iso::make_clip_box(extents, &box, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
-            if (!bbfmm::iso::finish_fits(n_vertices, n_facets, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if ((!detect || extents) && !bbfmm::iso::make_clip_box(extents, &box, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if (!detect && !bbfmm::iso::finish_fits(n_vertices, n_facets, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
             if ((n_vertices > 0 && !vertices) || (n_facets > 0 && !facets))
                 return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: vertices and facets must not be null");
             for (int64_t q = 0; q < 3 * n_facets; ++q)
                 if (facets[q] < 0 || facets[q] >= n_vertices)
                     return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: facet " + std::to_string(q / 3) + " names vertex " +
                                                                   std::to_string(facets[q]) + " of " + std::to_string(n_vertices));
+            if (detect)
+                for (int64_t q = 0; q < 3 * n_vertices; ++q)
+                    if (!std::isfinite(vertices[q]))
+                        return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: vertex " + std::to_string(q / 3) + " is not finite");
         } else {
             if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
             if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
-            if (!iso_methods_ok(cluster_method, finish, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if (!iso_methods_ok(cluster_method, finish, self_intersections, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
         }
         if (h && h->tree.host_only()) return iso_fail(h, r, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
         if (h && h->group) {
@@ -509,9 +527,11 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
             r->meshes.assign(1, bbfmm::iso::Mesh());
             double *d_v = nullptr;
             int64_t *d_f = nullptr;
+            uint8_t *d_flag = nullptr;
             hipError_t e = hipSuccess;
             if (n_facets > 0) {
                 e = hipMalloc(reinterpret_cast<void **>(&d_v), 3 * static_cast<size_t>(n_vertices) * sizeof(double));
+                if (e == hipSuccess && detect) e = hipMalloc(reinterpret_cast<void **>(&d_flag), static_cast<size_t>(n_facets));
                 if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_f), 3 * static_cast<size_t>(n_facets) * sizeof(int64_t));
                 if (e == hipSuccess) e = hipMemcpyAsync(d_v, vertices, 3 * static_cast<size_t>(n_vertices) * sizeof(double), hipMemcpyHostToDevice, st);
                 if (e == hipSuccess) e = hipMemcpyAsync(d_f, facets, 3 * static_cast<size_t>(n_facets) * sizeof(int64_t), hipMemcpyHostToDevice, st);
@@ -520,11 +540,27 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
             if (e != hipSuccess) {
                 rc = BBFMM_DEVICE_ERROR;
                 err = std::string("isosurface: upload of the mesh: ") + hipGetErrorString(e);
+            } else if (detect) {
+                bbfmm::iso::Mesh &m = r->meshes[0];
+                rc = bbfmm::iso::self_intersections_device(d_v, n_vertices, d_f, n_facets, extents ? &box : nullptr, st, d_flag,
+                                                           m.isect_stats, &err);
+                if (rc == BBFMM_OK && m.isect_stats[bbfmm::iso::kIsectTriangles] > 0) { // the sorted ids: the flags in facet order
+                    std::vector<uint8_t> flag(static_cast<size_t>(n_facets));
+                    e = hipMemcpyAsync(flag.data(), d_flag, flag.size(), hipMemcpyDeviceToHost, st);
+                    if (e == hipSuccess) e = hipStreamSynchronize(st);
+                    if (e != hipSuccess) {
+                        rc = BBFMM_DEVICE_ERROR;
+                        err = std::string("isosurface: download of the flags: ") + hipGetErrorString(e);
+                    }
+                    for (int64_t t = 0; rc == BBFMM_OK && t < n_facets; ++t)
+                        if (flag[t]) m.isect_ids.push_back(t);
+                }
             } else {
                 rc = bbfmm::iso::finish_device(d_v, n_vertices, d_f, n_facets, box, st, &r->meshes[0], &err);
             }
             (void)hipFree(d_v);
             (void)hipFree(d_f);
+            (void)hipFree(d_flag);
         } else {
             bbfmm::iso::Request req;
             req.isovalues = isovalues;
@@ -534,6 +570,7 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
             req.cluster = cluster_method;
             req.finish = finish;
             req.extents = extents;
+            req.self_intersections = self_intersections;
             rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
         }
         if (own) (void)hipStreamDestroy(st);
@@ -563,40 +600,76 @@ int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double re
                                int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
                                int32_t cluster_method, bbfmm_isosurface_result **out) {
     return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch_bytes, cluster_method,
-                                  BBFMM_FINISH_RAW, out);
+                                  BBFMM_FINISH_RAW, BBFMM_SELF_INTERSECTIONS_IGNORE, out);
 }
 
 int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                  int32_t n_isovalues, const double *drift, double *d_field_out,
                                  const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out) {
-    int32_t cluster, finish;
+    int32_t cluster, finish, isect;
     int64_t batch;
     std::string err;
-    if (!iso_options(options, &cluster, &finish, &batch, &err)) {
+    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err)) {
         if (out) *out = nullptr;
         return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
     }
-    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch, cluster, finish, out);
+    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch, cluster, finish, isect, out);
 }
 
 int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                        const double *isovalues, int32_t n_isovalues,
                                        const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out) {
-    int32_t cluster, finish;
+    int32_t cluster, finish, isect;
     int64_t batch;
     std::string err;
-    if (!iso_options(options, &cluster, &finish, &batch, &err)) {
+    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err)) {
         if (out) *out = nullptr;
         return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
     }
-    return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch, cluster, finish, nullptr, 0, nullptr, 0,
-                                 false, out);
+    return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch, cluster, finish, isect, nullptr, 0,
+                                 nullptr, 0, kIsoField, out);
 }
 
 int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
                                  int64_t n_facets, const double *extents, bbfmm_isosurface_result **out) {
-    return isosurfaces_from_host(h, nullptr, extents, 0.0, nullptr, 0, 0, BBFMM_CLUSTER_NONE, BBFMM_FINISH_CLIPPED, vertices, n_vertices,
-                                 facets, n_facets, true, out);
+    return isosurfaces_from_host(h, nullptr, extents, 0.0, nullptr, 0, 0, BBFMM_CLUSTER_NONE, BBFMM_FINISH_CLIPPED,
+                                 BBFMM_SELF_INTERSECTIONS_IGNORE, vertices, n_vertices, facets, n_facets, kIsoFinishMesh, out);
+}
+
+int bbfmm_isosurface_self_intersections(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                        int64_t n_facets, const double *extents, bbfmm_isosurface_result **out) {
+    return isosurfaces_from_host(h, nullptr, extents, 0.0, nullptr, 0, 0, BBFMM_CLUSTER_NONE, BBFMM_FINISH_RAW,
+                                 BBFMM_SELF_INTERSECTIONS_IGNORE, vertices, n_vertices, facets, n_facets, kIsoDetectMesh, out);
+}
+
+int bbfmm_isosurface_intersection_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(stats_out, r->meshes[i].isect_stats, sizeof(r->meshes[i].isect_stats));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_intersection_ids(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_ids_out, int64_t *ids_out) {
+    if (!r || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    const std::vector<int64_t> &ids = r->meshes[i].isect_ids;
+    if (n_ids_out) *n_ids_out = static_cast<int64_t>(ids.size());
+    if (ids_out && !ids.empty()) std::memcpy(ids_out, ids.data(), ids.size() * sizeof(int64_t));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_triangle_pair(const double *tri_a, const int64_t *ids_a, const double *tri_b, const int64_t *ids_b,
+                                   int32_t *result_out, int32_t *stage_out) {
+    using namespace bbfmm::iso;
+    if (!tri_a || !ids_a || !tri_b || !ids_b || !result_out) return BBFMM_BAD_ARGUMENT;
+    Tri3 a, b;
+    for (int k = 0; k < 3; ++k)
+        for (int x = 0; x < 3; ++x) {
+            a.p[k].x[x] = tri_a[3 * k + x];
+            b.p[k].x[x] = tri_b[3 * k + x];
+        }
+    int stage = 0;
+    *result_out = triangle_pair(a, ids_a, b, ids_b, &stage) ? 1 : 0;
+    if (stage_out) *stage_out = stage;
+    return BBFMM_OK;
 }
 
 int bbfmm_isosurface_finish_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
@@ -636,7 +709,7 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
                                      const double *isovalues, int32_t n_isovalues, int64_t batch_bytes,
                                      int32_t cluster_method, bbfmm_isosurface_result **out) {
     return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch_bytes, cluster_method, BBFMM_FINISH_RAW,
-                                 nullptr, 0, nullptr, 0, false, out);
+                                 BBFMM_SELF_INTERSECTIONS_IGNORE, nullptr, 0, nullptr, 0, kIsoField, out);
 }
 
 int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r) { return r ? static_cast<int32_t>(r->meshes.size()) : -1; }

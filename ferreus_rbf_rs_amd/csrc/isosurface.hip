@@ -473,6 +473,29 @@ __global__ __launch_bounds__(kThreads) void split_clusters_kernel(Slab s, const 
     }
 }
 
+// The self-intersection rollback (isosurface.rs:959-974): the vertices of the triangles on a true self-intersection
+// that are clusters of several edges are flagged as pass B flags them, so that split_clusters_kernel rolls the sample
+// points that own them back.  Plain stores of one value.
+__global__ __launch_bounds__(kThreads) void flag_intersecting_kernel(int64_t nf, const uint8_t *__restrict__ tri_flag,
+                                                                      const int64_t *__restrict__ facets, const int64_t *__restrict__ vinfo,
+                                                                      uint8_t *__restrict__ vflag, int32_t *__restrict__ found) {
+    for (int64_t t = blockIdx.x * int64_t(kThreads) + threadIdx.x; t < nf; t += int64_t(gridDim.x) * kThreads) {
+        if (!tri_flag[t]) continue;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t v = facets[3 * t + a];
+            if (vinfo[v] & 1) {
+                vflag[v] = 2;
+                *found = 1;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void count_flagged_kernel(int64_t nv, const uint8_t *__restrict__ vflag, unsigned long long *__restrict__ n) {
+    for (int64_t v = blockIdx.x * int64_t(kThreads) + threadIdx.x; v < nv; v += int64_t(gridDim.x) * kThreads)
+        if (vflag[v]) atomicAdd(n, 1ull); // a count only
+}
+
 int grid_for(int64_t n) {
     return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 4096)));
 }
@@ -550,16 +573,17 @@ struct ClusterState {
     int64_t *vbase = nullptr, *foff = nullptr;
     void *scan_tmp = nullptr;
     size_t scan_bytes = 0;
-    unsigned long long *d_stats = nullptr; // 16 counters
+    unsigned long long *d_stats = nullptr; // 16 counters, then kIsectVertices and kIsectRolled of the rollback
     int32_t *d_found = nullptr;
 };
 
 // The clustered mesh of one isovalue of the resident field (DESIGN.md "Isosurfaces on the RMT lattice", clustering).
-int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, const ClipBox *clip, Pool &pool,
-                    hipStream_t st, Mesh *mesh, std::string *err) {
+// inside: the extents of the self-intersection rollback, nullptr without it.
+int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, const ClipBox *clip,
+                    const ClipBox *inside, Pool &pool, hipStream_t st, Mesh *mesh, std::string *err) {
     const int g = grid_for(s.nodes);
     const size_t nodes = static_cast<size_t>(s.nodes);
-    ISO_HIP(hipMemsetAsync(c.d_stats, 0, 16 * sizeof(unsigned long long), st));
+    ISO_HIP(hipMemsetAsync(c.d_stats, 0, 18 * sizeof(unsigned long long), st));
     near_topology_kernel<<<g, kThreads, 0, st>>>(s, nk, c.f, iso, c.part, c.ccnt, c.d_stats);
     ISO_HIP(hipGetLastError());
     double *verts = nullptr;
@@ -645,11 +669,40 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
         ISO_HIP(hipGetLastError());
         if ((rc = march()) != BBFMM_OK) return rc;
     }
-    unsigned long long h_stats[16];
+    // The self-intersection rollback (isosurface.rs:932-1007), one round: the triangles on true self-intersections among
+    // the facets inside the extents, their vertices that are clusters of several edges, the sample points that own those:
+    // pass B's update, and one more march.  Nothing flagged: the mesh stays as it is.
+    if (inside && nf > 0) {
+        uint8_t *tri_flag = nullptr;
+        ISO_HIP(pool.get(&tri_flag, static_cast<size_t>(nf)));
+        if ((rc = self_intersections_device(verts, nv, facets, nf, inside, st, tri_flag, mesh->isect_stats, err)) != BBFMM_OK) return rc;
+        if (mesh->isect_stats[kIsectTriangles] > 0) {
+            ISO_HIP(hipMemsetAsync(vflag, 0, static_cast<size_t>(std::max<int64_t>(nv, 1)), st));
+            ISO_HIP(hipMemsetAsync(c.d_found, 0, sizeof(int32_t), st));
+            flag_intersecting_kernel<<<grid_for(nf), kThreads, 0, st>>>(nf, tri_flag, facets, vinfo, vflag, c.d_found);
+            ISO_HIP(hipGetLastError());
+            count_flagged_kernel<<<grid_for(nv), kThreads, 0, st>>>(nv, vflag, c.d_stats + 16);
+            ISO_HIP(hipGetLastError());
+            int32_t found = 0;
+            ISO_HIP(hipMemcpyAsync(&found, c.d_found, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            ISO_HIP(hipStreamSynchronize(st));
+            pool.put(tri_flag);
+            if (found) {
+                split_clusters_kernel<<<g, kThreads, 0, st>>>(s, c.vbase, vflag, c.part, c.ccnt, c.d_stats + kStatSplitA, c.d_stats + 17);
+                ISO_HIP(hipGetLastError());
+                if ((rc = march()) != BBFMM_OK) return rc;
+            }
+        } else {
+            pool.put(tri_flag);
+        }
+    }
+    unsigned long long h_stats[18];
     ISO_HIP(hipMemcpyAsync(h_stats, c.d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
     if (clip) { // clipped and cleaned while still on the device
         ISO_HIP(hipStreamSynchronize(st));
         for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
+        mesh->isect_stats[kIsectVertices] = static_cast<int64_t>(h_stats[16]);
+        mesh->isect_stats[kIsectRolled] = static_cast<int64_t>(h_stats[17]);
         pool.put(vinfo);
         pool.put(vflag);
         rc = finish_device(verts, nv, facets, nf, *clip, st, mesh, err);
@@ -663,6 +716,8 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
     if (nf) ISO_HIP(hipMemcpyAsync(mesh->facets.data(), facets, mesh->facets.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     ISO_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
+    mesh->isect_stats[kIsectVertices] = static_cast<int64_t>(h_stats[16]);
+    mesh->isect_stats[kIsectRolled] = static_cast<int64_t>(h_stats[17]);
     pool.put(verts);
     pool.put(vinfo);
     pool.put(facets);
@@ -810,8 +865,13 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         *err = "isosurface: unknown finish " + std::to_string(req.finish);
         return BBFMM_BAD_ARGUMENT;
     }
+    if (req.self_intersections != kSelfIntersectionsIgnore && req.self_intersections != kSelfIntersectionsRollback) {
+        *err = "isosurface: unknown self-intersection handling " + std::to_string(req.self_intersections);
+        return BBFMM_BAD_ARGUMENT;
+    }
+    const bool rollback = cluster && req.self_intersections == kSelfIntersectionsRollback; // nothing to roll back without clusters
     ClipBox clip_box;
-    if (clipped && !make_clip_box(req.extents, &clip_box, err)) return BBFMM_BAD_ARGUMENT;
+    if ((clipped || rollback) && !make_clip_box(req.extents, &clip_box, err)) return BBFMM_BAD_ARGUMENT;
     // bytes per k-plane: field, flags, indices, targets and the evaluator's per-target buffers; per isovalue masks,
     // vertex ids, counts and offsets
     const int64_t per_plane = P * (8 + 4 + 4 + 128 + 40 * static_cast<int64_t>(n_iso));
@@ -874,7 +934,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         ISO_HIP(pool.get(&cs.fcnt, box));
         ISO_HIP(pool.get(&cs.vbase, box));
         ISO_HIP(pool.get(&cs.foff, box));
-        ISO_HIP(pool.get(&cs.d_stats, 16));
+        ISO_HIP(pool.get(&cs.d_stats, 18));
         ISO_HIP(pool.get(&cs.d_found, 1));
         ISO_HIP(rocprim::exclusive_scan(nullptr, cs.scan_bytes, cs.ccnt, cs.vbase, int64_t(0), box, rocprim::plus<int64_t>(), st));
         ISO_HIP(pool.get(reinterpret_cast<uint8_t **>(&cs.scan_tmp), cs.scan_bytes));
@@ -1011,7 +1071,8 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     if (cluster) {
         const Slab box = slab_for(0, nk);
         for (int q = 0; q < n_iso; ++q) {
-            const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], clipped ? &clip_box : nullptr, pool, st, &(*meshes)[q], err);
+            const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], clipped ? &clip_box : nullptr, rollback ? &clip_box : nullptr,
+                                           pool, st, &(*meshes)[q], err);
             if (rc != BBFMM_OK) return rc;
         }
         return BBFMM_OK;

@@ -1,11 +1,11 @@
 // Dense marching tetrahedra on the regularised-marching-tetrahedra (RMT) sampling lattice: the triangles of
 // ferreus_rmt's build_isosurface with ClusterMethod::None (raw, one vertex per crossed lattice edge) or
 // ClusterMethod::Average (the intersections near a sample point merged where the topology tests allow it, with the
-// predicted-edge and non-manifold rollbacks), taken from every sample point of the extraction domain in device passes
-// instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
+// predicted-edge and non-manifold rollbacks and, where asked for, the self-intersection rollback), taken from every sample
+// point of the extraction domain in device passes instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
 // finished mesh of BoundaryClosure::None; boundary closure is not run).  Contract: DESIGN.md "Isosurfaces on the RMT
-// lattice"; numpy restatements: tests/isosurface_restatement.py, tests/isosurface_cluster_restatement.py and
-// tests/isosurface_finish_restatement.py.
+// lattice"; numpy restatements: tests/isosurface_restatement.py, tests/isosurface_cluster_restatement.py,
+// tests/isosurface_finish_restatement.py and tests/isosurface_intersect_restatement.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -291,6 +291,8 @@ struct Mesh {
     std::vector<int64_t> facets;
     int64_t stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // kStat*, all 0 without clustering
     int64_t finish_stats[kFinStats] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // FinishStat, all 0 with kFinishRaw
+    int64_t isect_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // IntersectStat, all 0 without the detector
+    std::vector<int64_t> isect_ids;                                      // the detector on a caller's mesh: the triangles found
 };
 
 // Mesh::stats: [0, 6) sample points per TopologyCase; mesh edges with more than 2 faces before pass A and the clusters
@@ -300,6 +302,26 @@ constexpr int kStatOverA = 6, kStatSplitA = 7, kStatRolledB = 8, kStatOverB = 12
 
 enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1 };
 enum Finish : int { kFinishRaw = 0, kFinishClipped = 1 };
+enum SelfIntersections : int { kSelfIntersectionsIgnore = 0, kSelfIntersectionsRollback = 1 };
+
+// ---- self-intersections (ferreus_rmt/src/mesh_intersections.rs; DESIGN.md "Self-intersection rollback")
+// Mesh::isect_stats
+enum IntersectStat : int {
+    kIsectKept = 0,      // facets with all corners inside the extents (all facets without extents)
+    kIsectBoxPairs = 1,  // pairs a < b of those with overlapping bounding boxes
+    kIsectMoller = 2,    // of those, pairs that tri_tri_intersect accepts
+    kIsectTrue = 3,      // of those, true self-intersections
+    kIsectTriangles = 4, // triangles on a true pair
+    kIsectVertices = 5,  // their vertices that are clusters of several lattice edges
+    kIsectRolled = 6,    // sample points rolled back
+    kIsectStats = 8      // [7] reserved
+};
+// The broad phase puts every facet into the cell of its box's lowest corner on a grid of the largest box side and
+// probes the 27 cells around it.  A mesh where that is quadratic (one huge triangle among many small ones puts them all
+// into a few cells) is refused before any pair is tested: the estimate is the sum over the kept facets of the facets in
+// the 27 cells around them, the bound max(kIsectPairFloor, kIsectPairsPerFacet * kept facets).  A mesh of near-uniform
+// triangles has some hundreds per facet.
+constexpr int64_t kIsectPairFloor = int64_t(1) << 26, kIsectPairsPerFacet = 4096;
 
 // Finite extents with lo <= hi as a ClipBox with its eps; false with *err set otherwise.
 bool make_clip_box(const double *extents, ClipBox *out, std::string *err);
@@ -314,6 +336,13 @@ bool finish_fits(int64_t n_vertices, int64_t n_facets, std::string *err);
 int finish_device(const double *d_vertices, int64_t n_vertices, const int64_t *d_facets, int64_t n_facets, const ClipBox &box,
                   hipStream_t stream, Mesh *mesh, std::string *err);
 
+// The true self-intersections of a mesh on the device (get_intersecting_triangles, mesh_intersections.rs:163-208, with a
+// uniform grid in place of the R-tree): d_tri_flag[t] (n_facets bytes, zeroed here) becomes 1 for every facet on a true
+// pair, stats[kIsectKept .. kIsectTriangles] are filled.  box: only facets with every corner inside it (slack box->eps,
+// facet_fully_inside_aabb) take part; nullptr: all.  At most kFinishMaxFacets facets.  Returns a bbfmm_status.
+int self_intersections_device(const double *d_vertices, int64_t n_vertices, const int64_t *d_facets, int64_t n_facets,
+                              const ClipBox *box, hipStream_t stream, uint8_t *d_tri_flag, int64_t *stats, std::string *err);
+
 // Field values at m lattice nodes (SoA world coordinates on the device), written to d_vals[0..m) on the stream.
 // d_vals == nullptr: only check that every node can be evaluated (BBFMM_POINT_OUTSIDE_TREE otherwise).
 using FieldFn = std::function<int(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_vals)>;
@@ -327,7 +356,8 @@ struct Request {
     int64_t budget_bytes = 0;          // device memory for one batch of k-planes (<= 0: the default)
     int cluster = kClusterNone;        // kClusterAverage: the whole lattice field stays on the device (see extract)
     int finish = kFinishRaw;           // kFinishClipped: every mesh goes through finish_device before its download
-    const double *extents = nullptr;   // the 6 extents of the lattice, needed with kFinishClipped
+    const double *extents = nullptr;   // the 6 extents of the lattice, needed with kFinishClipped and the rollback
+    int self_intersections = kSelfIntersectionsIgnore; // kSelfIntersectionsRollback: with kClusterAverage, one round
 };
 
 // Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.  With kClusterAverage

@@ -273,7 +273,7 @@ class FmmTree:
 
     # -- isosurfaces (isosurface.py)
     def build_isosurfaces(self, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes=0,
-                          cluster="none", return_stats=False, finish="raw"):
+                          cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
         """RBFInterpolator::build_isosurfaces (ferreus_rbf/src/rbf.rs:980-) on the device, one field evaluation for all
         isovalues: a list of (vertices (n, 3) f64, facets (m, 3) int64), the marching-tetrahedra mesh of ferreus_rmt
         (isosurface.rs:489-) over every sample point of the extraction domain.  finish: "raw" (the default) is that mesh
@@ -281,11 +281,13 @@ class FmmTree:
         clip_mesh_to_aabb and clean_mesh on the device before the download (isosurface.rs:1009-1021), its finished mesh
         for BoundaryClosure::None; boundary closure is not implemented.  cluster: "none" (the default) is ClusterMethod::None, one vertex per crossed lattice edge; "average"
         is ClusterMethod::Average, the intersections near a sample point merged into their mean where the topology
-        tests allow it, with the predicted-edge and non-manifold rollbacks (isosurface.rs:715-930) but not the
-        self-intersection rollback; the lattice field then stays on the device (40 bytes per node of the lattice
+        tests allow it, with the predicted-edge and non-manifold rollbacks (isosurface.rs:715-930); its
+        self-intersection rollback (isosurface.rs:932-1007) runs with self_intersections="rollback" ("ignore", the
+        default, leaves it out; see isosurface.py); the lattice field then stays on the device (40 bytes per node of the lattice
         box), and a lattice that does not fit is refused before any work.  return_stats: (vertices, facets, stats) per
         isovalue, stats the clustering counts of isosurface.STATS and of the rollback passes, and with finish="clipped"
-        under "finish" the counts of isosurface.FINISH_STATS.  Needs set_local_coefficients (one column) first, like
+        under "finish" the counts of isosurface.FINISH_STATS, with self_intersections="rollback" under
+        "self_intersections" those of isosurface.INTERSECTION_STATS.  Needs set_local_coefficients (one column) first, like
         evaluate_leaves, and a tree whose extents hold the lattice (the reference pads its evaluator by 10 resolutions,
         rbf.rs:992-998; a node outside raises PointOutsideTree before any work).  drift: None, [a, b0, b1, b2] or
         (a, [b0, b1, b2]) added to the field as a + b . x (isosurface.affine_drift folds the reference's Constant /
@@ -294,14 +296,16 @@ class FmmTree:
         for one batch of k-planes (0: the default); the meshes do not depend on it."""
         from . import isosurface as I
         return I.build_isosurfaces(self, extents, resolution, isovalues, drift=drift, return_field=return_field,
-                                   batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish)
+                                   batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish,
+                                   self_intersections=self_intersections)
 
     def build_isosurface(self, extents, resolution, isovalue, *, drift=None, return_field=False, batch_bytes=0,
-                         cluster="none", return_stats=False, finish="raw"):
+                         cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
         """RBFInterpolator::build_isosurface (rbf.rs:954-) at one isovalue: (vertices, facets), then the stats when
         return_stats, then the lattice field when return_field; see build_isosurfaces."""
         out = self.build_isosurfaces(extents, resolution, [isovalue], drift=drift, return_field=return_field,
-                                     batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish)
+                                     batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish,
+                                     self_intersections=self_intersections)
         if return_field:
             meshes, field = out
             return (*meshes[0], field)

@@ -5,12 +5,12 @@ over every sample point of the extraction domain instead of the sample points a 
 "Isosurfaces on the RMT lattice").  `finish="raw"` (the default) is that mesh as it is, before `clip_mesh_to_aabb` and
 `clean_mesh`: it reaches two lattice cells past the extents.  `finish="clipped"` runs both on the device before the
 download (isosurface.rs:1009-1021): the reference's finished mesh for `BoundaryClosure::None`.  Boundary closure
-(`ClosePositive` / `CloseNegative`), the self-intersection rollback, `CurvatureWeighted` clustering and vertex
-gradients are not implemented.  `cluster="none"` (the
+(`ClosePositive` / `CloseNegative`), `CurvatureWeighted` clustering and vertex gradients are not implemented.  `cluster="none"` (the
 default) is its `ClusterMethod::None`, one vertex per crossed lattice edge; `cluster="average"` its
 `ClusterMethod::Average`: the intersections near a sample point are merged into their mean where the topology tests
 allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 faces are split again
-(isosurface.rs:798-930); the reference's later self-intersection rollback is not run.
+(isosurface.rs:798-930); the reference's later self-intersection rollback (isosurface.rs:932-1007) is run with
+`self_intersections="rollback"` and left out with `"ignore"` (the default).
 
 * lattice (lattice.rs:55-96): spacing [r/2, r*sqrt2/2, r/sqrt2], max_ijk = ceil((hi - lo) / spacing), max_ijk[0] += 1,
   world(ijk) = lo + ijk * spacing;
@@ -22,6 +22,13 @@ allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 f
 * facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order;
 * cluster="average": one vertex per cluster, ordered by sample point and lowest edge; triangles that two corners of
   share a vertex are dropped; `return_stats=True` adds the counts of `STATS` per mesh;
+* self_intersections="rollback", with cluster="average", after the two passes above and before the clip, one round: the
+  triangles on true self-intersections (mesh_intersections.rs:125-208; `triangle_pair` is the predicate) among the
+  facets with every corner inside the extents, found on the device through a uniform grid over their bounding boxes;
+  their vertices that are clusters of several lattice edges; the sample points that own those go back to one vertex
+  per edge and the mesh is marched again.  Nothing found: the mesh is bit for bit the one of "ignore".  With
+  cluster="none" nothing is done.  `return_stats=True` then holds the counts of `INTERSECTION_STATS` under
+  "self_intersections";
 * finish="clipped" (aabb_clipping.rs:55-105, mesh_cleanup.rs:32-96), with eps = 1e-10 * max(|hi - lo|, 1): every facet
   clipped against the six planes of the extents in turn and fanned; vertices within eps welded, the lowest-index
   vertex of a group its representative; collapsed, zero-area (|ab x ac|^2 <= eps^4), repeated and lone facets dropped;
@@ -116,14 +123,28 @@ FINISH_STATS = ("facets_in", "straddling", "outside", "vertices_emitted", "welde
                 "duplicate", "lone")
 
 
+SELF_INTERSECTIONS = {"ignore": 0, "rollback": 1}
+# return_stats with self_intersections="rollback", and mesh_self_intersections (bbfmm_isosurface_intersection_stats)
+INTERSECTION_STATS = ("inside_facets", "box_pairs", "moller_pairs", "true_pairs", "triangles", "cluster_vertices",
+                      "rolled_back")
+# triangle_pair: the test that decided
+PAIR_STAGES = ("degenerate", "shared_two", "moller", "shared_crossing", "geometric_shared", "near_coplanar", "true")
+
+
+def _self_intersections(mode):
+    if mode not in SELF_INTERSECTIONS:
+        raise ValueError(f"self_intersections must be one of {sorted(SELF_INTERSECTIONS)}, got {mode!r}")
+    return SELF_INTERSECTIONS[mode]
+
+
 def _finish(finish):
     if finish not in FINISH:
         raise ValueError(f"finish must be one of {sorted(FINISH)}, got {finish!r}")
     return FINISH[finish]
 
 
-def _options(method, finish, batch_bytes):
-    return L.IsosurfaceOptions(ctypes.sizeof(L.IsosurfaceOptions), method, finish, int(batch_bytes))
+def _options(method, finish, batch_bytes, self_intersections=0):
+    return L.IsosurfaceOptions(ctypes.sizeof(L.IsosurfaceOptions), method, finish, int(batch_bytes), self_intersections)
 
 
 def _cluster(cluster):
@@ -174,7 +195,13 @@ def _finish_stats(lib, res, i):
     return {name: int(s[q]) for q, name in enumerate(FINISH_STATS)}
 
 
-def _meshes(lib, res, stats=False, finish=0):
+def _intersection_stats(lib, res, i):
+    s = np.zeros(8, dtype=np.int64)
+    lib.bbfmm_isosurface_intersection_stats(res, i, s.ctypes.data)
+    return {name: int(s[q]) for q, name in enumerate(INTERSECTION_STATS)}
+
+
+def _meshes(lib, res, stats=False, finish=0, self_intersections=0):
     out = []
     for i in range(lib.bbfmm_isosurface_count(res)):
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
@@ -186,6 +213,8 @@ def _meshes(lib, res, stats=False, finish=0):
             st = _stats(lib, res, i)
             if finish:
                 st["finish"] = _finish_stats(lib, res, i)
+            if self_intersections:
+                st["self_intersections"] = _intersection_stats(lib, res, i)
             out.append((v, f, st))
         else:
             out.append((v, f))
@@ -204,11 +233,11 @@ def _raise(rc, msg, leaf=True):
 
 
 def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0,
-                      cluster="none", return_stats=False, finish="raw"):
+                      cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
     """Meshes of the tree's field (set_local_coefficients first, one column) at each isovalue, one field evaluation
     for all of them; see FmmTree.build_isosurfaces."""
     lib = L.load()
-    method, fin = _cluster(cluster), _finish(finish)
+    method, fin, isect = _cluster(cluster), _finish(finish), _self_intersections(self_intersections)
     ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
     field_t = None
     if return_field:
@@ -218,8 +247,8 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
         field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
         torch.cuda.synchronize(field_t.device)
     res = ctypes.c_void_p()
-    if fin:
-        opts = _options(method, fin, batch_bytes)
+    if fin or isect:
+        opts = _options(method, fin, batch_bytes, isect)
         rc = lib.bbfmm_build_isosurfaces_opts(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
                                               d.ctypes.data if d is not None else None,
                                               field_t.data_ptr() if field_t is not None else None, ctypes.addressof(opts),
@@ -232,7 +261,7 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_last_error(tree._h).decode())
-        meshes = _meshes(lib, res, return_stats, fin)
+        meshes = _meshes(lib, res, return_stats, fin, isect)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
@@ -242,13 +271,14 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
 
 
 def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None,
-                            cluster="none", return_stats=False, finish="raw"):
+                            cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
-    current device (or the tree's).  cluster: "none" or "average", finish: "raw" or "clipped" (see the module);
-    return_stats: (vertices, facets, stats) per mesh, stats the clustering counts (all 0 with "none") and with
-    finish="clipped" under "finish" the counts of FINISH_STATS."""
+    current device (or the tree's).  cluster: "none" or "average", finish: "raw" or "clipped", self_intersections:
+    "ignore" or "rollback" (see the module); return_stats: (vertices, facets, stats) per mesh, stats the clustering
+    counts (all 0 with "none"), with finish="clipped" under "finish" the counts of FINISH_STATS and with
+    self_intersections="rollback" under "self_intersections" those of INTERSECTION_STATS."""
     lib = L.load()
-    method, fin = _cluster(cluster), _finish(finish)
+    method, fin, isect = _cluster(cluster), _finish(finish), _self_intersections(self_intersections)
     ext, iso = _ext(extents), _isovalues(isovalues)
     vals = np.ascontiguousarray(np.asarray(lattice_values, dtype=np.float64))
     info = lattice_info(ext, resolution, tree)
@@ -256,8 +286,8 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
         raise ValueError(f"lattice_values must have shape {info['shape']}, got {vals.shape}")
     res = ctypes.c_void_p()
     h = tree._h if tree is not None else None
-    if fin:
-        opts = _options(method, fin, batch_bytes)
+    if fin or isect:
+        opts = _options(method, fin, batch_bytes, isect)
         rc = lib.bbfmm_isosurfaces_from_values_opts(h, vals.ctypes.data, ext.ctypes.data, float(resolution),
                                                     iso.ctypes.data, len(iso), ctypes.addressof(opts), ctypes.byref(res))
     else:
@@ -266,18 +296,19 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
-        return _meshes(lib, res, return_stats, fin)
+        return _meshes(lib, res, return_stats, fin, isect)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
 
 
 def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None,
-                           cluster="none", return_stats=False, finish="raw"):
+                           cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
     """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue, and its stats when
     return_stats."""
     return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree,
-                                   cluster=cluster, return_stats=return_stats, finish=finish)[0]
+                                   cluster=cluster, return_stats=return_stats, finish=finish,
+                                   self_intersections=self_intersections)[0]
 
 
 def clip_mesh(vertices, facets, extents, return_stats=False, *, tree=None):
@@ -315,3 +346,53 @@ def clip_triangle(triangle, extents):
     if rc != L.OK:
         raise ValueError("extents must be finite with min <= max")
     return pts[:n.value].copy(), corner[:n.value].copy()
+
+
+def mesh_self_intersections(vertices, facets, extents=None, return_stats=False, *, tree=None):
+    """The ids (ascending, int64) of the triangles of a caller's own mesh on true self-intersections, found on the
+    current device (or the tree's): the reference's get_intersecting_triangles (mesh_intersections.rs:163-208).
+    extents: only the facets with every corner inside them take part (the filter of the rollback), None: all.
+    return_stats: also the counts "inside_facets", "box_pairs", "moller_pairs", "true_pairs" and "triangles" of
+    INTERSECTION_STATS.  A mesh whose largest facet makes the grid search quadratic is refused (FmmError)."""
+    lib = L.load()
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(facets, dtype=np.int64).reshape(-1, 3))
+    ext = _ext(extents) if extents is not None else None
+    res = ctypes.c_void_p()
+    h = tree._h if tree is not None else None
+    rc = lib.bbfmm_isosurface_self_intersections(h, v.ctypes.data, len(v), f.ctypes.data, len(f),
+                                                 ext.ctypes.data if ext is not None else None, ctypes.byref(res))
+    try:
+        if rc != L.OK:
+            _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface self-intersection search failed")
+        n = ctypes.c_int64()
+        lib.bbfmm_isosurface_intersection_ids(res, 0, ctypes.byref(n), None)
+        ids = np.empty(n.value, dtype=np.int64)
+        lib.bbfmm_isosurface_intersection_ids(res, 0, None, ids.ctypes.data)
+        if not return_stats:
+            return ids
+        st = _intersection_stats(lib, res, 0)
+        return ids, {k: st[k] for k in INTERSECTION_STATS[:5]}
+    finally:
+        if res:
+            lib.bbfmm_isosurface_destroy(res)
+
+
+def triangle_pair(tri_a, ids_a, tri_b, ids_b):
+    """(result, stage) of the pair predicate the device runs (host only; is_true_self_intersection,
+    mesh_intersections.rs:125-159): result True for a true self-intersection, stage the index into PAIR_STAGES of the
+    test that decided.  tri_a, tri_b: 3 points each, ids_a, ids_b: their vertex ids; a is the facet with the lower index.
+    The Moeller test inside compares unnormalised normals with 1e-6, so the answer depends on the scale of the
+    triangles, as the reference's does."""
+    lib = L.load()
+    ta = np.ascontiguousarray(np.asarray(tri_a, dtype=np.float64).reshape(-1))
+    tb = np.ascontiguousarray(np.asarray(tri_b, dtype=np.float64).reshape(-1))
+    ia = np.ascontiguousarray(np.asarray(ids_a, dtype=np.int64).reshape(-1))
+    ib = np.ascontiguousarray(np.asarray(ids_b, dtype=np.int64).reshape(-1))
+    if ta.shape != (9,) or tb.shape != (9,) or ia.shape != (3,) or ib.shape != (3,):
+        raise ValueError("a triangle holds 3 points and 3 vertex ids")
+    result, stage = ctypes.c_int32(), ctypes.c_int32()
+    rc = lib.bbfmm_isosurface_triangle_pair(ta.ctypes.data, ia.ctypes.data, tb.ctypes.data, ib.ctypes.data,
+                                            ctypes.byref(result), ctypes.byref(stage))
+    assert rc == L.OK
+    return bool(result.value), stage.value

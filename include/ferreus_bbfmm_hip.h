@@ -225,8 +225,9 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
 /* ---- Isosurfaces: dense marching tetrahedra on the RMT sampling lattice (ferreus_rmt build_isosurface with
  * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE its ClusterMethod::Average; the raw mesh
  * before clipping and cleaning, or with the *_opts entries and BBFMM_FINISH_CLIPPED the mesh clipped to the extents and
- * cleaned on the device, which is the reference's finished mesh for BoundaryClosure::None.  Boundary closure
- * (ClosePositive / CloseNegative) and the self-intersection rollback are not implemented; contract in DESIGN.md
+ * cleaned on the device, which is the reference's finished mesh for BoundaryClosure::None; its self-intersection
+ * rollback is run with BBFMM_SELF_INTERSECTIONS_ROLLBACK in the options.  Boundary closure (ClosePositive /
+ * CloseNegative) is not implemented; contract in DESIGN.md
  * "Isosurfaces on the RMT lattice").  extents = [min x, min y, min z, max x, max y, max z]; resolution > 0.  Lattice fields are arrays of
  * nk x nj x ni doubles (i fastest) over the bounding box of the extraction nodes E; entries off E are ignored (NaN in
  * returned fields).  Vertices are n x 3 doubles, facets m x 3 int64 vertex ids, both row-major. */
@@ -255,7 +256,8 @@ int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const d
 /* Vertex clustering.  BBFMM_CLUSTER_NONE: one vertex per crossed lattice edge (the entries above).
  * BBFMM_CLUSTER_AVERAGE: the intersections near a sample point are merged into their mean where the topology tests of
  * ferreus_rmt allow it (topology.rs:232-314), then clusters that give a mesh edge more than 2 faces are split again
- * (isosurface.rs:798-930); the self-intersection rollback of the reference is not run.  The whole lattice field then
+ * (isosurface.rs:798-930); the self-intersection rollback of the reference (isosurface.rs:932-1007) is run by the *_opts
+ * entries with self_intersections = BBFMM_SELF_INTERSECTIONS_ROLLBACK and not otherwise.  The whole lattice field then
  * stays on the device (40 bytes per node of the nk x nj x ni box); a lattice that does not fit is refused before any
  * work with BBFMM_BAD_ARGUMENT.  The meshes do not depend on batch_bytes. */
 #define BBFMM_CLUSTER_NONE 0
@@ -280,13 +282,26 @@ int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t 
  * before any work (ids are packed in 32 bits). */
 #define BBFMM_FINISH_RAW 0
 #define BBFMM_FINISH_CLIPPED 1
+/* Self-intersections.  BBFMM_SELF_INTERSECTIONS_IGNORE: the clustered mesh as the two passes above leave it (averaging can
+ * pull two sheets of a complex surface through each other).  BBFMM_SELF_INTERSECTIONS_ROLLBACK, with
+ * BBFMM_CLUSTER_AVERAGE (nothing is done with BBFMM_CLUSTER_NONE: the mesh and the counts are those without it): after
+ * pass B and before the clip, one round of the reference's third guard.  The triangles on true self-intersections
+ * (is_true_self_intersection, mesh_intersections.rs:125-159) among the facets with every corner inside the extents are
+ * found on the device, by a uniform grid over the facets' bounding boxes instead of an R-tree; their vertices that are
+ * clusters of several lattice edges send the sample points that own them back to one vertex per edge, and the mesh is
+ * marched again.  Nothing found: the mesh is bit for bit the one without the option.  A mesh of more than 2^26 facets is
+ * refused. */
+#define BBFMM_SELF_INTERSECTIONS_IGNORE 0
+#define BBFMM_SELF_INTERSECTIONS_ROLLBACK 1
 /* Options of the *_opts entries.  size: sizeof(bbfmm_isosurface_options) as the caller was compiled; fields beyond it
- * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0), as does every field with options == NULL. */
+ * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0, SELF_INTERSECTIONS_IGNORE), as does every field with
+ * options == NULL. */
 typedef struct bbfmm_isosurface_options {
     int64_t size;
     int32_t cluster_method; /* BBFMM_CLUSTER_* */
     int32_t finish;         /* BBFMM_FINISH_* */
     int64_t batch_bytes;    /* device memory for one batch of k-planes (<= 0: a default) */
+    int32_t self_intersections; /* BBFMM_SELF_INTERSECTIONS_* */
 } bbfmm_isosurface_options;
 int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                  int32_t n_isovalues, const double *drift, double *d_field_out,
@@ -304,6 +319,30 @@ int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_
  * another, [5] vertices further than eps from their representative (weld_loose; 0 where the weld is the reference's
  * greedy one); facets dropped as [6] collapsed, [7] zero-area, [8] repeated, [9] lone. */
 int bbfmm_isosurface_finish_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* The counts of the self-intersection detector for mesh i, stats_out[8] (all 0 where it did not run): [0] facets with
+ * every corner inside the extents, [1] pairs of those with overlapping bounding boxes, [2] of those, pairs the Moeller
+ * test accepts, [3] of those, true self-intersections, [4] triangles on a true pair, [5] their vertices that are clusters
+ * of several lattice edges, [6] sample points rolled back, [7] 0 (reserved). */
+int bbfmm_isosurface_intersection_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* The detector on a caller's own mesh (host arrays as for bbfmm_isosurface_finish_mesh, finite vertices) on the current
+ * device, or the handle's when h is not NULL: *out holds one entry without vertices or facets, whose
+ * bbfmm_isosurface_intersection_ids are the triangles on true self-intersections in ascending order (the reference's
+ * get_intersecting_triangles) and whose bbfmm_isosurface_intersection_stats are [0..4] above.  extents: only facets with
+ * every corner inside them (slack 1e-10 * max(|hi - lo|, 1)) take part; NULL: all facets.  The search probes a grid of
+ * the largest facet's bounding box: a mesh on which that is quadratic (a huge triangle among many small ones; more than
+ * max(2^26, 4096 * facets) candidates) is refused with BBFMM_BAD_ARGUMENT before any pair is tested. */
+int bbfmm_isosurface_self_intersections(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                        int64_t n_facets, const double *extents, bbfmm_isosurface_result **out);
+/* n_ids_out (may be NULL): the number of ids of entry i; ids_out (may be NULL): receives them. */
+int bbfmm_isosurface_intersection_ids(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_ids_out, int64_t *ids_out);
+/* Host only: the pair predicate the device runs (is_true_self_intersection with the reference's constants: tolerance
+ * 1e-8, Moeller epsilon 1e-6 on unnormalised normals, so it depends on the scale of the triangles).  tri_a, tri_b: 9
+ * doubles each, ids_a, ids_b: their 3 vertex ids; a is the facet with the lower index (the predicate is not symmetric in
+ * its last bits).  result_out: 1 for a true self-intersection.  stage_out (may be NULL), the test that decided: 0 a
+ * degenerate triangle, 1 two or more shared ids, 2 the Moeller test, 3 one shared id: the crossing test, 4 coincident
+ * vertices under distinct ids (two or more: no; one: the crossing test), 5 nearly coplanar, 6 a true self-intersection. */
+int bbfmm_isosurface_triangle_pair(const double *tri_a, const int64_t *ids_a, const double *tri_b, const int64_t *ids_b,
+                                   int32_t *result_out, int32_t *stage_out);
 /* Host only: the clip of one triangle (9 doubles) by the function the device runs.  points_out: up to 12 x 3 doubles,
  * corner_out (may be NULL): per point the corner of the triangle it is a kept copy of, -1 for a point made on a plane;
  * n_points_out: 0 when the triangle is dropped. */

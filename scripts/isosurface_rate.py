@@ -6,9 +6,13 @@ isovalue; measured as the extraction of an isovalue that no node crosses), the w
 same work for both), and the clustering counts are recorded.  With --finish raw,clipped every method is also timed
 with the mesh clipped to the extents and cleaned on the device: finish_ms is what "clipped" adds to the whole call of
 "raw" in the same run, clip_mesh_ms the same stage alone on the raw mesh (clip_mesh: with the upload of the mesh), and
-the finish counts are recorded.
+the finish counts are recorded.  With --self-intersections ignore,rollback the clustered raw call of every case is
+also timed with the self-intersection rollback on: rollback_ms is what it adds to the clustered call without it in the
+same run (the yardstick), and its counts are recorded; a third case, the noisy sphere (0.15 * standard_normal(seed 1) at
+resolution 0.1, a caller's field), is one where the rollback has sample points to roll back.
 
-    python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--finish raw,clipped] [--out FILE]
+    python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--finish raw,clipped]
+                                      [--self-intersections ignore,rollback] [--out FILE]
 """
 import argparse
 import json
@@ -56,6 +60,20 @@ def measure(te, ext, res, iso, repeats, label, cluster="none", finish="raw", raw
     return (rec, v, f) if finish == "raw" else rec
 
 
+def measure_rollback(call, repeats, label, res, yardstick_ms=None):
+    """The clustered raw call with the rollback on, beside the same call without it (timed here unless given)."""
+    kw = {"cluster": "average", "return_stats": True}
+    if yardstick_ms is None:
+        yardstick_ms, _ = timed(lambda: call(**kw), repeats)
+    t_roll, (v, f, stats) = timed(lambda: call(self_intersections="rollback", **kw), repeats)
+    rec = {"case": label, "cluster": "average", "finish": "raw", "self_intersections": "rollback", "resolution": res,
+           "vertices": int(len(v)), "facets": int(len(f)), "call_ms": t_roll, "call_ms_without": yardstick_ms,
+           "rollback_ms": t_roll - yardstick_ms, "intersection_stats": stats["self_intersections"],
+           "stats": {k: x for k, x in stats.items() if k != "self_intersections"}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def measure_all(te, ext, res, iso, a, label):
     recs = []
     for method in a.clusters.split(","):
@@ -64,9 +82,27 @@ def measure_all(te, ext, res, iso, a, label):
             if finish == "raw":
                 raw = measure(te, ext, res, iso, a.repeats, label, method)
                 recs.append(raw[0])
+                if method == "average" and "rollback" in a.self_intersections.split(","):
+                    recs.append(measure_rollback(lambda **kw: te.build_isosurface(ext, res, iso, **kw), a.repeats, label, res,
+                                                 raw[0]["call_ms"]))
             else:
                 recs.append(measure(te, ext, res, iso, a.repeats, label, method, finish, raw))
     return recs
+
+
+def noisy_sphere(a):
+    """A caller's field on [0, 6]^3 at resolution 0.1: |x - (3, 3, 3)| - 2 + 0.15 * standard_normal(seed 1)."""
+    import ferreus_rbf_rs_amd as F
+    from ferreus_rbf_rs_amd import isosurface as I
+    ext, res = [0.0, 0.0, 0.0, 6.0, 6.0, 6.0], 0.1
+    info = I.lattice_info(ext, res)
+    nk, nj, ni = info["shape"]
+    k, j, i = np.meshgrid(np.arange(nk), np.arange(nj), np.arange(ni), indexing="ij")
+    sp = np.array([res / 2.0, res * np.sqrt(2.0) / 2.0, res / np.sqrt(2.0)])
+    w = np.stack([(i + info["lo"][0]) * sp[0], (j + info["lo"][1]) * sp[1], (k + info["lo"][2]) * sp[2]], -1)
+    field = np.linalg.norm(w - 3.0, axis=-1) - 2.0 + 0.15 * np.random.default_rng(1).standard_normal((nk, nj, ni))
+    return [measure_rollback(lambda **kw: F.isosurface_from_values(field, ext, res, 0.0, **kw), a.repeats,
+                             "noisy_sphere_r0.1", res)]
 
 
 def main():
@@ -74,6 +110,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--clusters", default="none", help="comma-separated cluster methods, each timed on every case")
     ap.add_argument("--finish", default="raw", help="comma-separated finishes (raw first), each timed with every method")
+    ap.add_argument("--self-intersections", default="ignore",
+                    help="ignore,rollback: also time the clustered call with the self-intersection rollback")
     ap.add_argument("--out", default=None, help="JSON file for the list of results")
     a = ap.parse_args()
     import ferreus_rbf_rs_amd as F
@@ -111,6 +149,9 @@ def main():
     t1.set_local_coefficients(w)
     fmid = float(np.median(t1.evaluate_leaves(None, p[:2000])))
     recs += measure_all(t1, ext, res, fmid, a, "cloud_1M_linear")
+    del t1
+    if "rollback" in a.self_intersections.split(",") and "average" in a.clusters.split(","):
+        recs += noisy_sphere(a)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
