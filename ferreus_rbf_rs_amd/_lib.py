@@ -169,6 +169,13 @@ SIGNATURES = {
     "bbfmm_schwarz_level_size": (c_i64, [c_p, c_i32]),
     "bbfmm_schwarz_level_points": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_schwarz_debug_level_solve": (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i64, c_i32]),
+    "bbfmm_ddm_debug_level_create": (ctypes.c_int, [c_p, c_i64, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p]),
+    "bbfmm_ddm_debug_level_destroy": (None, [c_p]),
+    "bbfmm_ddm_debug_level_info": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_ddm_debug_level_layout": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p]),
+    "bbfmm_ddm_debug_level_assembled": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_ddm_debug_level_factor": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_ddm_debug_level_solve": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32]),
 }
 
 

@@ -510,6 +510,130 @@ int bbfmm_schwarz_debug_level_solve(bbfmm_schwarz *h, int32_t level, const doubl
     SCHWARZ_END_GUARD
 }
 
+// ---- test hook: ddm_level_build / ddm_level_solve on domains the caller prescribes (tests/test_gpu_ddm_local.py).
+// Nothing here computes: the level is built and solved by the product's own functions, the getters copy its buffers out.
+} // extern "C"
+
+struct bbfmm_ddm_debug_level {
+    DdmLevelSolver lv;
+    KernelSpec ks{};
+    double nugget = 0.0;
+    int64_t n = 0;
+    int d = 0;
+    ~bbfmm_ddm_debug_level() { ddm_level_free(&lv); }
+};
+
+extern "C" {
+
+int bbfmm_ddm_debug_level_create(const double *points, int64_t n, int32_t d, int64_t ld, int64_t n_dom,
+                                 const int64_t *dom_ptr, const int64_t *dom_idx, const uint8_t *dom_internal,
+                                 const bbfmm_interpolant *settings, int32_t basis_size, int32_t solve_for_poly,
+                                 bbfmm_ddm_debug_level **out) {
+    if (!out) return BBFMM_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!points || !dom_ptr || !dom_idx || !dom_internal || !settings || n < 1 || d < 1 || d > 3 || ld < n || n_dom < 1)
+        return BBFMM_BAD_ARGUMENT;
+    if (settings->kernel_type < 0 || settings->kernel_type > 6 || settings->polynomial_degree < -1 ||
+        settings->polynomial_degree > 2 || basis_size != monomial_basis_size(d, settings->polynomial_degree))
+        return BBFMM_BAD_ARGUMENT;
+    if (dom_ptr[0] != 0) return BBFMM_BAD_ARGUMENT;
+    for (int64_t i = 0; i < n_dom; ++i)
+        if (dom_ptr[i + 1] <= dom_ptr[i]) return BBFMM_BAD_ARGUMENT;
+    for (int64_t e = 0; e < dom_ptr[n_dom]; ++e)
+        if (dom_idx[e] < 0 || dom_idx[e] >= n) return BBFMM_BAD_ARGUMENT;
+    SCHWARZ_GUARD
+    std::unique_ptr<bbfmm_ddm_debug_level> h(new bbfmm_ddm_debug_level());
+    h->ks = make_kernel_spec(settings->kernel_type, settings->base_range, settings->total_sill);
+    h->nugget = settings->nugget;
+    h->n = n;
+    h->d = d;
+    DdmLevel level;
+    level.leaves.resize(static_cast<size_t>(n_dom));
+    for (int64_t i = 0; i < n_dom; ++i) {
+        level.leaves[i].idx.assign(dom_idx + dom_ptr[i], dom_idx + dom_ptr[i + 1]);
+        level.leaves[i].internal.assign(dom_internal + dom_ptr[i], dom_internal + dom_ptr[i + 1]);
+    }
+    const int rc = ddm_level_build(points, ld, d, &level, h->ks, h->nugget, settings->polynomial_degree, basis_size,
+                                   solve_for_poly != 0, nullptr, &h->lv);
+    if (rc) return rc;
+    *out = h.release();
+    return BBFMM_OK;
+    SCHWARZ_END_GUARD
+}
+
+void bbfmm_ddm_debug_level_destroy(bbfmm_ddm_debug_level *h) { delete h; }
+
+int bbfmm_ddm_debug_level_info(const bbfmm_ddm_debug_level *h, int64_t *info) {
+    if (!h || !info) return BBFMM_BAD_ARGUMENT;
+    const DdmLevelSolver &lv = h->lv;
+    info[0] = lv.n_dom;
+    info[1] = lv.n_entries;
+    info[2] = lv.q_off.back();
+    info[3] = lv.fac_off.back();
+    info[4] = ddm_level_is_big(lv) ? 1 : 0;
+    info[5] = lv.d_lu ? 1 : 0;
+    info[6] = lv.n_fallback;
+    info[7] = lv.max_m;
+    return BBFMM_OK;
+}
+
+int bbfmm_ddm_debug_level_layout(const bbfmm_ddm_debug_level *h, int32_t *k, int64_t *indices, uint8_t *internal, double *q,
+                                 uint8_t *mode) {
+    if (!h || !k || !indices || !internal || !q || !mode) return BBFMM_BAD_ARGUMENT;
+    const DdmLevelSolver &lv = h->lv;
+    std::copy(lv.k.begin(), lv.k.end(), k);
+    std::copy(lv.gidx_h.begin(), lv.gidx_h.end(), indices);
+    HIPOK(hipMemcpy(internal, lv.d_internal, static_cast<size_t>(lv.n_entries), hipMemcpyDeviceToHost));
+    if (lv.q_off.back() > 0)
+        HIPOK(hipMemcpy(q, lv.d_q, static_cast<size_t>(lv.q_off.back()) * sizeof(double), hipMemcpyDeviceToHost));
+    std::fill(mode, mode + lv.n_dom, uint8_t(0));
+    if (lv.d_mode) HIPOK(hipMemcpy(mode, lv.d_mode, static_cast<size_t>(lv.n_dom), hipMemcpyDeviceToHost));
+    return BBFMM_OK;
+}
+
+int bbfmm_ddm_debug_level_factor(const bbfmm_ddm_debug_level *h, double *out) {
+    if (!h || !out) return BBFMM_BAD_ARGUMENT;
+    HIPOK(hipMemcpy(out, h->lv.d_fac, static_cast<size_t>(h->lv.fac_off.back()) * sizeof(double), hipMemcpyDeviceToHost));
+    return BBFMM_OK;
+}
+
+int bbfmm_ddm_debug_level_assembled(const bbfmm_ddm_debug_level *h, double *out) {
+    if (!h || !out) return BBFMM_BAD_ARGUMENT;
+    SCHWARZ_GUARD
+    // launch_ddm_prep / launch_ddm_assemble as ddm_level_build issues them, on a copy of the level whose packed matrices
+    // are a scratch buffer: the factors stay as they are (T and G are written again with the values they hold)
+    DdmLevelSolver tmp = h->lv;
+    const size_t bytes = static_cast<size_t>(std::max<int64_t>(tmp.fac_off.back(), 1)) * sizeof(double);
+    tmp.d_fac = nullptr;
+    HIPOK(hipMalloc(reinterpret_cast<void **>(&tmp.d_fac), bytes));
+    launch_ddm_prep(h->ks, h->nugget, h->d, tmp, nullptr);
+    launch_ddm_assemble(h->ks, h->nugget, h->d, tmp, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, tmp.d_fac, static_cast<size_t>(tmp.fac_off.back()) * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(tmp.d_fac);
+    return e == hipSuccess ? BBFMM_OK : BBFMM_DEVICE_ERROR;
+    SCHWARZ_END_GUARD
+}
+
+int bbfmm_ddm_debug_level_solve(bbfmm_ddm_debug_level *h, const double *values, double *out, int64_t n, int32_t all_points) {
+    if (!h || !values || !out || n != h->n) return BBFMM_BAD_ARGUMENT;
+    const size_t bytes = static_cast<size_t>(n) * sizeof(double);
+    double *d_v = nullptr, *d_o = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d_v), bytes) != hipSuccess) return BBFMM_DEVICE_ERROR;
+    if (hipMalloc(reinterpret_cast<void **>(&d_o), bytes) != hipSuccess) {
+        (void)hipFree(d_v);
+        return BBFMM_DEVICE_ERROR;
+    }
+    int rc = BBFMM_OK;
+    if (hipMemcpy(d_v, values, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_o, out, bytes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = BBFMM_DEVICE_ERROR;
+    if (rc == BBFMM_OK) rc = ddm_level_solve(h->lv, d_v, d_o, all_points != 0, nullptr);
+    if (rc == BBFMM_OK && hipMemcpy(out, d_o, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = BBFMM_DEVICE_ERROR;
+    (void)hipFree(d_v);
+    (void)hipFree(d_o);
+    return rc;
+}
+
 // schwarz_preconditioner (schwarz.rs:32-82) as a bbfmm_apply_fn: user = bbfmm_schwarz*, n = N + basis
 int bbfmm_schwarz_apply(void *user, const double *rg, double *sl, int64_t n) {
     bbfmm_schwarz *h = static_cast<bbfmm_schwarz *>(user);

@@ -103,6 +103,90 @@ class InterpolantSettings:
         self.nugget, self.base_range, self.total_sill = float(nugget), float(base_range), float(total_sill)
 
 
+class DebugLevel:
+    """Test hook (bbfmm_ddm_debug_level_*): the device's local solvers of one level on prescribed domains.
+    `domains`: a list of (point indices, internal mask) over `points`.  After the build:
+      k[i], m[i]        special points / reduced size of domain i
+      indices[i]        its global indices in the reordered point order (special points first)
+      internal[i]       its internal mask in that order
+      q[i]              Q, k x m
+      mode[i]           1: the Cholesky factorisation failed (host fallback, the factor slot holds the packed inverse)
+      is_big, lu_taken  one large domain on the multi-launch path / factorised by the pivoted LU
+    assembled() / factor(): per domain the packed lower triangle (column by column) before / after the factorisation."""
+
+    def __init__(self, points, domains, settings: InterpolantSettings, solve_for_poly: bool = False):
+        pts = np.asfortranarray(np.atleast_2d(np.asarray(points, dtype=np.float64)))
+        n, d = pts.shape
+        lib = L.load()
+        ptr = np.zeros(len(domains) + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum([len(ix) for ix, _ in domains])
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(ix, dtype=np.int64) for ix, _ in domains]))
+        internal = np.ascontiguousarray(np.concatenate([np.asarray(mk, dtype=bool) for _, mk in domains]).astype(np.uint8))
+        if idx.size != internal.size:
+            raise ValueError("every domain needs one internal flag per point")
+        st = L.Interpolant(settings.kernel_type, settings.polynomial_degree, settings.nugget, settings.base_range,
+                           settings.total_sill, 0)
+        h = ctypes.c_void_p()
+        self._h, self._lib = None, lib
+        rc = lib.bbfmm_ddm_debug_level_create(pts.ctypes.data, n, d, n, len(domains), ptr.ctypes.data, idx.ctypes.data,
+                                              internal.ctypes.data, ctypes.byref(st), settings.basis_size,
+                                              int(solve_for_poly), ctypes.byref(h))
+        if rc != L.OK:
+            raise ValueError(f"bbfmm_ddm_debug_level_create failed with status {rc}")
+        self._h, self.n = h, n
+        info = np.zeros(8, dtype=np.int64)
+        self._check(lib.bbfmm_ddm_debug_level_info(h, info.ctypes.data), "info")
+        nd, ne, nq, self._nfac = (int(v) for v in info[:4])
+        self.is_big, self.lu_taken, self.n_fallback, self.max_m = bool(info[4]), bool(info[5]), int(info[6]), int(info[7])
+        k = np.zeros(nd, dtype=np.int32)
+        gidx = np.zeros(ne, dtype=np.int64)
+        mask = np.zeros(ne, dtype=np.uint8)
+        q = np.zeros(max(nq, 1))
+        mode = np.zeros(nd, dtype=np.uint8)
+        self._check(lib.bbfmm_ddm_debug_level_layout(h, k.ctypes.data, gidx.ctypes.data, mask.ctypes.data, q.ctypes.data,
+                                                     mode.ctypes.data), "layout")
+        self.k = [int(v) for v in k]
+        self.m = [int(ptr[i + 1] - ptr[i]) - self.k[i] for i in range(nd)]
+        self.mode = [int(v) for v in mode]
+        self.indices = [gidx[ptr[i]:ptr[i + 1]].copy() for i in range(nd)]
+        self.internal = [mask[ptr[i]:ptr[i + 1]].astype(bool) for i in range(nd)]
+        qo = np.concatenate([[0], np.cumsum([a * b for a, b in zip(self.k, self.m)])])
+        self.q = [q[qo[i]:qo[i + 1]].reshape(self.k[i], self.m[i]).copy() for i in range(nd)]
+        self._fac_off = np.concatenate([[0], np.cumsum([b * (b + 1) // 2 for b in self.m])])
+
+    def _check(self, rc, what):
+        if rc != L.OK:
+            raise RuntimeError(f"bbfmm_ddm_debug_level_{what} failed with status {rc}")
+
+    def _packed(self, fn, what):
+        buf = np.zeros(max(self._nfac, 1))
+        self._check(fn(self._h, buf.ctypes.data), what)
+        return [buf[self._fac_off[i]:self._fac_off[i + 1]].copy() for i in range(len(self.m))]
+
+    def assembled(self):
+        return self._packed(self._lib.bbfmm_ddm_debug_level_assembled, "assembled")
+
+    def factor(self):
+        return self._packed(self._lib.bbfmm_ddm_debug_level_factor, "factor")
+
+    def solve(self, values, out, all_points: bool = False) -> np.ndarray:
+        """ddm_level_solve: returns `out` (n doubles) with the rows the level writes replaced"""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        o = np.array(out, dtype=np.float64).reshape(-1)
+        if v.size != self.n or o.size != self.n:
+            raise ValueError("values and out hold one double per point")
+        self._check(self._lib.bbfmm_ddm_debug_level_solve(self._h, v.ctypes.data, o.ctypes.data, v.size, int(all_points)), "solve")
+        return o
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.bbfmm_ddm_debug_level_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class SchwarzPreconditioner:
     """schwarz_preconditioner (preconditioning/schwarz.rs:32-155) with the local solves batched on
     the device.  `tree`: an FmmTree over the same points / kernel (serves matvec_partial).  Use it

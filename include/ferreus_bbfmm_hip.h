@@ -754,6 +754,34 @@ int bbfmm_schwarz_level_points(const bbfmm_schwarz *h, int32_t level, int64_t *o
  * (n = N + basis_size values in, n out); parity checks. */
 int bbfmm_schwarz_debug_level_solve(bbfmm_schwarz *h, int32_t level, const double *residual, double *out,
                                     int64_t n, int32_t add_poly);
+/* Test hook: the local solvers of ONE level (Domain::factorise / Domain::solve, domain.rs:153-475, batched on the device)
+ * on domains the caller prescribes instead of those of the decomposition.  Domain i holds the points
+ * dom_idx[dom_ptr[i] .. dom_ptr[i + 1]) of `points` (n x d column-major, ld) with their internal flags; settings as for
+ * bbfmm_schwarz_create, basis_size = the monomial basis of (d, polynomial_degree).  The level is built and solved by the
+ * functions the preconditioner itself calls; the getters only copy its buffers out.
+ *   _info: info[8] = {domains, entries (points of all domains), doubles of Q, doubles of the packed matrices, 1 when the
+ *          level is one large domain (more than 2048 rows: the multi-launch path), 1 when that domain went to the pivoted
+ *          LU, domains on the host fallback, largest m}
+ *   _layout: per domain k (special points); per entry, in the domains' reordered point order (special points first), the
+ *          global index and the internal flag; Q (per domain k x m row-major, m = points - k); per domain mode (1: the
+ *          Cholesky factorisation failed, the packed matrix holds the symmetric inverse)
+ *   _assembled: Q^T A Q of every domain as the assembly kernels write it, packed lower triangles column by column (m (m +
+ *          1) / 2 doubles each), assembled again into a scratch buffer by the same launches
+ *   _factor: the packed matrices as the solves read them (the Cholesky factors, or the inverses of mode 1)
+ *   _solve: ddm_level_solve: values n doubles in; out n doubles in and out -- rows of internal points (all points when
+ *          all_points) receive the domain coefficients, the other rows are left alone. */
+typedef struct bbfmm_ddm_debug_level bbfmm_ddm_debug_level;
+int bbfmm_ddm_debug_level_create(const double *points, int64_t n, int32_t d, int64_t ld, int64_t n_dom,
+                                 const int64_t *dom_ptr, const int64_t *dom_idx, const uint8_t *dom_internal,
+                                 const bbfmm_interpolant *settings, int32_t basis_size, int32_t solve_for_poly,
+                                 bbfmm_ddm_debug_level **out);
+void bbfmm_ddm_debug_level_destroy(bbfmm_ddm_debug_level *h);
+int bbfmm_ddm_debug_level_info(const bbfmm_ddm_debug_level *h, int64_t *info);
+int bbfmm_ddm_debug_level_layout(const bbfmm_ddm_debug_level *h, int32_t *k, int64_t *indices, uint8_t *internal, double *q,
+                                 uint8_t *mode);
+int bbfmm_ddm_debug_level_assembled(const bbfmm_ddm_debug_level *h, double *out);
+int bbfmm_ddm_debug_level_factor(const bbfmm_ddm_debug_level *h, double *out);
+int bbfmm_ddm_debug_level_solve(bbfmm_ddm_debug_level *h, const double *values, double *out, int64_t n, int32_t all_points);
 /* a bbfmm_apply_fn: user = bbfmm_schwarz*, vectors of N + basis_size doubles */
 int bbfmm_schwarz_apply(void *user, const double *residual, double *correction, int64_t n);
 

@@ -33,6 +33,15 @@ def test_python_binding_covers_header():
     L.load()
 
 
+def test_ddm_debug_level_hook_is_declared_and_bound():
+    names = ["bbfmm_ddm_debug_level_create", "bbfmm_ddm_debug_level_destroy", "bbfmm_ddm_debug_level_info",
+             "bbfmm_ddm_debug_level_layout", "bbfmm_ddm_debug_level_assembled", "bbfmm_ddm_debug_level_factor",
+             "bbfmm_ddm_debug_level_solve"]
+    lib = ctypes.CDLL(L.LIB_PATH)
+    for n in names:
+        assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n
+
+
 def test_params_defaults_match_reference():
     # FmmParams::new_defaults, ferreus_bbfmm/src/bbfmm.rs:96-103
     lib = L.load()
