@@ -1196,6 +1196,18 @@ int bbfmm_debug_m2l_variants(const bbfmm_handle *h, int64_t *n_variants, int64_t
     return BBFMM_OK;
 }
 
+// Pairs and singles of the stage-1 operators (FmmTree::debug_m2l_pairs): *n_out = number of values; out (capacity
+// cap, may be NULL) receives the first min(cap, *n_out) of them.  *pairs_on: whether the handle pairs at all.
+int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on) {
+    if (!h || !n_out) return BBFMM_BAD_ARGUMENT;
+    std::vector<int32_t> v;
+    h->tree.debug_m2l_pairs(&v);
+    *n_out = static_cast<int64_t>(v.size());
+    if (pairs_on) *pairs_on = h->tree.m2l_pairs() ? 1 : 0;
+    if (out) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap, *n_out), out);
+    return BBFMM_OK;
+}
+
 int bbfmm_debug_get_coefficients(bbfmm_handle *h, char which, int32_t k, double *out) {
     GUARD(h) return h->tree.debug_get_coefficients(which, k, out);
     END_GUARD(h)

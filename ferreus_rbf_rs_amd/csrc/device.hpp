@@ -21,6 +21,9 @@ namespace bbfmm {
 constexpr int kMaxOrder = 16;      // Chebyshev nodes per axis supported on device
 constexpr int kM2lTile = 128;      // cells per M2L workgroup: 8 waves x 16
 constexpr int kM2lS1Block = 176;   // stacked-operator rows per stage-1 column block (11 groups of 16)
+constexpr int kM2lS1BlockPairs = 160; // the same of a handle whose stage 1 runs in the parity basis (10 groups: two accumulator sets)
+constexpr int kM2lSlotWindow = 128;   // most list positions (transfer vectors) a stage-1 column block may span: the kernel's slot table
+constexpr int kM2lBlkTwoDst = 1 << 30; // flag in M2lClass::blk_t0: some column of the block has a second destination
 
 struct DevCheb { // lives in device memory; kernels take a pointer
     int p, d, n, n_pad;
@@ -39,11 +42,14 @@ struct ChebRef { // device pointer + the host copies the launchers size their gr
 // of admissible transfer vectors t, hence one stacked ("tall") operator per class.
 struct M2lClass {
     // stage 1 (source side): c[(t,kk)] = sum_m VtAllT[m][row] * M_V[m]
-    const double *vt_all;   // n_pad x r_pad16 (row m contiguous over tall rows)
+    const double *vt_all;   // n_pad x r_pad16 (row m contiguous over tall rows); in the parity basis n_par x r_pad16,
+                            // rows [Vt_e | pad | Vt_o | pad] over the representatives of the node pairs {m, rho m}
     const int32_t *row_dst;  // r_pad16: -1 (padding row) or ((tpos - blk_t0[block]) << 24) | off, with tpos the
                              // position of the row's transfer vector in the class list and off the offset of
                              // the row inside the target's slot (= off_target_class[t] + kk)
-    const int32_t *blk_t0;   // r_pad16 / kM2lS1Block: first tpos of each column block
+    const int32_t *row_dst2; // parity-basis stage 1: the same for the partner Rt of the row's transfer vector, which
+                             // receives a - b where row_dst receives a + b; -1: the row belongs to a single
+    const int32_t *blk_t0;   // r_pad16 / kM2lS1Block: first tpos of each column block (| kM2lBlkTwoDst)
     int32_t n_rows;          // exact number of tall rows
     int32_t r_pad16;         // n_rows rounded up to a multiple of kM2lS1Block
     int32_t n_t;             // number of transfer vectors of this class (189 in 3-D)
@@ -104,7 +110,11 @@ int launch_l2l(const ChebRef &ch, int K, int64_t C, const int32_t *cells, int n_
 // (tile.first indexes tile_idx; a partition's compact source tiles)
 void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int max_slot_t, int K, int64_t C, const double *M, double *cbuf,
-                       int64_t cbuf_len, hipStream_t s, bool own_blocks = false, int max_blocks = 8);
+                       int64_t cbuf_len, hipStream_t s, bool own_blocks = false, int max_blocks = 8, int ne16 = 0);
+// Stage 1 in the parity basis (ne16 > 0 above: M is Mp, n_pad is n_par, the first ne16 contraction indices are the even
+// part): Mp[cell] = [M_e | pad | M_o | pad] of every cell and right-hand side; the pads are never written.
+void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne16, int n_e, int n_o, int p, int64_t rows,
+                       hipStream_t s);
 void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
                        const uint16_t *qlist, double *L, hipStream_t s, bool allow_ksplit = true);
@@ -127,6 +137,7 @@ struct M2lAssembleTv { // one transfer vector of a class list
 struct M2lAssembleClass {
     const M2lAssembleTv *src, *tgt; // device arrays
     int32_t n_src, n_tgt, r_pad16, k_pad, max_rank;
+    int32_t n_e, n_o, ne16, n_par, p; // parity basis (n_e > 0): src lists the transfer vectors that own rows
 };
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s);

@@ -96,7 +96,11 @@ __device__ inline void dma16s(const double *sbase, unsigned voff_bytes, unsigned
 // IN values of four cells (the same for every block), D_b[i][j] = OUT[cell j][col 4b + i].  A wave
 // owns 16 cells (four groups tg) and keeps 4 x NG16 accumulators; the operator tile and the
 // cells' IN values of step q+1 stream into LDS by DMA while step q is multiplied.
-template <int NG16, int STAGE, int MINW>
+// PAIRS (stage 1 in the parity basis of the x reflection): IN = Mp = [M_e | pad | M_o | pad] (n_pad = n_par values per
+// cell), OP = [Vt_e | pad | Vt_o | pad]; the first in_len / 16 steps of a column block are the even part a, the rest
+// the odd part b.  At the boundary the accumulators move to a second set, and the epilogue stores a + b through
+// row_dst and, for the blocks that hold pairs, a - b through row_dst2: one product serves t and Rt.
+template <int NG16, int STAGE, int MINW, bool PAIRS = false>
 __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restrict__ classes,
                                                   const M2lTileDesc *__restrict__ tiles, int n_pad, int g16_0,
                                                   int64_t C, const double *__restrict__ in, int64_t in_len,
@@ -112,7 +116,8 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // stage 1: the workgroup walks the column blocks zb0 .. zb1 of kM2lS1Block stacked rows (g16_0
     // selects a chunk inside a block); stage 2: one block, g16_0 selects the nodes
-    const int n_zb = STAGE == 1 ? cls.r_pad16 / kM2lS1Block : 1;
+    constexpr int BLK = PAIRS ? kM2lS1BlockPairs : kM2lS1Block; // stacked rows per column block
+    const int n_zb = STAGE == 1 ? cls.r_pad16 / BLK : 1;
     // (a tile of a sparse plan, pad == 2, names its own column blocks: q_first, q_count)
     const bool own_blocks = STAGE == 1 && tile.pad == 2;
     const int zb0 = STAGE == 1 ? (own_blocks ? tile.q_first : (int)((int64_t)n_zb * blockIdx.z / gridDim.z)) : 0;
@@ -129,6 +134,7 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     const int q_lo = STAGE == 2 ? tile.q_count * zk / ksplit : 0;
     const int nq = STAGE == 1 ? n_pad / 16 : STAGE == 2 ? tile.q_count * (zk + 1) / ksplit - q_lo : (int)(in_len / 16);
     const uint16_t *ql = qlist + tile.q_first + q_lo;
+    const int nq_e = PAIRS ? (int)(in_len / 16) : 0;
     if (zb0 >= zb1) return;
     // stage 2 with gridDim.z > 1: the z workgroups of a tile take adjacent chunks of NG16 column groups
     const int g16 = g16_0 + (STAGE >= 2 ? zc * NG16 : 0);
@@ -184,7 +190,7 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
 #pragma unroll
         for (int i = 0; i < NCH; ++i)
             if (wave + 8 * i < OP_CHUNKS)
-                dma16s(opbase + (int64_t)zb * kM2lS1Block + q * qstride, voff[i],
+                dma16s(opbase + (int64_t)zb * BLK + q * qstride, voff[i],
                        lds0 + (unsigned)(buf * BUF + (wave + 8 * i) * 128) * 8u);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -192,10 +198,14 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     };
 
     double acc[4][NG16];
+    double acc_e[4][PAIRS ? NG16 : 1]; // PAIRS: the even part a, while acc collects the odd part b
 #pragma unroll
     for (int tg = 0; tg < 4; ++tg)
 #pragma unroll
-        for (int g = 0; g < NG16; ++g) acc[tg][g] = 0.0;
+        for (int g = 0; g < NG16; ++g) {
+            acc[tg][g] = 0.0;
+            if constexpr (PAIRS) acc_e[tg][g] = 0.0;
+        }
 
     const int bk = lane >> 4, bj = lane & 3; // B layout (k, j); the block index is broadcast
     const bool wave_live = wave * 16 < tile.count;
@@ -211,7 +221,8 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     //   slots[wave][cell][slot_t]  slot bases of the wave's 16 cells for the block's transfer vectors
     //                              (requested two steps before the block ends)
     // and the stores of a block leave together and drain under the next block.
-    constexpr int AUX = 192;
+    //   PAIRS: aux[parity][192 .. 192 + 16 NG16) the second destinations of the block's columns
+    constexpr int AUX = PAIRS ? 384 : 192;
     const int32_t *aux = reinterpret_cast<const int32_t *>(lds + 2 * BUF);
     int32_t *ptab = reinterpret_cast<int32_t *>(lds + 2 * BUF) + 2 * AUX; // class positions of the 128 cells
     const int32_t *slds = aux + 2 * AUX + 128 + wave * 16 * slot_t;
@@ -220,13 +231,17 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     auto stage_cols = [&](int zb_, int par) {
         if (STAGE == 1 && 64 * wave <= 16 * NG16) {
             const int e = 64 * wave + lane;
-            const int32_t *src = e < 16 * NG16 ? cls.row_dst + zb_ * kM2lS1Block + 16 * g16 + e : cls.blk_t0 + zb_;
+            const int32_t *src = e < 16 * NG16 ? cls.row_dst + zb_ * BLK + 16 * g16 + e : cls.blk_t0 + zb_;
+            dma4(src, aux0 + (unsigned)(par * AUX + 64 * wave) * 4u);
+        } else if (PAIRS && 64 * wave < 192 + 16 * NG16) { // (16 NG16 <= 192: waves 3 .. 5)
+            const int e = 64 * wave + lane - 192;
+            const int32_t *src = e < 16 * NG16 ? cls.row_dst2 + zb_ * BLK + 16 * g16 + e : cls.blk_t0 + zb_;
             dma4(src, aux0 + (unsigned)(par * AUX + 64 * wave) * 4u);
         }
     };
     const int slot_sh = 31 - __builtin_clz(slot_t | 1); // slot_t is a power of two >= 16 in stage 1
     auto stage_slots = [&](int par) {
-        const int t0 = __builtin_amdgcn_readfirstlane(aux[par * AUX + 16 * NG16]);
+        const int t0 = __builtin_amdgcn_readfirstlane(aux[par * AUX + 16 * NG16]) & (kM2lBlkTwoDst - 1);
         const unsigned dst0 = aux0 + (unsigned)(2 * AUX + 128 + wave * 16 * slot_t) * 4u;
         for (int i = 0; i < slot_t / 4; ++i) {
             const int e = i * 64 + lane, cl = e >> slot_sh, tl = e & (slot_t - 1);
@@ -250,40 +265,98 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
             if (qcnt == nq - 2) stage_slots((zb - zb0) & 1);
         }
         if (wave_live) { // a wave without cells (short tile) only helps with the DMA and the barriers
-            double bq[4][4];
-#pragma unroll
-            for (int tg = 0; tg < 4; ++tg)
-#pragma unroll
-                for (int eh = 0; eh < 2; ++eh) {
-                    const double2 v = *reinterpret_cast<const double2 *>(ct + ((tg * 2 + eh) * 16) * 2);
-                    bq[tg][2 * eh] = v.x;
-                    bq[tg][2 * eh + 1] = v.y;
-                }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int pr = 0; pr < NP; ++pr) {
-                    const double2 a = op2[(e * NP + pr) * 64];
-#pragma unroll
-                    for (int tg = 0; tg < 4; ++tg) {
-                        acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, bq[tg][e], acc[tg][2 * pr], 0, 0, 0);
-                        acc[tg][2 * pr + 1] =
-                            __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, bq[tg][e], acc[tg][2 * pr + 1], 0, 0, 0);
-                    }
-                }
-                if (NS) {
-                    const double a = op[4 * NP * 128 + e * 64];
+            if constexpr (PAIRS) {
+                if (qcnt == nq_e) { // the even part is complete: keep it, collect the odd part
 #pragma unroll
                     for (int tg = 0; tg < 4; ++tg)
-                        acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bq[tg][e], acc[tg][NG16 - 1], 0, 0, 0);
+#pragma unroll
+                        for (int g = 0; g < NG16; ++g) {
+                            acc_e[tg][g] = acc[tg][g];
+                            acc[tg][g] = 0.0;
+                        }
+                }
+            }
+            // the cells' values of contraction indices 2 eh, 2 eh + 1 (PAIRS holds twice the accumulators: one half
+            // of the values at a time, where the other instances keep all sixteen in registers)
+            constexpr int EH = PAIRS ? 1 : 2;
+#pragma unroll
+            for (int eh0 = 0; eh0 < 2; eh0 += EH) {
+                double bq[4][2 * EH];
+#pragma unroll
+                for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                    for (int eh = 0; eh < EH; ++eh) {
+                        const double2 v = *reinterpret_cast<const double2 *>(ct + ((tg * 2 + eh0 + eh) * 16) * 2);
+                        bq[tg][2 * eh] = v.x;
+                        bq[tg][2 * eh + 1] = v.y;
+                    }
+#pragma unroll
+                for (int el = 0; el < 2 * EH; ++el) {
+                    const int e = 2 * eh0 + el;
+#pragma unroll
+                    for (int pr = 0; pr < NP; ++pr) {
+                        const double2 a = op2[(e * NP + pr) * 64];
+#pragma unroll
+                        for (int tg = 0; tg < 4; ++tg) {
+                            acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, bq[tg][el], acc[tg][2 * pr], 0, 0, 0);
+                            acc[tg][2 * pr + 1] =
+                                __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, bq[tg][el], acc[tg][2 * pr + 1], 0, 0, 0);
+                        }
+                    }
+                    if (NS) {
+                        const double a = op[4 * NP * 128 + e * 64];
+#pragma unroll
+                        for (int tg = 0; tg < 4; ++tg)
+                            acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bq[tg][el], acc[tg][NG16 - 1], 0, 0, 0);
+                    }
                 }
             }
         }
         if (++qcnt == nq) { // a column block is complete: write it out, start the next one
             qcnt = 0;
-            const int col0 = zb * kM2lS1Block + 16 * g16;
+            const int col0 = zb * BLK + 16 * g16;
             ++zb;
-            if (STAGE == 1 && wave_live) {
+            bool two_dst = false; // PAIRS: the block holds pairs (wave-uniform)
+            if constexpr (PAIRS) {
+              if (wave_live) {
+                // As below with two destinations per column: a + b to the slot of V + t, a - b to that of V + Rt.
+                double *cb = out + (int64_t)kr * out_len;
+                double *dump = cb + (out_len - 128) + 2 * lane;
+                const int32_t *auxb = aux + ((zb - 1 - zb0) & 1) * AUX;
+                two_dst = (__builtin_amdgcn_readfirstlane(auxb[16 * NG16]) & kM2lBlkTwoDst) != 0;
+                int pk[NP + NS], pk2[NP + NS];
+#pragma unroll
+                for (int pr = 0; pr < NP + NS; ++pr) {
+                    pk[pr] = auxb[pr < NP ? 32 * pr + 2 * (4 * db + di) : 32 * NP + 4 * db + di]; // the even column of a pair of columns
+                    pk2[pr] = two_dst ? auxb[192 + (pr < NP ? 32 * pr + 2 * (4 * db + di) : 32 * NP + 4 * db + di)] : -1;
+                }
+#pragma unroll
+                for (int tg = 0; tg < 4; ++tg) {
+                    const bool spv = wave * 16 + 4 * tg + dj < tile.count;
+                    const int32_t *srow = slds + (4 * tg + dj) * slot_t;
+#pragma unroll
+                    for (int pr = 0; pr < NP + NS; ++pr) {
+                        const bool single = NS && pr == NP;
+                        const int g0 = single ? NG16 - 1 : 2 * pr, g1 = single ? NG16 - 1 : 2 * pr + 1;
+                        const int sl = srow[max(pk[pr] >> 24, 0)];
+                        const int okm = (spv ? -1 : 0) & ~(pk[pr] | sl); // sign bit set: valid cell, row, slot
+                        double *dst = okm < 0 ? cb + (int64_t)sl * 2 + (pk[pr] & 0xffffff) : dump;
+                        if (single) *dst = acc_e[tg][g0] + acc[tg][g0];
+                        else *reinterpret_cast<double2 *>(dst) = make_double2(acc_e[tg][g0] + acc[tg][g0], acc_e[tg][g1] + acc[tg][g1]);
+                        if (two_dst) {
+                            const int sl2 = srow[max(pk2[pr] >> 24, 0)];
+                            const int okm2 = (spv ? -1 : 0) & ~(pk2[pr] | sl2);
+                            double *dst2 = okm2 < 0 ? cb + (int64_t)sl2 * 2 + (pk2[pr] & 0xffffff) : dump;
+                            if (single) *dst2 = acc_e[tg][g0] - acc[tg][g0];
+                            else *reinterpret_cast<double2 *>(dst2) = make_double2(acc_e[tg][g0] - acc[tg][g0], acc_e[tg][g1] - acc[tg][g1]);
+                        }
+                    }
+                    // (both accumulator sets are live here: keep the slot lookups of the next cell group from being
+                    // hoisted above this group's stores, which would spill)
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+              }
+            } else if (STAGE == 1 && wave_live) {
                 // Scatter into the target slots, branch-free: entries without a destination (padding
                 // rows, absent targets, cells beyond the tile) go to a dump area behind the slot buffer.
                 // Measured: the epilogue is store-issue bound (about 75 cycles per store instruction
@@ -345,7 +418,8 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
             // the 4 * (NP + NS) scatter stores issued after this step's DMA drain under the next block
             // (a wave without cells stored nothing: it waits for its DMA as usual)
             if (STAGE == 1) {
-                if (wave_live) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NP + NS) < 63 ? 4 * (NP + NS) : 63) : "memory");
+                if (wave_live && two_dst) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NP + NS) < 63 ? 8 * (NP + NS) : 63) : "memory");
+                else if (wave_live) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NP + NS) < 63 ? 4 * (NP + NS) : 63) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 continue;
@@ -355,16 +429,16 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     }
 }
 
-template <int NG16, int STAGE, int MINW>
+template <int NG16, int STAGE, int MINW, bool PAIRS = false>
 static void m2l_gemm_launch(const M2lClass *classes, const M2lTileDesc *tiles, int n_tiles, int n_pad, int g16_0,
                             int n_colblocks, int K, int64_t C, const double *in, int64_t in_len, double *out,
                             int64_t out_len, const uint16_t *qlist, int slot_t, const int32_t *tile_idx, hipStream_t s) {
-    const size_t lds = 2 * sizeof(double) * (size_t)(2 * NG16 * 128 + 2048) + (STAGE == 1 ? (size_t)(2 * 192 + 128 + 8 * 16 * (slot_t & 0xffff)) * 4 : 0); // + aux, cell and slot tables
+    const size_t lds = 2 * sizeof(double) * (size_t)(2 * NG16 * 128 + 2048) + (STAGE == 1 ? (size_t)(2 * (PAIRS ? 384 : 192) + 128 + 8 * 16 * (slot_t & 0xffff)) * 4 : 0); // + aux, cell and slot tables
     // one flag word per template instance; a refused attribute shows up as the failed launch
     static std::atomic<uint64_t> attr_set[4] = {{0}, {0}, {0}, {0}};
-    (void)allow_large_dynamic_lds(reinterpret_cast<const void *>(&m2l_gemm_k4<NG16, STAGE, MINW>), lds, attr_set);
+    (void)allow_large_dynamic_lds(reinterpret_cast<const void *>(&m2l_gemm_k4<NG16, STAGE, MINW, PAIRS>), lds, attr_set);
     const int zdim = STAGE == 2 && slot_t > 1 ? n_colblocks * slot_t : n_colblocks; // stage 2: slot_t = parts of the contraction
-    hipLaunchKernelGGL((m2l_gemm_k4<NG16, STAGE, MINW>), dim3(n_tiles, K, zdim), dim3(512), lds, s, classes,
+    hipLaunchKernelGGL((m2l_gemm_k4<NG16, STAGE, MINW, PAIRS>), dim3(n_tiles, K, zdim), dim3(512), lds, s, classes,
                        tiles, n_pad, g16_0, C, in, in_len, out, out_len, qlist, slot_t, tile_idx);
 }
 
@@ -436,7 +510,7 @@ static void m2l_dispatch_chunks(int total_groups, const M2lClass *classes, const
 // blockIdx.z walks the column blocks, the chunk plan splits a block.
 void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int max_slot_t, int K, int64_t C, const double *M, double *cbuf, int64_t cbuf_len,
-                       hipStream_t s, bool own_blocks, int max_blocks) {
+                       hipStream_t s, bool own_blocks, int max_blocks, int ne16) {
     if (n_tiles == 0) return;
     int slot_t = 16; // LDS slot-table width: power of two covering the transfer vectors of any block
     while (slot_t < max_slot_t) slot_t *= 2;
@@ -461,6 +535,11 @@ void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const 
         }
     }
     const int n_colblocks = own_blocks ? 1 : zsplit; // tiles that name their own blocks are not split further
+    if (ne16 > 0) { // parity basis: one instance, a whole column block per walk step (in_len carries the even part's length)
+        m2l_gemm_launch<kM2lS1BlockPairs / 16, 1, 1, true>(classes, tiles, n_tiles, n_pad, 0, n_colblocks, K, C, M, ne16, cbuf, cbuf_len,
+                                                      nullptr, slot_t, tile_idx, s);
+        return;
+    }
     m2l_dispatch_chunks<1>(kM2lS1Block / 16, classes, tiles, n_tiles, n_pad, n_colblocks, K, C, M, 0, cbuf, cbuf_len, nullptr,
                            slot_t, tile_idx, s);
 }
@@ -508,6 +587,35 @@ void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const 
         }
     }
     m2l_dispatch_chunks<2>(n_pad / 16, classes, tiles, n_tiles, n_pad, z, K, C, cbuf, cbuf_len, L, 0, qlist, ksplit > 1 ? ksplit : 0, tile_idx, s);
+}
+
+// The multipoles in the parity basis of the x reflection: row = (right-hand side, cell), Mp[row] = [M_e | pad | M_o | pad]
+// with M_e[j] = M[j] + M[rho j], M_o[j] = M[j] - M[rho j] for the representatives j < n_o, M_e[j] = M[j] on the centre
+// plane n_o <= j < n_e of an odd order.  rho j = j + (p - 1 - 2 (j / p1)) p1, p1 = n_e / ceil(p / 2).  Streaming, HBM bound.
+__global__ __launch_bounds__(256) void m2l_parity_kernel(const double *__restrict__ M, int n_pad, double *__restrict__ Mp, int n_par,
+                                                         int ne16, int n_e, int n_o, int p, int p1, int64_t rows) {
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double *src = M + row * n_pad;
+    double *dst = Mp + row * n_par;
+    for (int j = threadIdx.x & 63; j < n_e; j += 64) {
+        const double v = src[j];
+        if (j < n_o) {
+            const double w = src[j + (p - 1 - 2 * (j / p1)) * p1];
+            dst[j] = v + w;
+            dst[ne16 + j] = v - w;
+        } else {
+            dst[j] = v;
+        }
+    }
+}
+
+void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne16, int n_e, int n_o, int p, int64_t rows,
+                       hipStream_t s) {
+    if (rows <= 0) return;
+    const int p1 = n_e / ((p + 1) / 2);
+    hipLaunchKernelGGL(m2l_parity_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, M, n_pad, Mp, n_par, ne16, n_e,
+                       n_o, p, p1, rows);
 }
 
 // Slot segments of absent pairs: 16 lanes per segment, 16 bytes per lane and round.
@@ -610,6 +718,31 @@ __global__ __launch_bounds__(256) void assemble_vt_kernel(M2lAssembleClass c, in
     }
 }
 
+// The same in the parity basis: one thread per (row-owning transfer vector, representative j < n_e) writes the entries
+// of Vt_e row j and, off the centre plane, of Vt_o row ne16 + j; the factor 1/2 is exact.
+__global__ __launch_bounds__(256) void assemble_vt_parity_kernel(M2lAssembleClass c, int n, const double *__restrict__ ops,
+                                                                 const int32_t *__restrict__ invperm, double *__restrict__ vt_all) {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(c.n_src) * c.n_e) return;
+    const int pos = static_cast<int>(t / c.n_e), j = static_cast<int>(t % c.n_e);
+    const M2lAssembleTv tv = c.src[pos];
+    const int p1 = n / c.p;
+    const int rj = j + (c.p - 1 - 2 * (j / p1)) * p1;
+    const int32_t *inv = invperm + static_cast<int64_t>(tv.perm) * n;
+    const double *s0 = ops + tv.vt_off + static_cast<int64_t>(inv[j]) * tv.rank;
+    const double *s1 = ops + tv.vt_off + static_cast<int64_t>(inv[rj]) * tv.rank;
+    double *de = vt_all + static_cast<int64_t>(j) * c.r_pad16 + tv.row;
+    double *dod = vt_all + static_cast<int64_t>(c.ne16 + j) * c.r_pad16 + tv.row;
+    if (j >= c.n_o) {
+        for (int kk = 0; kk < tv.rank; ++kk) de[kk] = s0[kk];
+    } else {
+        for (int kk = 0; kk < tv.rank; ++kk) {
+            de[kk] = 0.5 * (s0[kk] + s1[kk]);
+            dod[kk] = 0.5 * (s0[kk] - s1[kk]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void assemble_u_kernel(M2lAssembleClass c, int n, int n_pad, const double *__restrict__ ops,
                                                          const int32_t *__restrict__ invperm, double *__restrict__ u_all) {
     const int pos = blockIdx.y;
@@ -622,9 +755,12 @@ __global__ __launch_bounds__(256) void assemble_u_kernel(M2lAssembleClass c, int
 
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s) {
-    (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(n_pad) * c.r_pad16 * sizeof(double), s);
+    (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(c.n_e > 0 ? c.n_par : n_pad) * c.r_pad16 * sizeof(double), s);
     (void)hipMemsetAsync(u_all, 0, static_cast<size_t>(c.k_pad) * n_pad * sizeof(double), s);
-    if (c.n_src > 0)
+    if (c.n_src > 0 && c.n_e > 0)
+        hipLaunchKernelGGL(assemble_vt_parity_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * c.n_e + 255) / 256)), dim3(256),
+                           0, s, c, n, ops, invperm, vt_all);
+    else if (c.n_src > 0)
         // (one thread per entry, no grid-stride loop: the exact block count, not grid_for's capped one)
         hipLaunchKernelGGL(assemble_vt_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * n + 255) / 256)), dim3(256), 0, s, c, n, n_pad,
                            compressed ? 1 : 0, ops, invperm, vt_all);

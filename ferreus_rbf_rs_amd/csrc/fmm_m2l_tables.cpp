@@ -8,12 +8,12 @@ namespace bbfmm {
 void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, std::vector<double> *vt_all,
                                        std::vector<double> *u_all) const {
     const int n_pad = round_up(ops_.n, 32);
-    vt_all->resize(static_cast<size_t>(n_pad) * hc.r_pad16);
+    vt_all->resize(static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : n_pad) * hc.r_pad16);
     u_all->resize(static_cast<size_t>(hc.k_pad) * n_pad);
     fill_m2l_operator_arrays(hc, vt_all->data(), u_all->data());
 }
 
-// vt_all: n_pad x r_pad16, u_all: k_pad x n_pad (both overwritten, padding zeroed)
+// vt_all: n_pad x r_pad16 (m2l_npar_ x r_pad16 in the parity basis), u_all: k_pad x n_pad (both overwritten, padding zeroed)
 void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, double *u_all) const {
     const int n = ops_.n, n_pad = round_up(n, 32);
     const bool compressed = ops_.compression != kCompressionNone;
@@ -23,7 +23,7 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
             std::memset(p + b, 0, static_cast<size_t>(e - b) * sizeof(double));
         });
     };
-    zero(vt_all, static_cast<size_t>(n_pad) * hc.r_pad16);
+    zero(vt_all, static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : n_pad) * hc.r_pad16);
     zero(u_all, static_cast<size_t>(hc.k_pad) * n_pad);
     struct RowSrc {
         const M2lOperator *op;
@@ -31,26 +31,49 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
         int first_row;
     };
     std::vector<RowSrc> row_src;
-    int row = 0;
-    for (int tv : hc.src_tv) {
+    for (size_t pos = 0; pos < hc.src_tv.size(); ++pos) {
+        if (m2l_pairs_ && hc.src_pair[pos] == -2) continue; // the second of a pair shares the rows of the first
+        const int tv = hc.src_tv[pos];
         const M2lOperator &op = lops[ops_.ref_lookup[tv]];
-        row_src.push_back(RowSrc{&op, &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[tv]) * n], row});
-        row += round_up(op.rank, 2);
+        row_src.push_back(RowSrc{&op, &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[tv]) * n], hc.src_row0[pos]});
     }
-    // c[kk] = sum_m Vt[kk][invperm[m]] * M_V[m]   (bbfmm.rs:924-930 folded)
-    parallel_for(n, 8, [&](int64_t m) {
-        double *dst = vt_all + static_cast<size_t>(m) * hc.r_pad16;
-        for (const RowSrc &rs : row_src) {
-            const int r = rs.op->rank;
-            const int im = rs.inv[m];
-            if (compressed) {
-                const double *src = &rs.op->vt[static_cast<size_t>(im) * r];
-                for (int kk = 0; kk < r; ++kk) dst[rs.first_row + kk] = src[kk];
-            } else {
-                dst[rs.first_row + im] = 1.0;
+    // Parity basis: rows [0, ne16) hold Vt_e[kk][j] = (Vt_t[kk][j] + Vt_t[kk][rho j]) / 2 (the centre plane of an odd
+    // order: Vt_t[kk][j]), rows [ne16, n_par) hold Vt_o[kk][j] = (Vt_t[kk][j] - Vt_t[kk][rho j]) / 2
+    if (m2l_pairs_) {
+        parallel_for(m2l_ne_, 8, [&](int64_t j) {
+            const bool centre = j >= m2l_no_;
+            const int rj = m2l_rho(static_cast<int>(j));
+            double *de = vt_all + static_cast<size_t>(j) * hc.r_pad16;
+            double *dod = vt_all + static_cast<size_t>(m2l_ne16_ + j) * hc.r_pad16;
+            for (const RowSrc &rs : row_src) {
+                const int r = rs.op->rank;
+                const double *s0 = &rs.op->vt[static_cast<size_t>(rs.inv[j]) * r], *s1 = &rs.op->vt[static_cast<size_t>(rs.inv[rj]) * r];
+                for (int kk = 0; kk < r; ++kk) {
+                    if (centre) {
+                        de[rs.first_row + kk] = s0[kk];
+                    } else {
+                        de[rs.first_row + kk] = 0.5 * (s0[kk] + s1[kk]);
+                        dod[rs.first_row + kk] = 0.5 * (s0[kk] - s1[kk]);
+                    }
+                }
             }
-        }
-    });
+        });
+    } else {
+        // c[kk] = sum_m Vt[kk][invperm[m]] * M_V[m]   (bbfmm.rs:924-930 folded)
+        parallel_for(n, 8, [&](int64_t m) {
+            double *dst = vt_all + static_cast<size_t>(m) * hc.r_pad16;
+            for (const RowSrc &rs : row_src) {
+                const int r = rs.op->rank;
+                const int im = rs.inv[m];
+                if (compressed) {
+                    const double *src = &rs.op->vt[static_cast<size_t>(im) * r];
+                    for (int kk = 0; kk < r; ++kk) dst[rs.first_row + kk] = src[kk];
+                } else {
+                    dst[rs.first_row + im] = 1.0;
+                }
+            }
+        });
+    }
     // L_B[i] += sum_kk U[invperm[i]][kk] * c[kk]   (bbfmm.rs:975-981 folded)
     parallel_for(static_cast<int64_t>(hc.tgt_tv.size()), 1, [&](int64_t pos) {
         const int tv = hc.tgt_tv[pos];
@@ -97,6 +120,35 @@ int FmmTree::build_m2l_tables() {
     }
 
     auto comp = [&](int tv, int a) { return ops_.all_vecs[static_cast<size_t>(tv) * d + a]; };
+    // Reflected pairs of stage 1.  t and Rt (component 0 negated) use the same reference operator, and their
+    // permutations differ by the node reflection rho of axis 0: Vt_{Rt}[kk][m] = Vt_t[kk][rho m].  The identity is
+    // checked here for every candidate; a pair that fails it stays two singles.
+    {
+        const char *e = std::getenv("BBFMM_M2L_S1_PAIRS"); // read per handle, like BBFMM_M2L_CBUF_MB
+        m2l_pairs_ = !(e && std::atoi(e) == 0) && compressed && !shared_basis_ && d >= 2 && ops_.p >= 2;
+        m2l_partner_.assign(static_cast<size_t>(nvec), -1);
+        m2l_s1_block_ = m2l_pairs_ ? kM2lS1BlockPairs : kM2lS1Block;
+        const int p1 = n / ops_.p;
+        m2l_ne_ = (ops_.p + 1) / 2 * p1;
+        m2l_no_ = ops_.p / 2 * p1;
+        m2l_ne16_ = round_up(m2l_ne_, 16);
+        m2l_npar_ = m2l_ne16_ + round_up(m2l_no_, 16);
+        for (int tv = 0; tv < nvec && m2l_pairs_; ++tv) {
+            if (comp(tv, 0) == 0) continue;
+            int rt = -1;
+            for (int u = 0; u < nvec && rt < 0; ++u) {
+                bool same = comp(u, 0) == -comp(tv, 0);
+                for (int a = 1; a < d; ++a) same = same && comp(u, a) == comp(tv, a);
+                if (same) rt = u;
+            }
+            if (rt < 0 || ops_.ref_lookup[rt] != ops_.ref_lookup[tv]) continue;
+            const int32_t *it = &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[tv]) * n];
+            const int32_t *ir = &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[rt]) * n];
+            bool ok = true;
+            for (int m = 0; m < n && ok; ++m) ok = ir[m] == it[m2l_rho(m)];
+            if (ok) m2l_partner_[static_cast<size_t>(tv)] = rt;
+        }
+    }
     auto far = [&](int tv) {
         int mx = 0;
         for (int a = 0; a < d; ++a) mx = std::max(mx, std::abs(comp(tv, a)));
@@ -122,6 +174,27 @@ int FmmTree::build_m2l_tables() {
                 tpos_src[o][tv] = static_cast<int>(src_list[o].size());
                 src_list[o].push_back(tv);
             }
+        }
+    // the source lists in stage-1 order: the pairs first (Rt directly behind t), then the singles
+    if (m2l_pairs_)
+        for (int o = 0; o < ncls; ++o) {
+            std::vector<int> ordered, singles;
+            std::vector<uint8_t> used(static_cast<size_t>(nvec), 0);
+            for (int tv : src_list[o]) {
+                const int rt = m2l_partner_[static_cast<size_t>(tv)];
+                if (used[static_cast<size_t>(tv)]) continue;
+                if (rt >= 0 && tpos_src[o][rt] >= 0 && m2l_partner_[static_cast<size_t>(rt)] == tv) {
+                    const int first = comp(tv, 0) > 0 ? tv : rt;
+                    ordered.push_back(first);
+                    ordered.push_back(first == tv ? rt : tv);
+                    used[static_cast<size_t>(tv)] = used[static_cast<size_t>(rt)] = 1;
+                } else {
+                    singles.push_back(tv);
+                }
+            }
+            ordered.insert(ordered.end(), singles.begin(), singles.end());
+            src_list[o] = ordered;
+            for (size_t i = 0; i < ordered.size(); ++i) tpos_src[o][ordered[i]] = static_cast<int>(i);
         }
     auto target_class = [&](int o, int tv) {
         int oc = 0;
@@ -221,49 +294,101 @@ int FmmTree::build_m2l_tables() {
         // Stage-1 row tables of a class-o operator stacked over the transfer vectors `tvs` (the whole admissible
         // list for the class itself, the present ones for a boundary variant): every transfer vector's rows
         // start at an even stacked row (the scatter stores pairs of adjacent rows as 16 bytes).
+        // a pair: Rt directly behind t in the list, the identity verified (a variant or a group operator that lost
+        // one of the two keeps the other as a single).  Returns the stacked rows of the list and the first row of every
+        // vector that owns rows.  The kernel's slot table holds kM2lSlotWindow list positions per column block: where
+        // the ranks are so low that a block would span more (160 columns of rank-2 pairs: 160 positions), the next
+        // vector starts a new block and the rest of the old one stays padding.
+        auto mark_pairs = [&](const std::vector<int> &tvs, std::vector<int32_t> *src_pair, std::vector<int32_t> *row0 = nullptr) {
+            src_pair->assign(tvs.size(), -1);
+            for (size_t pos = 0; m2l_pairs_ && pos + 1 < tvs.size(); ++pos)
+                if (m2l_partner_[static_cast<size_t>(tvs[pos])] == tvs[pos + 1] && m2l_partner_[static_cast<size_t>(tvs[pos + 1])] == tvs[pos]) {
+                    (*src_pair)[pos] = static_cast<int32_t>(pos + 1);
+                    (*src_pair)[pos + 1] = -2;
+                    ++pos;
+                }
+            if (row0) row0->assign(tvs.size(), 0);
+            int rows = 0, blk = -1, blk_first = 0; // blk_first: first list position with rows in block blk
+            for (size_t pos = 0; pos < tvs.size(); ++pos) {
+                if ((*src_pair)[pos] == -2) continue;
+                const int r = rank_of(tvs[pos]);
+                if (r == 0) continue;
+                const int last = (*src_pair)[pos] >= 0 ? static_cast<int>(pos) + 1 : static_cast<int>(pos);
+                if (rows / m2l_s1_block_ == blk && last - blk_first + 1 > kM2lSlotWindow) rows = round_up(rows, m2l_s1_block_);
+                if (row0) (*row0)[pos] = rows;
+                const int b1 = (rows + r - 1) / m2l_s1_block_; // the last block the vector's rows reach
+                if (rows / m2l_s1_block_ != blk || b1 != blk) {
+                    blk = b1;
+                    blk_first = static_cast<int>(pos); // (also of a block the vector only reaches into: it is the first there)
+                }
+                rows = round_up(rows + r, 2);
+            }
+            return rows;
+        };
         auto stage1_rows = [&](int o, const std::vector<int> &tvs, HostM2lClass *hcp) {
             HostM2lClass &hc = *hcp;
             hc.n_t = static_cast<int>(tvs.size());
-            hc.n_rows = 0;
-            for (int tv : tvs) hc.n_rows += round_up(rank_of(tv), 2);
-            hc.r_pad16 = round_up(std::max(hc.n_rows, 1), kM2lS1Block);
+            std::vector<int32_t> first_row;
+            hc.n_rows = mark_pairs(tvs, &hc.src_pair, &first_row);
+            hc.r_pad16 = round_up(std::max(hc.n_rows, 1), m2l_s1_block_);
             hc.row_tpos.assign(hc.r_pad16, -1);
             hc.row_off.assign(hc.r_pad16, 0);
+            hc.row_tpos2.assign(hc.r_pad16, -1);
+            hc.row_off2.assign(hc.r_pad16, 0);
             hc.src_tv = tvs;
             int row = 0;
             hc.src_row0.assign(tvs.size(), 0);
             hc.src_row1.assign(tvs.size(), 0);
             for (size_t pos = 0; pos < tvs.size(); ++pos) {
+                if (hc.src_pair[pos] == -2) { // the rows of the first of the pair
+                    hc.src_row0[pos] = hc.src_row0[pos - 1];
+                    hc.src_row1[pos] = hc.src_row1[pos - 1];
+                    continue;
+                }
                 const int tv = tvs[pos];
                 const int oc = target_class(o, tv);
                 const int base_off = off_tgt[oc][tpos_tgt[oc][tv]];
+                int base_off2 = 0;
+                if (hc.src_pair[pos] >= 0) {
+                    const int tv2 = tvs[pos + 1], oc2 = target_class(o, tv2);
+                    base_off2 = off_tgt[oc2][tpos_tgt[oc2][tv2]];
+                }
+                if (rank_of(tv) > 0) row = first_row[pos];
                 hc.src_row0[pos] = row;
                 for (int kk = 0; kk < rank_of(tv); ++kk, ++row) {
                     hc.row_tpos[row] = static_cast<int32_t>(pos);
                     hc.row_off[row] = base_off + kk;
+                    if (hc.src_pair[pos] >= 0) {
+                        hc.row_tpos2[row] = static_cast<int32_t>(pos + 1);
+                        hc.row_off2[row] = base_off2 + kk;
+                    }
                 }
                 hc.src_row1[pos] = row;
                 row = round_up(row, 2); // the padding row keeps tpos -1 (never stored on its own)
             }
             // per column block: first transfer-vector position, and the packed row table
-            const int n_blk = hc.r_pad16 / kM2lS1Block;
+            const int n_blk = hc.r_pad16 / m2l_s1_block_;
             m2l_max_blocks_ = std::max(m2l_max_blocks_, n_blk);
             hc.blk_t0.assign(n_blk, 0);
             hc.row_dst.assign(hc.r_pad16, -1);
+            hc.row_dst2.assign(hc.r_pad16, -1);
             for (int b = 0; b < n_blk; ++b) {
                 int t0 = -1, t1 = -1;
-                for (int r = b * kM2lS1Block; r < (b + 1) * kM2lS1Block; ++r) {
+                bool two = false; // some column of the block has a second destination
+                for (int r = b * m2l_s1_block_; r < (b + 1) * m2l_s1_block_; ++r) {
                     if (hc.row_tpos[r] < 0) continue;
                     if (t0 < 0) t0 = hc.row_tpos[r];
-                    t1 = hc.row_tpos[r];
+                    t1 = std::max(hc.row_tpos[r], hc.row_tpos2[r]); // (positions ascend with the rows; a partner is pos + 1)
+                    two = two || hc.row_tpos2[r] >= 0;
                 }
                 if (t0 < 0) continue;
-                hc.blk_t0[b] = t0;
+                hc.blk_t0[b] = t0 | (two ? kM2lBlkTwoDst : 0);
                 m2l_slot_t_ = std::max(m2l_slot_t_, t1 - t0 + 1);
-                for (int r = b * kM2lS1Block; r < (b + 1) * kM2lS1Block; ++r) {
+                for (int r = b * m2l_s1_block_; r < (b + 1) * m2l_s1_block_; ++r) {
                     if (hc.row_tpos[r] < 0) continue;
-                    if (hc.row_off[r] >= (1 << 24)) return false;
+                    if (hc.row_off[r] >= (1 << 24) || hc.row_off2[r] >= (1 << 24)) return false;
                     hc.row_dst[r] = ((hc.row_tpos[r] - t0) << 24) | hc.row_off[r];
+                    if (hc.row_tpos2[r] >= 0) hc.row_dst2[r] = ((hc.row_tpos2[r] - t0) << 24) | hc.row_off2[r];
                 }
             }
             return true;
@@ -521,15 +646,16 @@ int FmmTree::build_m2l_tables() {
                 while (j < nc && same_pattern(i, j)) ++j;
                 size_t full = 0;
                 if (variants_on && j - i >= static_cast<size_t>(variant_min_tiles) * kM2lTile) {
-                    int present_rows = 0;
                     std::vector<int> tvs;
                     for (int ps = 0; ps < nt; ++ps)
-                        if (hc.cslot[i * nt + ps] >= 0) {
-                            tvs.push_back(hc.src_tv[ps]);
-                            present_rows += round_up(rank_of(hc.src_tv[ps]), 2);
-                        }
-                    // worth a variant: at least one column block of 26 saved
-                    if (!tvs.empty() && round_up(present_rows, kM2lS1Block) < hc.r_pad16) {
+                        if (hc.cslot[i * nt + ps] >= 0) tvs.push_back(hc.src_tv[ps]);
+                    std::vector<int32_t> marks;
+                    const int present_rows = mark_pairs(tvs, &marks);
+                    // worth a variant: at least one column block saved -- or, in the parity basis, pairs that lost their
+                    // partner (the cells of an x face): no columns go, but the blocks of the singles that remain issue
+                    // one store per column instead of two (the epilogue is bound by the number of stores)
+                    auto n_pairs = [](const std::vector<int32_t> &m) { return std::count_if(m.begin(), m.end(), [](int32_t v) { return v >= 0; }); };
+                    if (!tvs.empty() && (round_up(present_rows, m2l_s1_block_) < hc.r_pad16 || n_pairs(marks) < n_pairs(hc.src_pair))) {
                         full = (j - i) / kM2lTile * kM2lTile;
                         HostM2lClass v;
                         v.level = level;
@@ -895,6 +1021,23 @@ int FmmTree::build_shared_basis(std::vector<DevBuf<double>> *d_level_ops) {
 // construction without a GPU; never reached from a compute entry point.
 int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
     const int n = ops_.n, n_pad = round_up(n, 32);
+    // the multipoles in the parity basis, as the device's change-of-basis pass writes them: [M_e | pad | M_o | pad]
+    std::vector<double> Mp;
+    if (m2l_pairs_) {
+        Mp.assign(static_cast<size_t>(tree_.n_cells()) * m2l_npar_, 0.0);
+        for (int64_t c = 0; c < tree_.n_cells(); ++c) {
+            const double *Mv = M + static_cast<size_t>(c) * n;
+            double *mp = &Mp[static_cast<size_t>(c) * m2l_npar_];
+            for (int j = 0; j < m2l_ne_; ++j) {
+                if (j < m2l_no_) {
+                    mp[j] = Mv[j] + Mv[m2l_rho(j)];
+                    mp[m2l_ne16_ + j] = Mv[j] - Mv[m2l_rho(j)];
+                } else {
+                    mp[j] = Mv[j];
+                }
+            }
+        }
+    }
     // exactly as the unrestricted device launches walk them: batch by batch through ONE buffer of the largest
     // batch's length (slot addresses are relative to the batch), stage 1 over the batch's tile list (boundary
     // variants, group operators), stage 2 over the classes of the batch.  The buffer is NOT cleared between batches:
@@ -922,6 +1065,17 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
                 for (int row = 0; row < hc.n_rows; ++row) {
                     if (hc.row_tpos[row] < 0) continue; // padding row
                     const int32_t slot = hc.cslot[pos * hc.n_t + hc.row_tpos[row]];
+                    if (m2l_pairs_) { // a over the even part, b over the odd part; a + b to the row's vector, a - b to its partner
+                        const int32_t slot2 = hc.row_tpos2[row] >= 0 ? hc.cslot[pos * hc.n_t + hc.row_tpos2[row]] : -1;
+                        if (slot < 0 && slot2 < 0) continue;
+                        const double *mp = &Mp[static_cast<size_t>(hc.cells[pos]) * m2l_npar_];
+                        double a = 0.0, bsum = 0.0;
+                        for (int j = 0; j < m2l_ne16_; ++j) a += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                        for (int j = m2l_ne16_; j < m2l_npar_; ++j) bsum += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                        if (slot >= 0) cbuf[static_cast<size_t>(slot) * 2 + hc.row_off[row]] = a + bsum;
+                        if (slot2 >= 0) cbuf[static_cast<size_t>(slot2) * 2 + hc.row_off2[row]] = a - bsum;
+                        continue;
+                    }
                     if (slot < 0) continue;
                     double s = 0.0;
                     for (int m = 0; m < n; ++m) s += hc.vt_all[static_cast<size_t>(m) * hc.r_pad16 + row] * Mv[m];
@@ -954,6 +1108,28 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
             if (seen[c] != want) return BBFMM_BAD_ARGUMENT;
         }
     return BBFMM_OK;
+}
+
+void FmmTree::debug_m2l_pairs(std::vector<int32_t> *out) const {
+    out->clear();
+    const int d = d_;
+    for (size_t i = 0; i < m2l_host_.size() + m2l_variants_.size(); ++i) {
+        const HostM2lClass &h = i < m2l_host_.size() ? m2l_host_[i] : m2l_variants_[i - m2l_host_.size()];
+        if (h.cells.empty()) continue;
+        out->push_back(h.level);
+        out->push_back(h.octant);
+        out->push_back(i < m2l_host_.size() ? 0 : 1);
+        const size_t n_at = out->size();
+        out->push_back(0);
+        int32_t n_entries = 0;
+        for (size_t pos = 0; pos < h.src_tv.size(); ++pos) {
+            if (h.src_pair[pos] == -2) continue;
+            out->push_back(h.src_pair[pos] >= 0 ? 1 : 0);
+            for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.src_tv[pos]) * d + a]);
+            ++n_entries;
+        }
+        (*out)[n_at] = n_entries;
+    }
 }
 
 } // namespace bbfmm

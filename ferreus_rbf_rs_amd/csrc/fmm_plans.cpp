@@ -659,7 +659,7 @@ int FmmTree::build_downward_plan(const std::vector<int32_t> &target_leaves, Down
     } else {
         std::vector<int64_t> bm_off(sops.size() + 1, 0); // per source operator: n_blk x n_cells flags
         for (size_t si = 0; si < sops.size(); ++si)
-            bm_off[si + 1] = bm_off[si] + static_cast<int64_t>(sops[si].h->r_pad16 / kM2lS1Block) * static_cast<int64_t>(sops[si].h->cells.size());
+            bm_off[si + 1] = bm_off[si] + static_cast<int64_t>(sops[si].h->r_pad16 / m2l_s1_block_) * static_cast<int64_t>(sops[si].h->cells.size());
         std::vector<uint8_t> bm(static_cast<size_t>(bm_off.back()), 0);
         std::vector<std::vector<int32_t>> spos(sops.size());
         for (size_t si = 0; si < sops.size(); ++si) {
@@ -683,7 +683,7 @@ int FmmTree::build_downward_plan(const std::vector<int32_t> &target_leaves, Down
                     const HostM2lClass &hs = *sops[static_cast<size_t>(si)].h;
                     if (hs.src_row1[sp] <= hs.src_row0[sp]) continue;
                     const int64_t nc = static_cast<int64_t>(hs.cells.size());
-                    for (int zb = hs.src_row0[sp] / kM2lS1Block; zb <= (hs.src_row1[sp] - 1) / kM2lS1Block; ++zb)
+                    for (int zb = hs.src_row0[sp] / m2l_s1_block_; zb <= (hs.src_row1[sp] - 1) / m2l_s1_block_; ++zb)
                         flag(&bm[static_cast<size_t>(bm_off[static_cast<size_t>(si)] + zb * nc + pos_of[S])]);
                 }
             }
@@ -691,7 +691,7 @@ int FmmTree::build_downward_plan(const std::vector<int32_t> &target_leaves, Down
         for (size_t si = 0; si < sops.size(); ++si) {
             const HostM2lClass &hs = *sops[si].h;
             const int64_t nc = static_cast<int64_t>(hs.cells.size());
-            const int n_blk = hs.r_pad16 / kM2lS1Block;
+            const int n_blk = hs.r_pad16 / m2l_s1_block_;
             const size_t bidx = static_cast<size_t>(m2l_batch_of_class_[static_cast<size_t>(sops[si].dev_class)]);
             // one tile per (column block, up to 128 of the sources that need it)
             for (int zb = 0; zb < n_blk; ++zb) {

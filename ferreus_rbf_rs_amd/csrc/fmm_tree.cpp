@@ -501,20 +501,21 @@ int FmmTree::upload() {
         c.n_cells = static_cast<int32_t>(h.cells.size());
         if (h.cells.empty()) continue;
         DevBuf<double> vt, ua;
-        DevBuf<int32_t> rt, ro, ce, cs;
+        DevBuf<int32_t> rt, rt2, ro, ce, cs;
         DevBuf<int64_t> cb;
         {
-            const size_t nvt = static_cast<size_t>(cheb_.n_pad) * h.r_pad16, nu = static_cast<size_t>(h.k_pad) * cheb_.n_pad;
+            const size_t nvt = static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : cheb_.n_pad) * h.r_pad16, nu = static_cast<size_t>(h.k_pad) * cheb_.n_pad;
             CHK(dalloc(&vt, nvt));
             CHK(dalloc(&ua, nu));
             const auto &lops = ops_.m2l[h.level];
             std::vector<M2lAssembleTv> src_tv, tgt_tv;
-            int row = 0, max_rank = 0;
-            for (int tv : h.src_tv) {
+            int max_rank = 0;
+            for (size_t pos = 0; pos < h.src_tv.size(); ++pos) {
+                if (m2l_pairs_ && h.src_pair[pos] == -2) continue; // the second of a pair owns no rows
+                const int tv = h.src_tv[pos];
                 const int ref = ops_.ref_lookup[tv];
                 const int rank = lops[ref].rank;
-                src_tv.push_back(M2lAssembleTv{ops_.perm_lookup[tv], rank, row, vt_off[h.level][ref], u_off[h.level][ref]});
-                row += round_up(rank, 2);
+                src_tv.push_back(M2lAssembleTv{ops_.perm_lookup[tv], rank, h.src_row0[pos], vt_off[h.level][ref], u_off[h.level][ref]});
             }
             for (size_t pos = 0; pos < h.tgt_tv.size(); ++pos) {
                 const int tv = h.tgt_tv[pos];
@@ -527,7 +528,8 @@ int FmmTree::upload() {
             CHK(dupload(&d_src, src_tv));
             CHK(dupload(&d_tgt, tgt_tv));
             const M2lAssembleClass ac{d_src.p, d_tgt.p, static_cast<int32_t>(src_tv.size()), static_cast<int32_t>(tgt_tv.size()),
-                                      h.r_pad16, h.k_pad, max_rank};
+                                      h.r_pad16, h.k_pad, max_rank,
+                                      m2l_pairs_ ? m2l_ne_ : 0, m2l_no_, m2l_ne16_, m2l_npar_, ops_.p};
             static const bool host_fill = std::getenv("BBFMM_M2L_ASSEMBLE_HOST") != nullptr; // checker: the host fill of round 1
             if (host_fill) {
                 std::vector<double> hv, hu;
@@ -553,6 +555,7 @@ int FmmTree::upload() {
             }
         }
         CHK(dupload(&rt, h.row_dst));
+        CHK(dupload(&rt2, h.row_dst2));
         CHK(dupload(&ro, h.blk_t0));
         CHK(dupload(&ce, h.cells));
         CHK(dalloc(&cs, h.cslot.size()));
@@ -561,6 +564,7 @@ int FmmTree::upload() {
         c.vt_all = vt.p;
         c.u_all = ua.p;
         c.row_dst = rt.p;
+        c.row_dst2 = rt2.p;
         c.blk_t0 = ro.p;
         c.cells = ce.p;
         c.cslot = cs.p;
@@ -602,6 +606,10 @@ int FmmTree::ensure_rhs_capacity(int k) {
     CHK(dalloc(&d_w_sorted_, static_cast<size_t>(k) * N));
     CHK(dalloc(&d_M_, coef, true));
     CHK(dalloc(&d_L_, coef, true));
+    if (m2l_pairs_) { // zeroed once: the pad columns are never written
+        dfree(&d_Mp_);
+        CHK(dalloc(&d_Mp_, static_cast<size_t>(k) * C * m2l_npar_, true));
+    }
     if (shared_basis_) {
         dfree(&d_Mc_);
         dfree(&d_Lc_);
@@ -907,7 +915,13 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     // a plan runs stage 1 on compact tiles of the sources its targets need, stage 2 on the tiles that
     // hold a cell with targets, P2L / L2L on the cells with targets (cells_with_targets, bbfmm.rs:468-480)
     const int m2l_len = shared_basis_ ? basis_pad_ : cheb_.n_pad;
-    const double *m_in = shared_basis_ ? d_Mc_.p : d_M_.p;
+    const double *m_in = shared_basis_ ? d_Mc_.p : m2l_pairs_ ? d_Mp_.p : d_M_.p;
+    const int s1_len = m2l_pairs_ ? m2l_npar_ : m2l_len, s1_ne16 = m2l_pairs_ ? m2l_ne16_ : 0; // stage 1's contraction
+    if (m2l_pairs_ && !m2l_batches_.empty()) { // the multipoles in the parity basis, once per matvec (part of stage 1's time)
+        phase_begin();
+        launch_m2l_parity(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_ne16_, m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(k) * C, stream_);
+        phase_end(kPhM2L1);
+    }
     double *l_out = shared_basis_ ? d_Lc_.p : d_L_.p;
     if (shared_basis_) { // coordinates of every multipole in its level's basis; stage 2 leaves untouched tiles at 0
         phase_begin();
@@ -920,7 +934,7 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     const int nb = static_cast<int>(m2l_batches_.size());
     for (int k0 = 0; k0 < k; k0 += m2l_rhs_chunk_) {
         const int kb = std::min(m2l_rhs_chunk_, k - k0);
-        const double *m_chunk = m_in + static_cast<size_t>(k0) * C * m2l_len;
+        const double *m_chunk = m_in + static_cast<size_t>(k0) * C * s1_len;
         double *l_chunk = l_out + static_cast<size_t>(k0) * C * m2l_len;
         for (int b = 0; b < nb; ++b) {
             const M2lBatch &mb = m2l_batches_[static_cast<size_t>(b)];
@@ -933,13 +947,13 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
                                          m2l_zero_ptr_[static_cast<size_t>(b) + 1] - m2l_zero_ptr_[static_cast<size_t>(b)], kb, d_cbuf_.p,
                                          cbuf_batch_len_, stream_);
             if (dp) { // whole-operator tiles, then the tiles of single column blocks (sources in the halo of the target set)
-                launch_m2l_stage1(d_m2l_classes_.p, dp->d_tiles1.p + t1_first, dp->d_tile_idx.p, t1_count, m2l_len, m2l_slot_t_, kb,
-                                  C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_);
+                launch_m2l_stage1(d_m2l_classes_.p, dp->d_tiles1.p + t1_first, dp->d_tile_idx.p, t1_count, s1_len, m2l_slot_t_, kb,
+                                  C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16);
                 launch_m2l_stage1(d_m2l_classes_.p, dp->d_tiles1.p + dp->batch_t1[4 * b + 2], dp->d_tile_idx.p, dp->batch_t1[4 * b + 3],
-                                  m2l_len, m2l_slot_t_, kb, C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, true, m2l_max_blocks_);
+                                  s1_len, m2l_slot_t_, kb, C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, true, m2l_max_blocks_, s1_ne16);
             } else
-                launch_m2l_stage1(d_m2l_classes_.p, d_m2l_tiles1_.p + t1_first, d_tile_idx1_.p, t1_count, m2l_len, m2l_slot_t_, kb, C,
-                                  m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_);
+                launch_m2l_stage1(d_m2l_classes_.p, d_m2l_tiles1_.p + t1_first, d_tile_idx1_.p, t1_count, s1_len, m2l_slot_t_, kb, C,
+                                  m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16);
             phase_end(kPhM2L1);
             phase_begin();
             if (dp)

@@ -42,6 +42,10 @@ struct HostM2lClass {
     std::vector<int32_t> row_tpos, row_off, row_dst, blk_t0, cells;
     std::vector<int32_t, DefaultInitAllocator<int32_t>> cslot; // cells x n_t, filled by parallel loops
     std::vector<int32_t> src_row0, src_row1; // stacked rows [row0, row1) of each source-side transfer vector
+    // x-reflected pairs (FmmTree::m2l_pairs_): the rows of a pair (t, Rt) belong to t and carry a second destination
+    // for Rt, which owns no rows of its own (its src_row0 / src_row1 repeat those of t)
+    std::vector<int32_t> row_tpos2, row_off2, row_dst2; // as row_tpos / row_off / row_dst for the difference a - b; -1: none
+    std::vector<int32_t> src_pair;                      // per source position: partner's position (first of a pair), -1 (single), -2 (second of a pair)
     std::vector<int64_t> cbase;
 };
 
@@ -237,6 +241,11 @@ class FmmTree {
         *n_cells = 0;
         for (const HostM2lClass &v : m2l_variants_) *n_cells += static_cast<int64_t>(v.cells.size());
     }
+    // Test hook: pairs and singles of every stage-1 operator.  Per operator with cells: level, octant, kind (0: class,
+    // 1: boundary variant or group operator), number of entries; per entry: 1 (a pair t, Rt; t is listed) or 0 (a
+    // single), then the d components of t.
+    void debug_m2l_pairs(std::vector<int32_t> *out) const;
+    bool m2l_pairs() const { return m2l_pairs_; }
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
     // M, L: n_cells x n (cell-major, one rhs).  L is accumulated into.
     int debug_apply_m2l_tables_host(const double *M, double *L) const;
@@ -328,6 +337,18 @@ class FmmTree {
     std::vector<M2lTileDesc> m2l_tiles2_h_; // stage-2 launch list: m2l_tiles_h_ with the tail of every batch split
     int m2l_slot_t_ = 1; // most transfer vectors any stage-1 column block touches
     int m2l_max_blocks_ = 1; // most stage-1 column blocks any class has (how far a small launch may split the walk)
+    // Stage 1 in the parity basis of the reflection R of axis 0: one product serves t and Rt.
+    // Nodes m < m2l_ne_ represent the pairs {m, rho(m)}; the contraction runs over [M_e | pad | M_o | pad], m2l_npar_ values.
+    int m2l_s1_block_ = kM2lS1Block;     // stacked rows per stage-1 column block: kM2lS1Block, or kM2lS1BlockPairs with m2l_pairs_
+    bool m2l_pairs_ = false;             // BBFMM_M2L_S1_PAIRS (read per handle), compressed operators, no shared basis, d >= 2
+    int m2l_ne_ = 0, m2l_no_ = 0;        // even / odd representatives: ceil(p/2) p^(d-1), floor(p/2) p^(d-1)
+    int m2l_ne16_ = 0, m2l_npar_ = 0;    // round_up(m2l_ne_, 16), + round_up(m2l_no_, 16)
+    std::vector<int32_t> m2l_partner_;   // per transfer vector: Rt when the pair identity was verified, else -1
+    int m2l_rho(int m) const { // reflection of node m along axis 0 (the slowest digit)
+        const int p1 = ops_.n / ops_.p;
+        return m + (ops_.p - 1 - 2 * (m / p1)) * p1;
+    }
+    DevBuf<double> d_Mp_;                // k x C x m2l_npar_: the multipoles in the parity basis (pads stay zero)
     // partition
     int part_rank_ = 0, part_world_ = 1;
     std::vector<int64_t> part_rows_, part_bounds_;

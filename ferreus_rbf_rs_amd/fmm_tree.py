@@ -565,6 +565,23 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_m2l_variants(self._h, ctypes.byref(nv), ctypes.byref(nc)))
         return nv.value, nc.value
 
+    def debug_m2l_pairs(self):
+        """(pairs_on, operators): per stage-1 operator a dict with level, octant, kind (0: class, 1: boundary variant
+        or group operator), pairs (the vectors t whose product also serves Rt) and singles, as tuples of components."""
+        n, on = ctypes.c_int64(), ctypes.c_int32()
+        self._raise(self._lib.bbfmm_debug_m2l_pairs(self._h, None, 0, ctypes.byref(n), ctypes.byref(on)))
+        buf = np.zeros(max(n.value, 1), dtype=np.int32)
+        self._raise(self._lib.bbfmm_debug_m2l_pairs(self._h, buf.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(on)))
+        d, ops, i = self.dim, [], 0
+        while i < n.value:
+            level, octant, kind, ne = (int(v) for v in buf[i:i + 4])
+            ent = buf[i + 4:i + 4 + ne * (d + 1)].reshape(ne, d + 1)
+            ops.append({"level": level, "octant": octant, "kind": kind,
+                        "pairs": [tuple(int(x) for x in e[1:]) for e in ent if e[0] == 1],
+                        "singles": [tuple(int(x) for x in e[1:]) for e in ent if e[0] == 0]})
+            i += 4 + ne * (d + 1)
+        return bool(on.value), ops
+
     def debug_get_coefficients(self, which: str, k: int) -> np.ndarray:
         s = self.stats()
         out = np.zeros((k, s.n_cells, s.n_nodes))
