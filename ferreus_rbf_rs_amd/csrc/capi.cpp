@@ -1208,6 +1208,24 @@ int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int6
     return BBFMM_OK;
 }
 
+// The same for the stage-2 operators (FmmTree::debug_m2l_pairs_stage2).
+int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on) {
+    if (!h || !n_out) return BBFMM_BAD_ARGUMENT;
+    std::vector<int32_t> v;
+    h->tree.debug_m2l_pairs_stage2(&v);
+    *n_out = static_cast<int64_t>(v.size());
+    if (pairs_on) *pairs_on = h->tree.m2l_pairs_stage2() ? 1 : 0;
+    if (out) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap, *n_out), out);
+    return BBFMM_OK;
+}
+
+// Debug only: parts into which the handle's most recent parity-basis stage-2 launch split the contraction (0: no launch yet).
+int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit) {
+    if (!h || !ksplit) return BBFMM_BAD_ARGUMENT;
+    *ksplit = h->tree.debug_m2l_s2_last_ksplit();
+    return BBFMM_OK;
+}
+
 int bbfmm_debug_get_coefficients(bbfmm_handle *h, char which, int32_t k, double *out) {
     GUARD(h) return h->tree.debug_get_coefficients(which, k, out);
     END_GUARD(h)

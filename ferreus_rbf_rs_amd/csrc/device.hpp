@@ -54,8 +54,11 @@ struct M2lClass {
     int32_t r_pad16;         // n_rows rounded up to a multiple of kM2lS1Block
     int32_t n_t;             // number of transfer vectors of this class (189 in 3-D)
     // stage 2 (target side): L_B[i] = sum_k UAllT[k][i] * ccat_B[k]
-    const double *u_all;     // k_pad x n_pad
+    const double *u_all;     // k_pad x n_pad; in the parity basis of stage 2 (k_pad - kp) x n_par, [U_e | pad | U_o | pad]
     int32_t k_pad;           // slot length of a target of this class (multiple of 16)
+    int32_t kp;              // parity-basis stage 2: the slot is [A | B | S] with the pairs' leaders in A and their partners
+                             // in B (kp values each, a multiple of 16), the singles in S; operator row r < kp contracts
+                             // slot[r] +- slot[kp + r], row r >= kp contracts slot[kp + r].  0: the plain layout
     // cells of this class at this level
     const int32_t *cells;    // cell indices
     int32_t n_cells;
@@ -118,6 +121,24 @@ void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne
 void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
                        const uint16_t *qlist, double *L, hipStream_t s, bool allow_ksplit = true);
+// Stage 2 in the parity basis of the x reflection: the operators are [U_e | pad | U_o | pad] (M2lClass::kp), Lp gets n_par =
+// 16 (ce ga + co gb) values per cell and right-hand side: ce chunks of ga column groups for the even part, then co chunks
+// of gb groups for the odd part (m2l_s2_pairs_plan chooses them for ne16 / 16 and no16 / 16 groups of real columns).
+struct M2lS2PairsPlan {
+    int ga, gb, ce, co;
+    int ne16() const { return 16 * ga * ce; }
+    int n_par() const { return 16 * (ga * ce + gb * co); }
+};
+M2lS2PairsPlan m2l_s2_pairs_plan(int groups_even, int groups_odd);
+// Returns false (and launches nothing) when the plan's widths have no kernel instance.  *ksplit_out (may be NULL): the parts
+// into which the launch split the contraction.
+bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                             const M2lS2PairsPlan &plan, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
+                             const uint16_t *qlist, double *Lp, hipStream_t s, bool allow_ksplit = true, int *ksplit_out = nullptr);
+// L[row] from Lp[row] = [L_e | pad | L_o | pad]: L[j] = L_e[j] + L_o[j], L[rho j] = L_e[j] - L_o[j] (centre plane: L_e[j]);
+// writes all n_pad values of every row (the padding as zeros).
+void launch_m2l_unparity(const double *Lp, int n_par, int ne16, double *L, int n, int n_pad, int n_e, int n_o, int p, int64_t rows,
+                         hipStream_t s);
 // Zeroes the slot segments of absent V pairs of a batch: segs = (slot / 2, length / 2) pairs, K buffers of cbuf_len.
 void launch_m2l_zero_segments(const int32_t *segs, int64_t n_segs, int K, double *cbuf, int64_t cbuf_len, hipStream_t s);
 // shared-basis extension: per-cell change of basis (OUT[cell] = IN[cell] * OP_level), setup-time dense product
@@ -138,6 +159,9 @@ struct M2lAssembleClass {
     const M2lAssembleTv *src, *tgt; // device arrays
     int32_t n_src, n_tgt, r_pad16, k_pad, max_rank;
     int32_t n_e, n_o, ne16, n_par, p; // parity basis (n_e > 0): src lists the transfer vectors that own rows
+    // parity basis of stage 2 (u_npar > 0): tgt lists the transfer vectors that own operator rows (row = operator row),
+    // u_all is u_rows x u_npar with the odd part from column u_ne16; u_ne / u_no as n_e / n_o
+    int32_t u_npar, u_ne16, u_rows, u_ne, u_no;
 };
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s);

@@ -544,6 +544,31 @@ void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const 
                            slot_t, tile_idx, s);
 }
 
+// Parts of stage 2's contraction for a launch of `wgs` workgroups (the rule of launch_m2l_stage2's comment, shared by the
+// node-basis and the parity-basis launch): 1 when the launch fills the chip or the handle is deterministic (the parts add
+// atomically), else the cheapest of 1..16 by ceil(workgroups * parts / CUs) * (0.05 + 1 / parts).  BBFMM_M2L_S2_KSPLIT overrides.
+static int m2l_s2_ksplit(int64_t wgs, bool allow_ksplit) {
+    static const int ks_env = [] {
+        const int v = env_int("BBFMM_M2L_S2_KSPLIT", 0);
+        return v >= 1 && v <= 32 ? v : 0;
+    }();
+    if (!allow_ksplit) return 1;
+    if (ks_env > 0) return ks_env;
+    const int n_cu = device_cu_count();
+    int ksplit = 1;
+    if (wgs * 2 <= static_cast<int64_t>(kM2lS2KsplitFill) * n_cu) { // (launches of at most two workgroups per CU)
+        double best = 1e300;
+        for (int ks = 1; ks <= 16; ++ks) {
+            const double cost = std::ceil(static_cast<double>(wgs * ks) / n_cu) * (0.05 + 1.0 / ks);
+            if (cost < best - 1e-12) {
+                best = cost;
+                ksplit = ks;
+            }
+        }
+    }
+    return ksplit;
+}
+
 // Stage 2: the output nodes (n_pad, in groups of 16; n_pad is a multiple of 32) in column chunks.
 void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int K, int64_t C, const double *cbuf, int64_t cbuf_len, const uint16_t *qlist,
@@ -566,27 +591,260 @@ void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const 
     // the other (two resident ones share its matrix pipe), a part costs a fixed 4-5 % of a whole chain plus its share of it,
     // so the launch takes ceil(workgroups * parts / CUs) * (0.05 + 1 / parts) chains: 585 cells (32 workgroups) 16 -> 8 parts,
     // 0.105 -> 0.085 ms; 4,681 cells (158 workgroups) 4 -> 3 parts, 0.419 -> 0.368 ms (5 parts: 0.462, 8: 0.411, 2: 0.511).
-    static const int ks_env = [] {
-        const int v = env_int("BBFMM_M2L_S2_KSPLIT", 0);
-        return v >= 1 && v <= 32 ? v : 0;
-    }();
-    int ksplit = allow_ksplit ? ks_env : 1; // (the parts add atomically: not for BBFMM_FLAG_DETERMINISTIC handles)
-    if (ksplit == 0) {
-        const int n_cu = device_cu_count();
-        const int64_t wgs = static_cast<int64_t>(n_tiles) * z * K;
-        ksplit = 1;
-        if (wgs * 2 <= static_cast<int64_t>(kM2lS2KsplitFill) * n_cu) { // (launches of at most two workgroups per CU, as before)
-            double best = 1e300;
-            for (int ks = 1; ks <= 16; ++ks) {
-                const double cost = std::ceil(static_cast<double>(wgs * ks) / n_cu) * (0.05 + 1.0 / ks);
-                if (cost < best - 1e-12) {
-                    best = cost;
-                    ksplit = ks;
+    const int ksplit = m2l_s2_ksplit(static_cast<int64_t>(n_tiles) * z * K, allow_ksplit);
+    m2l_dispatch_chunks<2>(n_pad / 16, classes, tiles, n_tiles, n_pad, z, K, C, cbuf, cbuf_len, L, 0, qlist, ksplit > 1 ? ksplit : 0, tile_idx, s);
+}
+
+// ------------------------------------------------------------------ stage 2 in the parity basis of the x reflection
+// The slot of a target is [A | B | S] (M2lClass::kp): for a pair (t, Rt) the leader's segment x lies in A and the partner's
+// segment y at the same offset in B; the operator is [U_e | pad | U_o | pad] with one set of rows per pair.  A workgroup
+// takes a chunk of column groups that lies wholly in the even or wholly in the odd half.  Step q of the operator's rows
+// brings the 16 slot values at kp + 16 q by DMA and, for a pair step (16 q < kp), the 16 at 16 q into a second IN tile;
+// every lane forms x + y (even half) or x - y (odd half) from LDS before the MFMAs.  A singles step multiplies the one
+// tile as m2l_gemm_k4 does.  The operator image, the IN tile layout, the MFMA loop and the epilogue are those of
+// m2l_gemm_k4's stage 2 (its comments apply); OUT is Lp with n_par values per cell.
+template <int NG16>
+__device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2lTileDesc &tile, int n_par, int g16, bool odd,
+                                                  int zk, int ksplit, int64_t C, const double *__restrict__ in, int64_t in_len,
+                                                  double *__restrict__ out, const uint16_t *__restrict__ qlist,
+                                                  const int32_t *__restrict__ tile_idx, double *lds) {
+    const int kr = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int ld = n_par;
+    const int q_lo = tile.q_count * zk / ksplit;
+    const int nq = tile.q_count * (zk + 1) / ksplit - q_lo;
+    const uint16_t *ql = qlist + tile.q_first + q_lo;
+    const int kp = cls.kp, kp16 = kp >> 4;
+    const double *opbase = cls.u_all + 16 * g16;
+
+    constexpr int OP_CHUNKS = 2 * NG16;
+    constexpr int NCH = (OP_CHUNKS + 7) / 8;
+    constexpr int OP_DOUBLES = OP_CHUNKS * 128;
+    constexpr int BUF = OP_DOUBLES + 4096; // the operator tile, the x tile (pair steps), the y / singles tile
+    constexpr int NP = NG16 / 2, NS = NG16 & 1;
+    unsigned voff[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = wave + 8 * i;
+        if (c < 4 * NP) {
+            const int e = c / (NP > 0 ? NP : 1), pr = c - e * NP, k = lane >> 4, p = lane & 15;
+            voff[i] = (unsigned)(((4 * k + e) * ld + 32 * pr + 2 * p) * 8);
+        } else {
+            const int e = 2 * (c - 4 * NP) + (lane >> 5), r = lane & 31, k = r >> 3, pair = r & 7;
+            voff[i] = (unsigned)(((4 * k + e) * ld + 32 * NP + 2 * pair) * 8);
+        }
+    }
+    auto cell_p = [&](int pos) {
+        const int q = pos < tile.count ? pos : 0;
+        return tile.pad ? tile_idx[tile.first + q] : tile.first + q;
+    };
+    const double *cptr[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int tg = 2 * h + (lane >> 5), eh = (lane >> 4) & 1, k = (lane >> 2) & 3, j = lane & 3;
+        const int p = cell_p(wave * 16 + 4 * tg + j);
+        cptr[h] = in + (int64_t)kr * in_len + cls.cbase[p] + 4 * k + 2 * eh;
+    }
+    const unsigned lds0 = lds_offset(lds);
+    const int64_t qstride = (int64_t)16 * ld;
+    auto stage = [&](int qi, int buf) { // returns whether the step is a pair step (wave-uniform)
+        const int q = (int)uniform_u32(ql[qi]);
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+            if (wave + 8 * i < OP_CHUNKS)
+                dma16s(opbase + q * qstride, voff[i], lds0 + (unsigned)(buf * BUF + (wave + 8 * i) * 128) * 8u);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            dma16(cptr[h] + kp + 16 * q, lds0 + (unsigned)(buf * BUF + OP_DOUBLES + 2048 + (2 * wave + h) * 128) * 8u);
+        if (q < kp16) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                dma16(cptr[h] + 16 * q, lds0 + (unsigned)(buf * BUF + OP_DOUBLES + (2 * wave + h) * 128) * 8u);
+        }
+        return q < kp16;
+    };
+
+    double acc[4][NG16];
+#pragma unroll
+    for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+        for (int g = 0; g < NG16; ++g) acc[tg][g] = 0.0;
+
+    const int bk = lane >> 4, bj = lane & 3;
+    const bool wave_live = wave * 16 < tile.count;
+    const int di = lane >> 4, db = (lane >> 2) & 3, dj = lane & 3;
+    const double sgn = odd ? -1.0 : 1.0;
+    bool pair_cur = false;
+    if (nq > 0) pair_cur = stage(0, 0);
+    wait_dma_and_barrier();
+    for (int sidx = 0; sidx < nq; ++sidx) {
+        const double *op = lds + (sidx & 1) * BUF + lane;
+        const double2 *op2 = reinterpret_cast<const double2 *>(lds + (sidx & 1) * BUF) + lane;
+        const double *cx = lds + (sidx & 1) * BUF + OP_DOUBLES + wave * 256 + (bk * 4 + bj) * 2;
+        bool pair_next = false;
+        if (sidx + 1 < nq) pair_next = stage(sidx + 1, (sidx + 1) & 1); // streams in under the MFMAs below
+        if (wave_live) {
+            double bq[4][4];
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                for (int eh = 0; eh < 2; ++eh) {
+                    const double2 y = *reinterpret_cast<const double2 *>(cx + 2048 + ((tg * 2 + eh) * 16) * 2);
+                    bq[tg][2 * eh] = y.x;
+                    bq[tg][2 * eh + 1] = y.y;
+                }
+            if (pair_cur) { // x + y for the even half, x - y for the odd half (sgn * y is exact)
+#pragma unroll
+                for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                    for (int eh = 0; eh < 2; ++eh) {
+                        const double2 x = *reinterpret_cast<const double2 *>(cx + ((tg * 2 + eh) * 16) * 2);
+                        bq[tg][2 * eh] = x.x + sgn * bq[tg][2 * eh];
+                        bq[tg][2 * eh + 1] = x.y + sgn * bq[tg][2 * eh + 1];
+                    }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                for (int pr = 0; pr < NP; ++pr) {
+                    const double2 a = op2[(e * NP + pr) * 64];
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg) {
+                        acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, bq[tg][e], acc[tg][2 * pr], 0, 0, 0);
+                        acc[tg][2 * pr + 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, bq[tg][e], acc[tg][2 * pr + 1], 0, 0, 0);
+                    }
+                }
+                if (NS) {
+                    const double a = op[4 * NP * 128 + e * 64];
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg)
+                        acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bq[tg][e], acc[tg][NG16 - 1], 0, 0, 0);
                 }
             }
         }
+        pair_cur = pair_next;
+        wait_dma_and_barrier();
     }
-    m2l_dispatch_chunks<2>(n_pad / 16, classes, tiles, n_tiles, n_pad, z, K, C, cbuf, cbuf_len, L, 0, qlist, ksplit > 1 ? ksplit : 0, tile_idx, s);
+    const int col0 = 16 * g16;
+#pragma unroll
+    for (int tg = 0; tg < 4; ++tg) {
+        const int tp = wave * 16 + 4 * tg + dj;
+        if (tp < tile.count) {
+            const int cell = cls.cells[cell_p(tp)];
+            double *Lc = out + ((int64_t)kr * C + cell) * n_par + col0;
+            if (ksplit > 1) { // one of several parts of the contraction
+#pragma unroll
+                for (int pr = 0; pr < NP; ++pr) {
+                    unsafeAtomicAdd(Lc + 32 * pr + 2 * (4 * db + di), acc[tg][2 * pr]);
+                    unsafeAtomicAdd(Lc + 32 * pr + 2 * (4 * db + di) + 1, acc[tg][2 * pr + 1]);
+                }
+                if (NS) unsafeAtomicAdd(Lc + 32 * NP + 4 * db + di, acc[tg][NG16 - 1]);
+            } else {
+#pragma unroll
+                for (int pr = 0; pr < NP; ++pr)
+                    *reinterpret_cast<double2 *>(Lc + 32 * pr + 2 * (4 * db + di)) = make_double2(acc[tg][2 * pr], acc[tg][2 * pr + 1]);
+                if (NS) Lc[32 * NP + 4 * db + di] = acc[tg][NG16 - 1];
+            }
+        }
+    }
+}
+
+// One launch for both halves: blockIdx.z = part of the contraction * (ce + co) + chunk; the first ce chunks are GA groups
+// of the even half, the other co chunks GB groups of the odd half (two launches of one width each were measured slower
+// than one launch in the node basis: the halves of a tile read the same slot contents at about the same time).
+template <int GA, int GB>
+__global__ __launch_bounds__(512, 1) void m2l_s2_pairs_kernel(const M2lClass *__restrict__ classes, const M2lTileDesc *__restrict__ tiles,
+                                                              int n_par, int ce, int co, int ksplit, int64_t C,
+                                                              const double *__restrict__ in, int64_t in_len, double *__restrict__ out,
+                                                              const uint16_t *__restrict__ qlist, const int32_t *__restrict__ tile_idx) {
+    extern __shared__ double lds[];
+    const M2lTileDesc tile = tiles[blockIdx.x];
+    const M2lClass cls = classes[tile.level_class];
+    const int zcols = ce + co;
+    const int zk = (int)blockIdx.z / zcols, zc = (int)blockIdx.z - zk * zcols;
+    if (zc < ce) m2l_s2_pairs_body<GA>(cls, tile, n_par, zc * GA, false, zk, ksplit, C, in, in_len, out, qlist, tile_idx, lds);
+    else m2l_s2_pairs_body<GB>(cls, tile, n_par, ce * GA + (zc - ce) * GB, true, zk, ksplit, C, in, in_len, out, qlist, tile_idx, lds);
+}
+
+// The chunk widths the kernel is instantiated for, (even, odd): 3-D order 7 has 13 + 10 groups, order 9 26 + 21, order 5
+// 5 + 4; the equal widths serve the other orders.  A half is padded to a whole number of chunks (zero operator columns).
+// The planner's table and the launcher's dispatch are both generated from this list.
+#define M2L_S2_PAIR_WIDTHS(X) X(13, 10) X(13, 11) X(8, 8) X(7, 7) X(5, 4) X(4, 4) X(2, 2) X(1, 1)
+#define M2L_S2_WIDTH_ENTRY(A, B) {A, B},
+static constexpr int kM2lS2PairWidths[][2] = {M2L_S2_PAIR_WIDTHS(M2L_S2_WIDTH_ENTRY)};
+#undef M2L_S2_WIDTH_ENTRY
+
+// Fewest executed column groups, a chunk counted two groups dearer than its width (its share of the IN tiles and barriers).
+M2lS2PairsPlan m2l_s2_pairs_plan(int groups_even, int groups_odd) {
+    M2lS2PairsPlan best{1, 1, std::max(groups_even, 1), std::max(groups_odd, 1)};
+    int best_cost = 1 << 30;
+    for (const auto &w : kM2lS2PairWidths) {
+        const int ce = std::max(1, (groups_even + w[0] - 1) / w[0]), co = std::max(1, (groups_odd + w[1] - 1) / w[1]);
+        const int cost = ce * (w[0] + 2) + co * (w[1] + 2);
+        if (cost < best_cost) {
+            best_cost = cost;
+            best = M2lS2PairsPlan{w[0], w[1], ce, co};
+        }
+    }
+    return best;
+}
+
+template <int GA, int GB>
+static void m2l_s2_pairs_launch(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                                const M2lS2PairsPlan &plan, int ksplit, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
+                                const uint16_t *qlist, double *Lp, hipStream_t s) {
+    const size_t lds = 2 * sizeof(double) * (size_t)(2 * (GA > GB ? GA : GB) * 128 + 4096);
+    static std::atomic<uint64_t> attr_set[4] = {{0}, {0}, {0}, {0}};
+    (void)allow_large_dynamic_lds(reinterpret_cast<const void *>(&m2l_s2_pairs_kernel<GA, GB>), lds, attr_set);
+    hipLaunchKernelGGL((m2l_s2_pairs_kernel<GA, GB>), dim3(n_tiles, K, (plan.ce + plan.co) * ksplit), dim3(512), lds, s, classes, tiles,
+                       plan.n_par(), plan.ce, plan.co, ksplit, C, cbuf, cbuf_len, Lp, qlist, tile_idx);
+}
+
+bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                             const M2lS2PairsPlan &plan, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
+                             const uint16_t *qlist, double *Lp, hipStream_t s, bool allow_ksplit, int *ksplit_out) {
+    if (n_tiles == 0) return true;
+    // the contraction split of launch_m2l_stage2, on this launch's workgroups per tile (the parts add to the zeroed Lp)
+    const int ksplit = m2l_s2_ksplit(static_cast<int64_t>(n_tiles) * (plan.ce + plan.co) * K, allow_ksplit);
+    if (ksplit_out) *ksplit_out = ksplit;
+#define M2L_S2_DISPATCH(A, B)                                                                                            \
+    if (plan.ga == A && plan.gb == B) {                                                                                  \
+        m2l_s2_pairs_launch<A, B>(classes, tiles, tile_idx, n_tiles, plan, ksplit, K, C, cbuf, cbuf_len, qlist, Lp, s);  \
+        return true;                                                                                                     \
+    }
+    M2L_S2_PAIR_WIDTHS(M2L_S2_DISPATCH)
+#undef M2L_S2_DISPATCH
+    return false; // a plan that m2l_s2_pairs_plan did not make: no instance, nothing launched
+}
+
+// Lp = [L_e | pad | L_o | pad] back to the node order, one wave per row = (right-hand side, cell): L[j] = L_e[j] + L_o[j]
+// and L[rho j] = L_e[j] - L_o[j] for the representatives j < n_o, L[j] = L_e[j] on the centre plane; the padding of the
+// row is written as zeros, so L needs no clearing before.  Streaming, HBM bound.
+__global__ __launch_bounds__(256) void m2l_unparity_kernel(const double *__restrict__ Lp, int n_par, int ne16, double *__restrict__ L,
+                                                           int n, int n_pad, int n_e, int n_o, int p, int p1, int64_t rows) {
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double *src = Lp + row * n_par;
+    double *dst = L + row * n_pad;
+    for (int j = threadIdx.x & 63; j < n_e; j += 64) {
+        const double e = src[j];
+        if (j < n_o) {
+            const double o = src[ne16 + j];
+            dst[j] = e + o;
+            dst[j + (p - 1 - 2 * (j / p1)) * p1] = e - o;
+        } else {
+            dst[j] = e;
+        }
+    }
+    for (int j = n + (threadIdx.x & 63); j < n_pad; j += 64) dst[j] = 0.0;
+}
+
+void launch_m2l_unparity(const double *Lp, int n_par, int ne16, double *L, int n, int n_pad, int n_e, int n_o, int p, int64_t rows,
+                         hipStream_t s) {
+    if (rows <= 0) return;
+    const int p1 = n_e / ((p + 1) / 2);
+    hipLaunchKernelGGL(m2l_unparity_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, Lp, n_par, ne16, L, n, n_pad, n_e,
+                       n_o, p, p1, rows);
 }
 
 // The multipoles in the parity basis of the x reflection: row = (right-hand side, cell), Mp[row] = [M_e | pad | M_o | pad]
@@ -753,10 +1011,33 @@ __global__ __launch_bounds__(256) void assemble_u_kernel(M2lAssembleClass c, int
     u_all[static_cast<int64_t>(tv.row + kk) * n_pad + i] = ops[tv.u_off + static_cast<int64_t>(kk) * n + invperm[static_cast<int64_t>(tv.perm) * n + i]];
 }
 
+// The same in the parity basis of stage 2: one thread per (rank index kk, representative i < u_ne) of a transfer vector
+// that owns operator rows writes U_e[row + kk][i] and, off the centre plane, U_o[row + kk][i]; the factor 1/2 is exact.
+__global__ __launch_bounds__(256) void assemble_u_parity_kernel(M2lAssembleClass c, int n, const double *__restrict__ ops,
+                                                                const int32_t *__restrict__ invperm, double *__restrict__ u_all) {
+    const M2lAssembleTv tv = c.tgt[blockIdx.y];
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(tv.rank) * c.u_ne) return;
+    const int kk = static_cast<int>(t / c.u_ne), i = static_cast<int>(t % c.u_ne);
+    const int p1 = n / c.p;
+    const int ri = i + (c.p - 1 - 2 * (i / p1)) * p1;
+    const int32_t *inv = invperm + static_cast<int64_t>(tv.perm) * n;
+    const double *ucol = ops + tv.u_off + static_cast<int64_t>(kk) * n;
+    double *dst = u_all + static_cast<int64_t>(tv.row + kk) * c.u_npar;
+    const double a = ucol[inv[i]];
+    if (i >= c.u_no) {
+        dst[i] = a;
+    } else {
+        const double b = ucol[inv[ri]];
+        dst[i] = 0.5 * (a + b);
+        dst[c.u_ne16 + i] = 0.5 * (a - b);
+    }
+}
+
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s) {
     (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(c.n_e > 0 ? c.n_par : n_pad) * c.r_pad16 * sizeof(double), s);
-    (void)hipMemsetAsync(u_all, 0, static_cast<size_t>(c.k_pad) * n_pad * sizeof(double), s);
+    (void)hipMemsetAsync(u_all, 0, (c.u_npar > 0 ? static_cast<size_t>(c.u_rows) * c.u_npar : static_cast<size_t>(c.k_pad) * n_pad) * sizeof(double), s);
     if (c.n_src > 0 && c.n_e > 0)
         hipLaunchKernelGGL(assemble_vt_parity_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * c.n_e + 255) / 256)), dim3(256),
                            0, s, c, n, ops, invperm, vt_all);
@@ -764,7 +1045,10 @@ void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compr
         // (one thread per entry, no grid-stride loop: the exact block count, not grid_for's capped one)
         hipLaunchKernelGGL(assemble_vt_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * n + 255) / 256)), dim3(256), 0, s, c, n, n_pad,
                            compressed ? 1 : 0, ops, invperm, vt_all);
-    if (c.n_tgt > 0 && c.max_rank > 0)
+    if (c.n_tgt > 0 && c.max_rank > 0 && c.u_npar > 0)
+        hipLaunchKernelGGL(assemble_u_parity_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.max_rank) * c.u_ne + 255) / 256), c.n_tgt),
+                           dim3(256), 0, s, c, n, ops, invperm, u_all);
+    else if (c.n_tgt > 0 && c.max_rank > 0)
         hipLaunchKernelGGL(assemble_u_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.max_rank) * n + 255) / 256), c.n_tgt), dim3(256), 0, s, c,
                            n, n_pad, ops, invperm, u_all);
 }

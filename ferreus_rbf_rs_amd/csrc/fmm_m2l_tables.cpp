@@ -4,12 +4,13 @@
 
 namespace bbfmm {
 
-// Stacked operators of one (level, class): VtAll (n_pad x r_pad16) and UAll (k_pad x n_pad).
+// Stacked operators of one (level, class): VtAll (n_pad x r_pad16) and UAll (k_pad x n_pad; in the parity basis of stage 2
+// (k_pad - kp) x n_par).
 void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, std::vector<double> *vt_all,
                                        std::vector<double> *u_all) const {
     const int n_pad = round_up(ops_.n, 32);
     vt_all->resize(static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : n_pad) * hc.r_pad16);
-    u_all->resize(static_cast<size_t>(hc.k_pad) * n_pad);
+    u_all->resize(m2l_pairs2_ ? static_cast<size_t>(hc.k_pad - hc.kp) * m2l_s2_plan_.n_par() : static_cast<size_t>(hc.k_pad) * n_pad);
     fill_m2l_operator_arrays(hc, vt_all->data(), u_all->data());
 }
 
@@ -24,7 +25,7 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
         });
     };
     zero(vt_all, static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : n_pad) * hc.r_pad16);
-    zero(u_all, static_cast<size_t>(hc.k_pad) * n_pad);
+    zero(u_all, m2l_pairs2_ ? static_cast<size_t>(hc.k_pad - hc.kp) * m2l_s2_plan_.n_par() : static_cast<size_t>(hc.k_pad) * n_pad);
     struct RowSrc {
         const M2lOperator *op;
         const int32_t *inv;
@@ -73,6 +74,32 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
                 }
             }
         });
+    }
+    // Parity basis of stage 2: operator row (leader: its slot offset; single: its slot offset - kp) holds U_e[kk][i] =
+    // (U_t[kk][i] + U_t[kk][rho i]) / 2 in columns [0, ne16) and U_o[kk][i] = (U_t[kk][i] - U_t[kk][rho i]) / 2 behind them
+    if (m2l_pairs2_) {
+        const int n_par = m2l_s2_plan_.n_par(), ne16 = m2l_s2_plan_.ne16();
+        parallel_for(static_cast<int64_t>(hc.tgt_tv.size()), 1, [&](int64_t pos) {
+            if (hc.tgt_pair[pos] == -2) return; // the partner shares the rows of the leader
+            const int tv = hc.tgt_tv[pos];
+            const M2lOperator &op = lops[ops_.ref_lookup[tv]];
+            const int32_t *inv = &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[tv]) * n];
+            const int row0 = hc.tgt_off[pos] - (hc.tgt_pair[pos] >= 0 ? 0 : hc.kp);
+            for (int kk = 0; kk < op.rank; ++kk) {
+                double *dst = u_all + static_cast<size_t>(row0 + kk) * n_par;
+                const double *ucol = &op.u[static_cast<size_t>(kk) * n];
+                for (int i = 0; i < m2l_ne_; ++i) {
+                    const double a = ucol[inv[i]], b = ucol[inv[m2l_rho(i)]];
+                    if (i >= m2l_no_) {
+                        dst[i] = a;
+                    } else {
+                        dst[i] = 0.5 * (a + b);
+                        dst[ne16 + i] = 0.5 * (a - b);
+                    }
+                }
+            }
+        });
+        return;
     }
     // L_B[i] += sum_kk U[invperm[i]][kk] * c[kk]   (bbfmm.rs:975-981 folded)
     parallel_for(static_cast<int64_t>(hc.tgt_tv.size()), 1, [&](int64_t pos) {
@@ -126,6 +153,10 @@ int FmmTree::build_m2l_tables() {
     {
         const char *e = std::getenv("BBFMM_M2L_S1_PAIRS"); // read per handle, like BBFMM_M2L_CBUF_MB
         m2l_pairs_ = !(e && std::atoi(e) == 0) && compressed && !shared_basis_ && d >= 2 && ops_.p >= 2;
+        // stage 2 pairs the slot segments of t and Rt on the same identity: UAll_Rt[kk][i] = U_ref[kk][invperm_Rt[i]] =
+        // U_ref[kk][invperm_t[rho i]] = UAll_t[kk][rho i]
+        const char *e2 = std::getenv("BBFMM_M2L_S2_PAIRS");
+        m2l_pairs2_ = !(e2 && std::atoi(e2) == 0) && compressed && !shared_basis_ && d >= 2 && ops_.p >= 2;
         m2l_partner_.assign(static_cast<size_t>(nvec), -1);
         m2l_s1_block_ = m2l_pairs_ ? kM2lS1BlockPairs : kM2lS1Block;
         const int p1 = n / ops_.p;
@@ -133,7 +164,8 @@ int FmmTree::build_m2l_tables() {
         m2l_no_ = ops_.p / 2 * p1;
         m2l_ne16_ = round_up(m2l_ne_, 16);
         m2l_npar_ = m2l_ne16_ + round_up(m2l_no_, 16);
-        for (int tv = 0; tv < nvec && m2l_pairs_; ++tv) {
+        m2l_s2_plan_ = m2l_s2_pairs_plan(m2l_ne16_ / 16, round_up(m2l_no_, 16) / 16);
+        for (int tv = 0; tv < nvec && (m2l_pairs_ || m2l_pairs2_); ++tv) {
             if (comp(tv, 0) == 0) continue;
             int rt = -1;
             for (int u = 0; u < nvec && rt < 0; ++u) {
@@ -175,27 +207,43 @@ int FmmTree::build_m2l_tables() {
                 src_list[o].push_back(tv);
             }
         }
-    // the source lists in stage-1 order: the pairs first (Rt directly behind t), then the singles
-    if (m2l_pairs_)
-        for (int o = 0; o < ncls; ++o) {
-            std::vector<int> ordered, singles;
-            std::vector<uint8_t> used(static_cast<size_t>(nvec), 0);
-            for (int tv : src_list[o]) {
-                const int rt = m2l_partner_[static_cast<size_t>(tv)];
-                if (used[static_cast<size_t>(tv)]) continue;
-                if (rt >= 0 && tpos_src[o][rt] >= 0 && m2l_partner_[static_cast<size_t>(rt)] == tv) {
-                    const int first = comp(tv, 0) > 0 ? tv : rt;
-                    ordered.push_back(first);
-                    ordered.push_back(first == tv ? rt : tv);
-                    used[static_cast<size_t>(tv)] = used[static_cast<size_t>(rt)] = 1;
-                } else {
-                    singles.push_back(tv);
-                }
+    // the source lists in stage-1 order: the pairs first (Rt directly behind t), then the singles; the target lists of
+    // stage 2 by the same rule
+    auto pairs_first = [&](std::vector<int> *list, std::vector<int> *tpos) {
+        std::vector<int> ordered, singles;
+        std::vector<uint8_t> used(static_cast<size_t>(nvec), 0);
+        for (int tv : *list) {
+            const int rt = m2l_partner_[static_cast<size_t>(tv)];
+            if (used[static_cast<size_t>(tv)]) continue;
+            if (rt >= 0 && (*tpos)[rt] >= 0 && m2l_partner_[static_cast<size_t>(rt)] == tv) {
+                const int first = comp(tv, 0) > 0 ? tv : rt;
+                ordered.push_back(first);
+                ordered.push_back(first == tv ? rt : tv);
+                used[static_cast<size_t>(tv)] = used[static_cast<size_t>(rt)] = 1;
+            } else {
+                singles.push_back(tv);
             }
-            ordered.insert(ordered.end(), singles.begin(), singles.end());
-            src_list[o] = ordered;
-            for (size_t i = 0; i < ordered.size(); ++i) tpos_src[o][ordered[i]] = static_cast<int>(i);
         }
+        ordered.insert(ordered.end(), singles.begin(), singles.end());
+        *list = ordered;
+        for (size_t i = 0; i < ordered.size(); ++i) (*tpos)[ordered[i]] = static_cast<int>(i);
+    };
+    for (int o = 0; o < ncls; ++o) {
+        if (m2l_pairs_) pairs_first(&src_list[o], &tpos_src[o]);
+        if (m2l_pairs2_) pairs_first(&tgt_list[o], &tpos_tgt[o]);
+    }
+    // per target position: the partner's position (leader of a pair), -1 (single), -2 (partner)
+    std::vector<std::vector<int32_t>> tgt_pair(ncls);
+    for (int o = 0; o < ncls; ++o) {
+        const std::vector<int> &tl = tgt_list[o];
+        tgt_pair[o].assign(tl.size(), -1);
+        for (size_t pos = 0; m2l_pairs2_ && pos + 1 < tl.size(); ++pos)
+            if (m2l_partner_[static_cast<size_t>(tl[pos])] == tl[pos + 1] && m2l_partner_[static_cast<size_t>(tl[pos + 1])] == tl[pos]) {
+                tgt_pair[o][pos] = static_cast<int32_t>(pos + 1);
+                tgt_pair[o][pos + 1] = -2;
+                ++pos;
+            }
+    }
     auto target_class = [&](int o, int tv) {
         int oc = 0;
         for (int a = 0; a < d; ++a) {
@@ -208,17 +256,34 @@ int FmmTree::build_m2l_tables() {
     std::vector<int32_t> pos_in_class(t.n_cells(), -1);
     int64_t bad_pairs = 0;
     // slot layout of a target of class o at `level`: one segment per admissible transfer vector
-    auto slot_layout = [&](int level, std::vector<std::vector<int>> *off_tgt, std::vector<int> *k_pad) {
+    // With the pairs of stage 2 the slot is [A | B | S]: the leaders' segments, padded to kp (a multiple of 16); their
+    // partners' at the same offsets behind them; the singles.  Step q of the pair region contracts the 16 values at 16 q
+    // and the 16 at kp + 16 q; a vector's rows stay contiguous, so stage 1 stores as before.
+    auto slot_layout = [&](int level, std::vector<std::vector<int>> *off_tgt, std::vector<int> *k_pad, std::vector<int> *kp_out = nullptr) {
         const auto &lops = ops_.m2l[level];
         off_tgt->assign(ncls, {});
         k_pad->assign(ncls, 0);
+        if (kp_out) kp_out->assign(ncls, 0);
         for (int o = 0; o < ncls; ++o) {
-            int off = 0;
-            for (int tv : tgt_list[o]) {
-                (*off_tgt)[o].push_back(off);
-                off += round_up(lops[ops_.ref_lookup[tv]].rank, 2); // 16-byte aligned segments
+            int lead = 0;
+            for (size_t pos = 0; pos < tgt_list[o].size(); ++pos)
+                if (tgt_pair[o][pos] >= 0) lead += round_up(lops[ops_.ref_lookup[tgt_list[o][pos]]].rank, 2);
+            const int kp = round_up(lead, 16);
+            int off = 0, off_s = 2 * kp;
+            for (size_t pos = 0; pos < tgt_list[o].size(); ++pos) {
+                const int seg = round_up(lops[ops_.ref_lookup[tgt_list[o][pos]]].rank, 2); // 16-byte aligned segments
+                if (tgt_pair[o][pos] >= 0) {
+                    (*off_tgt)[o].push_back(off);
+                } else if (tgt_pair[o][pos] == -2) {
+                    (*off_tgt)[o].push_back(kp + off);
+                    off += seg;
+                } else {
+                    (*off_tgt)[o].push_back(off_s);
+                    off_s += seg;
+                }
             }
-            (*k_pad)[o] = round_up(std::max(off, 16), 16);
+            (*k_pad)[o] = round_up(std::max(off_s, 16), 16);
+            if (kp_out) (*kp_out)[o] = kp;
         }
     };
     // ---- batches.  The slots of all targets (one per cell, sum_t r_t doubles: 37 KB at order 7) are what the two
@@ -288,8 +353,8 @@ int FmmTree::build_m2l_tables() {
         const auto &lops = ops_.m2l[level];
         auto rank_of = [&](int tv) { return lops[ops_.ref_lookup[tv]].rank; };
         std::vector<std::vector<int>> off_tgt;
-        std::vector<int> k_pad;
-        slot_layout(level, &off_tgt, &k_pad);
+        std::vector<int> k_pad, kp_cls;
+        slot_layout(level, &off_tgt, &k_pad, &kp_cls);
         const size_t first_class = m2l_host_.size();
         // Stage-1 row tables of a class-o operator stacked over the transfer vectors `tvs` (the whole admissible
         // list for the class itself, the present ones for a boundary variant): every transfer vector's rows
@@ -430,6 +495,8 @@ int FmmTree::build_m2l_tables() {
             hc.octant = o;
             hc.n_t = static_cast<int>(src_list[o].size());
             hc.k_pad = k_pad[o];
+            hc.kp = kp_cls[o];
+            hc.tgt_pair = tgt_pair[o];
             // stage 1 tall operator rows
             if (!stage1_rows(o, src_list[o], &hc)) return fail(BBFMM_BAD_ARGUMENT, "M2L slot too long for the packed row table");
             if (hc.cells.empty()) continue;
@@ -513,7 +580,7 @@ int FmmTree::build_m2l_tables() {
             }
         for (int o = 0; o < ncls; ++o) {
             const HostM2lClass &hc = m2l_host_[first_class + o];
-            const int nq = hc.k_pad / 16;
+            const int nq = (hc.k_pad - hc.kp) / 16; // steps of the operator's rows (a pair step serves both members)
             const int64_t n_tiles_cls = (static_cast<int64_t>(hc.cells.size()) + kM2lTile - 1) / kM2lTile;
             std::vector<std::vector<uint16_t>> tile_q(static_cast<size_t>(n_tiles_cls));
             parallel_for(n_tiles_cls, 4, [&](int64_t ti) {
@@ -527,7 +594,7 @@ int FmmTree::build_m2l_tables() {
                         const int tv = t.v_tidx[q];
                         const int pos = tpos_tgt[o][tv];
                         if (pos < 0) continue;
-                        const int a = off_tgt[o][pos], b = a + rank_of(tv);
+                        const int a = off_tgt[o][pos] - (off_tgt[o][pos] >= hc.kp ? hc.kp : 0), b = a + rank_of(tv); // operator rows
                         for (int sq = a / 16; sq <= (b - 1) / 16; ++sq) act[sq] = 1;
                     }
                 }
@@ -1089,6 +1156,29 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
             for (size_t pos = 0; pos < hc.cells.size(); ++pos) {
                 double *Lb = L + static_cast<size_t>(hc.cells[pos]) * n;
                 const double *cc = &cbuf[static_cast<size_t>(hc.cbase[pos])];
+                if (m2l_pairs2_) { // operator row r < kp: slot[r] + slot[kp + r] against U_e, their difference against U_o;
+                    // r >= kp: slot[kp + r] against both; then back to the node order
+                    const int n_par = m2l_s2_plan_.n_par(), ne16 = m2l_s2_plan_.ne16(), rows = hc.k_pad - hc.kp;
+                    std::vector<double> sm(static_cast<size_t>(rows)), df(static_cast<size_t>(rows));
+                    for (int r = 0; r < rows; ++r) {
+                        sm[static_cast<size_t>(r)] = r < hc.kp ? cc[r] + cc[hc.kp + r] : cc[hc.kp + r];
+                        df[static_cast<size_t>(r)] = r < hc.kp ? cc[r] - cc[hc.kp + r] : cc[hc.kp + r];
+                    }
+                    for (int i = 0; i < m2l_ne_; ++i) {
+                        double le = 0.0, lo = 0.0;
+                        for (int r = 0; r < rows; ++r) {
+                            le += hc.u_all[static_cast<size_t>(r) * n_par + i] * sm[static_cast<size_t>(r)];
+                            lo += hc.u_all[static_cast<size_t>(r) * n_par + ne16 + i] * df[static_cast<size_t>(r)];
+                        }
+                        if (i >= m2l_no_) {
+                            Lb[i] += le;
+                        } else {
+                            Lb[i] += le + lo;
+                            Lb[m2l_rho(i)] += le - lo;
+                        }
+                    }
+                    continue;
+                }
                 for (int i = 0; i < n; ++i) {
                     double s = 0.0;
                     for (int k = 0; k < hc.k_pad; ++k) s += hc.u_all[static_cast<size_t>(k) * n_pad + i] * cc[k];
@@ -1126,6 +1216,27 @@ void FmmTree::debug_m2l_pairs(std::vector<int32_t> *out) const {
             if (h.src_pair[pos] == -2) continue;
             out->push_back(h.src_pair[pos] >= 0 ? 1 : 0);
             for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.src_tv[pos]) * d + a]);
+            ++n_entries;
+        }
+        (*out)[n_at] = n_entries;
+    }
+}
+
+void FmmTree::debug_m2l_pairs_stage2(std::vector<int32_t> *out) const {
+    out->clear();
+    const int d = d_;
+    for (const HostM2lClass &h : m2l_host_) {
+        if (h.cells.empty()) continue;
+        out->push_back(h.level);
+        out->push_back(h.octant);
+        out->push_back(0);
+        const size_t n_at = out->size();
+        out->push_back(0);
+        int32_t n_entries = 0;
+        for (size_t pos = 0; pos < h.tgt_tv.size(); ++pos) {
+            if (h.tgt_pair[pos] == -2) continue;
+            out->push_back(h.tgt_pair[pos] >= 0 ? 1 : 0);
+            for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.tgt_tv[pos]) * d + a]);
             ++n_entries;
         }
         (*out)[n_at] = n_entries;

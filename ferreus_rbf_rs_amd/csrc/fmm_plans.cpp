@@ -612,7 +612,7 @@ int FmmTree::build_downward_plan(const std::vector<int32_t> &target_leaves, Down
         std::fill(tpos_of.begin(), tpos_of.end(), -1);
         for (size_t pos = 0; pos < hc.tgt_tv.size(); ++pos) tpos_of[hc.tgt_tv[pos]] = static_cast<int>(pos);
         const auto &lops = ops_.m2l[hc.level];
-        const int nq = hc.k_pad / 16;
+        const int nq = (hc.k_pad - hc.kp) / 16; // steps of the operator's rows (HostM2lClass::kp)
         const int64_t n_t2 = static_cast<int64_t>(tiles2.size() - t2);
         std::vector<std::vector<uint16_t>> tile_q(static_cast<size_t>(n_t2));
         parallel_for(n_t2, 4, [&](int64_t k) {
@@ -624,7 +624,7 @@ int FmmTree::build_downward_plan(const std::vector<int32_t> &target_leaves, Down
                     const int tv = t.v_tidx[q];
                     const int pos = tv >= 0 && tv < ops_.n_vec ? tpos_of[tv] : -1;
                     if (pos < 0) continue;
-                    const int a = hc.tgt_off[pos], b = a + lops[ops_.ref_lookup[tv]].rank;
+                    const int a = hc.tgt_off[pos] - (hc.tgt_off[pos] >= hc.kp ? hc.kp : 0), b = a + lops[ops_.ref_lookup[tv]].rank;
                     for (int sq = a / 16; sq <= (b - 1) / 16; ++sq) act_k[sq] = 1;
                 }
             }

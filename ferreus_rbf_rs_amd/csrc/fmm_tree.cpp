@@ -498,13 +498,14 @@ int FmmTree::upload() {
         c.r_pad16 = h.r_pad16;
         c.n_t = h.n_t;
         c.k_pad = h.k_pad;
+        c.kp = h.kp;
         c.n_cells = static_cast<int32_t>(h.cells.size());
         if (h.cells.empty()) continue;
         DevBuf<double> vt, ua;
         DevBuf<int32_t> rt, rt2, ro, ce, cs;
         DevBuf<int64_t> cb;
         {
-            const size_t nvt = static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : cheb_.n_pad) * h.r_pad16, nu = static_cast<size_t>(h.k_pad) * cheb_.n_pad;
+            const size_t nvt = static_cast<size_t>(m2l_pairs_ ? m2l_npar_ : cheb_.n_pad) * h.r_pad16, nu = m2l_pairs2_ ? static_cast<size_t>(h.k_pad - h.kp) * m2l_s2_plan_.n_par() : static_cast<size_t>(h.k_pad) * cheb_.n_pad;
             CHK(dalloc(&vt, nvt));
             CHK(dalloc(&ua, nu));
             const auto &lops = ops_.m2l[h.level];
@@ -518,18 +519,21 @@ int FmmTree::upload() {
                 src_tv.push_back(M2lAssembleTv{ops_.perm_lookup[tv], rank, h.src_row0[pos], vt_off[h.level][ref], u_off[h.level][ref]});
             }
             for (size_t pos = 0; pos < h.tgt_tv.size(); ++pos) {
+                if (m2l_pairs2_ && h.tgt_pair[pos] == -2) continue; // the partner owns no operator rows
                 const int tv = h.tgt_tv[pos];
                 const int ref = ops_.ref_lookup[tv];
                 const int rank = lops[ref].rank;
                 max_rank = std::max(max_rank, rank);
-                tgt_tv.push_back(M2lAssembleTv{ops_.perm_lookup[tv], rank, h.tgt_off[pos], vt_off[h.level][ref], u_off[h.level][ref]});
+                const int row = m2l_pairs2_ && h.tgt_pair[pos] < 0 ? h.tgt_off[pos] - h.kp : h.tgt_off[pos]; // (a single's operator row)
+                tgt_tv.push_back(M2lAssembleTv{ops_.perm_lookup[tv], rank, row, vt_off[h.level][ref], u_off[h.level][ref]});
             }
             DevBuf<M2lAssembleTv> d_src, d_tgt;
             CHK(dupload(&d_src, src_tv));
             CHK(dupload(&d_tgt, tgt_tv));
             const M2lAssembleClass ac{d_src.p, d_tgt.p, static_cast<int32_t>(src_tv.size()), static_cast<int32_t>(tgt_tv.size()),
                                       h.r_pad16, h.k_pad, max_rank,
-                                      m2l_pairs_ ? m2l_ne_ : 0, m2l_no_, m2l_ne16_, m2l_npar_, ops_.p};
+                                      m2l_pairs_ ? m2l_ne_ : 0, m2l_no_, m2l_ne16_, m2l_npar_, ops_.p,
+                                      m2l_pairs2_ ? m2l_s2_plan_.n_par() : 0, m2l_s2_plan_.ne16(), h.k_pad - h.kp, m2l_ne_, m2l_no_};
             static const bool host_fill = std::getenv("BBFMM_M2L_ASSEMBLE_HOST") != nullptr; // checker: the host fill of round 1
             if (host_fill) {
                 std::vector<double> hv, hu;
@@ -619,6 +623,10 @@ int FmmTree::ensure_rhs_capacity(int k) {
     // the M2L intermediate: as many right-hand sides per pass as fit the budget (at least one); absent pairs stay 0
     m2l_rhs_chunk_ = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(k, m2l_budget_bytes_ / 8 / std::max<int64_t>(cbuf_batch_len_, 1))));
     CHK(dalloc(&d_cbuf_, static_cast<size_t>(m2l_rhs_chunk_) * std::max<int64_t>(cbuf_batch_len_, 1), true));
+    if (m2l_pairs2_) { // stage 2's output in the parity basis, for the right-hand sides of one pass
+        dfree(&d_Lp_);
+        CHK(dalloc(&d_Lp_, static_cast<size_t>(m2l_rhs_chunk_) * C * m2l_s2_plan_.n_par(), true));
+    }
     CHK(dalloc(&d_out_, static_cast<size_t>(k) * N));
     CHK(dalloc(&src_targets_.out, static_cast<size_t>(k) * N));
     k_cap_ = k;
@@ -911,7 +919,11 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     have_locals_ = false; // L is being rewritten; downward_tail says what it holds at the end
     // reset_local_coefficients (bbfmm.rs:627-632): tiles without any V-list entry are not written by
     // stage 2, and P2L / L2L add onto L
-    HIPCHK(hipMemsetAsync(d_L_.p, 0, static_cast<size_t>(k) * C * cheb_.n_pad * sizeof(double), stream_));
+    // (parity basis of stage 2: the same holds for Lp, cleared per pass of right-hand sides below, and the pass back to the
+    // node order writes every row of L)
+    const bool s2_pairs = m2l_pairs2_ && !m2l_batches_.empty();
+    const int lp_len = m2l_s2_plan_.n_par();
+    if (!s2_pairs) HIPCHK(hipMemsetAsync(d_L_.p, 0, static_cast<size_t>(k) * C * cheb_.n_pad * sizeof(double), stream_));
     // a plan runs stage 1 on compact tiles of the sources its targets need, stage 2 on the tiles that
     // hold a cell with targets, P2L / L2L on the cells with targets (cells_with_targets, bbfmm.rs:468-480)
     const int m2l_len = shared_basis_ ? basis_pad_ : cheb_.n_pad;
@@ -922,7 +934,7 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
         launch_m2l_parity(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_ne16_, m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(k) * C, stream_);
         phase_end(kPhM2L1);
     }
-    double *l_out = shared_basis_ ? d_Lc_.p : d_L_.p;
+    double *l_out = shared_basis_ ? d_Lc_.p : s2_pairs ? d_Lp_.p : d_L_.p;
     if (shared_basis_) { // coordinates of every multipole in its level's basis; stage 2 leaves untouched tiles at 0
         phase_begin();
         launch_m2l_basis(d_basis_classes_.p, d_basis_tiles_c_.p, n_basis_tiles_, cheb_.n_pad, basis_pad_, k, C, d_M_.p, d_Mc_.p, stream_);
@@ -935,7 +947,8 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     for (int k0 = 0; k0 < k; k0 += m2l_rhs_chunk_) {
         const int kb = std::min(m2l_rhs_chunk_, k - k0);
         const double *m_chunk = m_in + static_cast<size_t>(k0) * C * s1_len;
-        double *l_chunk = l_out + static_cast<size_t>(k0) * C * m2l_len;
+        double *l_chunk = s2_pairs ? d_Lp_.p : l_out + static_cast<size_t>(k0) * C * m2l_len;
+        if (s2_pairs) HIPCHK(hipMemsetAsync(d_Lp_.p, 0, static_cast<size_t>(kb) * C * lp_len * sizeof(double), stream_));
         for (int b = 0; b < nb; ++b) {
             const M2lBatch &mb = m2l_batches_[static_cast<size_t>(b)];
             const int t1_first = dp ? dp->batch_t1[4 * b] : mb.t1_first, t1_count = dp ? dp->batch_t1[4 * b + 1] : mb.t1_count;
@@ -956,12 +969,23 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
                                   m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16);
             phase_end(kPhM2L1);
             phase_begin();
-            if (dp)
+            if (s2_pairs) {
+                if (!launch_m2l_stage2_pairs(d_m2l_classes_.p, dp ? dp->d_tiles2.p + t2_first : d_m2l_tiles2_.p + t2_first,
+                                             dp ? dp->d_tile_idx.p : nullptr, t2_count, m2l_s2_plan_, kb, C, d_cbuf_.p, cbuf_batch_len_,
+                                             dp ? dp->d_qlist.p : d_m2l_qlist_.p, l_chunk, stream_, !deterministic_, &m2l_s2_last_ksplit_))
+                    return fail(BBFMM_DEVICE_ERROR, "internal: no stage-2 kernel instance for the parity-basis column plan");
+            } else if (dp)
                 launch_m2l_stage2(d_m2l_classes_.p, dp->d_tiles2.p + t2_first, dp->d_tile_idx.p, t2_count, m2l_len, kb, C, d_cbuf_.p,
                                   cbuf_batch_len_, dp->d_qlist.p, l_chunk, stream_, !deterministic_);
             else
                 launch_m2l_stage2(d_m2l_classes_.p, d_m2l_tiles2_.p + t2_first, nullptr, t2_count, m2l_len, kb, C, d_cbuf_.p,
                                   cbuf_batch_len_, d_m2l_qlist_.p, l_chunk, stream_, !deterministic_);
+            phase_end(kPhM2L2);
+        }
+        if (s2_pairs) { // this pass's right-hand sides back to the node order (part of stage 2's time)
+            phase_begin();
+            launch_m2l_unparity(d_Lp_.p, lp_len, m2l_s2_plan_.ne16(), d_L_.p + static_cast<size_t>(k0) * C * cheb_.n_pad, ops_.n, cheb_.n_pad,
+                                m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(kb) * C, stream_);
             phase_end(kPhM2L2);
         }
     }

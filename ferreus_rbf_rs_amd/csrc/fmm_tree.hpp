@@ -46,6 +46,10 @@ struct HostM2lClass {
     // for Rt, which owns no rows of its own (its src_row0 / src_row1 repeat those of t)
     std::vector<int32_t> row_tpos2, row_off2, row_dst2; // as row_tpos / row_off / row_dst for the difference a - b; -1: none
     std::vector<int32_t> src_pair;                      // per source position: partner's position (first of a pair), -1 (single), -2 (second of a pair)
+    // x-reflected pairs of stage 2 (FmmTree::m2l_pairs2_): the slot is [A | B | S] -- the leaders' segments, their partners'
+    // at the same offsets kp further on, the singles from 2 kp; the operator has k_pad - kp rows (M2lClass::kp)
+    int kp = 0;
+    std::vector<int32_t> tgt_pair; // per target position: partner's position (leader), -1 (single), -2 (partner)
     std::vector<int64_t> cbase;
 };
 
@@ -246,6 +250,11 @@ class FmmTree {
     // single), then the d components of t.
     void debug_m2l_pairs(std::vector<int32_t> *out) const;
     bool m2l_pairs() const { return m2l_pairs_; }
+    // The same for the stage-2 operators (the target lists of the classes; kind is always 0).
+    void debug_m2l_pairs_stage2(std::vector<int32_t> *out) const;
+    bool m2l_pairs_stage2() const { return m2l_pairs2_; }
+    // Test hook: parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet).
+    int debug_m2l_s2_last_ksplit() const { return m2l_s2_last_ksplit_; }
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
     // M, L: n_cells x n (cell-major, one rhs).  L is accumulated into.
     int debug_apply_m2l_tables_host(const double *M, double *L) const;
@@ -349,6 +358,12 @@ class FmmTree {
         return m + (ops_.p - 1 - 2 * (m / p1)) * p1;
     }
     DevBuf<double> d_Mp_;                // k x C x m2l_npar_: the multipoles in the parity basis (pads stay zero)
+    // Stage 2 in the same basis: one product serves the slot segments of t and Rt (their sum against U_e, their difference
+    // against U_o); stage 2 writes Lp = [L_e | pad | L_o | pad], a streaming pass turns it into L.
+    bool m2l_pairs2_ = false;            // BBFMM_M2L_S2_PAIRS (read per handle), same conditions as m2l_pairs_
+    M2lS2PairsPlan m2l_s2_plan_{1, 1, 1, 1}; // column chunks of the two halves; n_par() values per cell in Lp
+    DevBuf<double> d_Lp_;                // m2l_rhs_chunk_ x C x m2l_s2_plan_.n_par(): one pass of right-hand sides at a time
+    int m2l_s2_last_ksplit_ = 0;         // debug_m2l_s2_last_ksplit
     // partition
     int part_rank_ = 0, part_world_ = 1;
     std::vector<int64_t> part_rows_, part_bounds_;

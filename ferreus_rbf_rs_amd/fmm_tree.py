@@ -565,13 +565,15 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_m2l_variants(self._h, ctypes.byref(nv), ctypes.byref(nc)))
         return nv.value, nc.value
 
-    def debug_m2l_pairs(self):
+    def debug_m2l_pairs(self, stage=1):
         """(pairs_on, operators): per stage-1 operator a dict with level, octant, kind (0: class, 1: boundary variant
-        or group operator), pairs (the vectors t whose product also serves Rt) and singles, as tuples of components."""
+        or group operator), pairs (the vectors t whose product also serves Rt) and singles, as tuples of components.
+        stage=2: the same for the stage-2 operators, the target lists of the classes (kind 0)."""
+        fn = self._lib.bbfmm_debug_m2l_pairs if stage == 1 else self._lib.bbfmm_debug_m2l_pairs_stage2
         n, on = ctypes.c_int64(), ctypes.c_int32()
-        self._raise(self._lib.bbfmm_debug_m2l_pairs(self._h, None, 0, ctypes.byref(n), ctypes.byref(on)))
+        self._raise(fn(self._h, None, 0, ctypes.byref(n), ctypes.byref(on)))
         buf = np.zeros(max(n.value, 1), dtype=np.int32)
-        self._raise(self._lib.bbfmm_debug_m2l_pairs(self._h, buf.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(on)))
+        self._raise(fn(self._h, buf.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(on)))
         d, ops, i = self.dim, [], 0
         while i < n.value:
             level, octant, kind, ne = (int(v) for v in buf[i:i + 4])
@@ -581,6 +583,12 @@ class FmmTree:
                         "singles": [tuple(int(x) for x in e[1:]) for e in ent if e[0] == 0]})
             i += 4 + ne * (d + 1)
         return bool(on.value), ops
+
+    def debug_m2l_s2_last_ksplit(self) -> int:
+        """Parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet)."""
+        ks = ctypes.c_int32()
+        self._raise(self._lib.bbfmm_debug_m2l_s2_last_ksplit(self._h, ctypes.byref(ks)))
+        return ks.value
 
     def debug_get_coefficients(self, which: str, k: int) -> np.ndarray:
         s = self.stats()
