@@ -79,6 +79,9 @@ SIGNATURES = {
     "bbfmm_isosurfaces_from_values_opts": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_p, c_p]),
     "bbfmm_isosurface_finish_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_follow_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_follow_times": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_follow_bricks": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
     "bbfmm_isosurface_intersection_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_isosurface_self_intersections": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_intersection_ids": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
@@ -194,7 +197,8 @@ FLAG_GLOBAL_SCALING = 1
 class IsosurfaceOptions(ctypes.Structure):
     """bbfmm_isosurface_options"""
     _fields_ = [("size", c_i64), ("cluster_method", c_i32), ("finish", c_i32), ("batch_bytes", c_i64),
-                ("self_intersections", c_i32)]
+                ("self_intersections", c_i32), ("follow", c_i32), ("seeds", ctypes.c_void_p), ("n_seeds", c_i64),
+                ("seeds_ld", c_i64)]
 
 
 class DdmParams(ctypes.Structure):

@@ -296,8 +296,14 @@ static bool iso_args(const double *extents, double resolution, const double *iso
 }
 
 // The fields of *o that its size covers; defaults for the rest and for o == nullptr.
+struct IsoFollow {
+    int32_t follow = BBFMM_FOLLOW_DENSE;
+    const double *seeds = nullptr;
+    int64_t n_seeds = 0, seeds_ld = 0;
+};
+
 static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int32_t *finish, int64_t *batch_bytes,
-                        int32_t *self_intersections, std::string *err) {
+                        int32_t *self_intersections, std::string *err, IsoFollow *fol = nullptr) {
     *cluster = BBFMM_CLUSTER_NONE;
     *finish = BBFMM_FINISH_RAW;
     *batch_bytes = 0;
@@ -312,6 +318,32 @@ static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int
     if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, batch_bytes) + sizeof(int64_t))) *batch_bytes = o->batch_bytes;
     if (o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, self_intersections) + sizeof(int32_t)))
         *self_intersections = o->self_intersections;
+    // follow lies in what was padding after self_intersections, which an older caller's size covers without having set
+    // it: it is read together with the seeds, from a struct that holds them all
+    if (fol && o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, seeds_ld) + sizeof(int64_t))) {
+        fol->follow = o->follow;
+        fol->seeds = o->seeds;
+        fol->n_seeds = o->n_seeds;
+        fol->seeds_ld = o->seeds_ld;
+    }
+    return true;
+}
+
+static bool iso_follow_ok(const IsoFollow &fol, bool need_seeds, std::string *err) {
+    if (fol.follow != BBFMM_FOLLOW_DENSE && fol.follow != BBFMM_FOLLOW_SURFACE) {
+        *err = "isosurface: unknown follow mode " + std::to_string(fol.follow);
+        return false;
+    }
+    if (fol.follow == BBFMM_FOLLOW_DENSE) return true;
+    if (fol.n_seeds < 0 || (fol.n_seeds > 0 && (!fol.seeds || fol.seeds_ld < fol.n_seeds))) {
+        *err = "isosurface: seeds must hold n_seeds >= 0 points with seeds_ld >= n_seeds";
+        return false;
+    }
+    if (need_seeds && !fol.seeds && fol.n_seeds == 0) {
+        // (an empty array of seeds is given as a non-null pointer with n_seeds = 0)
+        *err = "isosurface: follow=surface of a caller's values needs seeds";
+        return false;
+    }
     return true;
 }
 
@@ -411,13 +443,14 @@ int bbfmm_build_isosurfaces(bbfmm_handle *h, const double *extents, double resol
 static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                   int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
                                   int32_t cluster_method, int32_t finish, int32_t self_intersections,
-                                  bbfmm_isosurface_result **out) {
+                                  bbfmm_isosurface_result **out, const IsoFollow &fol = IsoFollow()) {
     GUARD(h)
     if (out) *out = nullptr;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     {
         std::string bad;
         if (!iso_methods_ok(cluster_method, finish, self_intersections, &bad)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, bad);
+        if (!iso_follow_ok(fol, false, &bad)) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, bad);
     }
     if (h->tree.tree().d != 3) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: only supported for 3D (d = 3)");
     bbfmm::iso::Lattice lat;
@@ -458,6 +491,27 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
     req.finish = finish;
     req.extents = extents;
     req.self_intersections = self_intersections;
+    req.follow = fol.follow;
+    if (fol.follow == BBFMM_FOLLOW_SURFACE) {
+        if (fol.seeds) {
+            req.seeds = fol.seeds;
+            req.n_seeds = fol.n_seeds;
+            req.seeds_ld = fol.seeds_ld;
+        } else { // the data points (rbf.rs:1049)
+            req.seeds = t.source_points().data();
+            req.n_seeds = req.seeds_ld = t.tree().n_points;
+        }
+        // BBFMM_ISO_SEED_GRADIENTS=differences (read per call): the reference's central differences of the values
+        // (seed_projection.rs:138-189), which a kernel without gradients takes anyway
+        const char *sg = std::getenv("BBFMM_ISO_SEED_GRADIENTS");
+        if (sg && *sg && std::strcmp(sg, "differences") != 0 && std::strcmp(sg, "leaf_pass") != 0)
+            return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, std::string("isosurface: BBFMM_ISO_SEED_GRADIENTS must be leaf_pass or differences, got '") + sg + "'");
+        if (t.supports_gradients() && !(sg && !std::strcmp(sg, "differences")))
+            req.grad = [&t](const double *x0, const double *x1, const double *x2, int64_t m, double *vals, double *grad) {
+                int64_t bad = -1;
+                return t.evaluate_leaves_device(x0, x1, x2, m, vals, &bad, grad);
+            };
+    }
     std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
     const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);
     if (rc != BBFMM_OK) {
@@ -476,7 +530,8 @@ enum IsoMeshOp : int { kIsoField = 0, kIsoFinishMesh = 1, kIsoDetectMesh = 2 };
 static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes, int32_t cluster_method,
                                  int32_t finish, int32_t self_intersections, const double *vertices, int64_t n_vertices,
-                                 const int64_t *facets, int64_t n_facets, int mesh_op, bbfmm_isosurface_result **out) {
+                                 const int64_t *facets, int64_t n_facets, int mesh_op, bbfmm_isosurface_result **out,
+                                 const IsoFollow &fol = IsoFollow()) {
     const bool one_mesh = mesh_op != kIsoField, detect = mesh_op == kIsoDetectMesh;
     if (!out) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: out must not be null");
     *out = nullptr;
@@ -509,6 +564,7 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
             if (!iso_args(extents, resolution, isovalues, n_isovalues, &lat, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
             if (!values) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, "isosurface: values must not be null");
             if (!iso_methods_ok(cluster_method, finish, self_intersections, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
+            if (!iso_follow_ok(fol, true, &err)) return iso_fail(h, r, BBFMM_BAD_ARGUMENT, err);
         }
         if (h && h->tree.host_only()) return iso_fail(h, r, BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
         if (h && h->group) {
@@ -571,6 +627,10 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
             req.finish = finish;
             req.extents = extents;
             req.self_intersections = self_intersections;
+            req.follow = fol.follow;
+            req.seeds = fol.seeds;
+            req.n_seeds = fol.n_seeds;
+            req.seeds_ld = fol.seeds_ld;
             rc = bbfmm::iso::extract(lat, bbfmm::iso::FieldFn(), req, st, &r->meshes, &err);
         }
         if (own) (void)hipStreamDestroy(st);
@@ -609,11 +669,12 @@ int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double 
     int32_t cluster, finish, isect;
     int64_t batch;
     std::string err;
-    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err)) {
+    IsoFollow fol;
+    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err, &fol)) {
         if (out) *out = nullptr;
         return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
     }
-    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch, cluster, finish, isect, out);
+    return build_isosurfaces_impl(h, extents, resolution, isovalues, n_isovalues, drift, d_field_out, batch, cluster, finish, isect, out, fol);
 }
 
 int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, const double *extents, double resolution,
@@ -622,12 +683,13 @@ int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, co
     int32_t cluster, finish, isect;
     int64_t batch;
     std::string err;
-    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err)) {
+    IsoFollow fol;
+    if (!iso_options(options, &cluster, &finish, &batch, &isect, &err, &fol)) {
         if (out) *out = nullptr;
         return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, err);
     }
     return isosurfaces_from_host(h, values, extents, resolution, isovalues, n_isovalues, batch, cluster, finish, isect, nullptr, 0,
-                                 nullptr, 0, kIsoField, out);
+                                 nullptr, 0, kIsoField, out, fol);
 }
 
 int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
@@ -669,6 +731,26 @@ int bbfmm_isosurface_triangle_pair(const double *tri_a, const int64_t *ids_a, co
     int stage = 0;
     *result_out = triangle_pair(a, ids_a, b, ids_b, &stage) ? 1 : 0;
     if (stage_out) *stage_out = stage;
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_follow_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(stats_out, r->meshes[i].follow_stats, sizeof(r->meshes[i].follow_stats));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_follow_bricks(const bbfmm_isosurface_result *r, int32_t i, int32_t *dims_out, uint8_t *bricks_out) {
+    if (!r || !dims_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    const bbfmm::iso::Mesh &m = r->meshes[i];
+    std::memcpy(dims_out, m.follow_dims, sizeof(m.follow_dims));
+    if (bricks_out && !m.follow_bricks.empty()) std::memcpy(bricks_out, m.follow_bricks.data(), m.follow_bricks.size());
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_follow_times(const bbfmm_isosurface_result *r, int32_t i, double *ms_out) {
+    if (!r || !ms_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(ms_out, r->meshes[i].follow_ms, sizeof(r->meshes[i].follow_ms));
     return BBFMM_OK;
 }
 

@@ -1320,14 +1320,19 @@ int FmmTree::evaluate(const double *w, int64_t rows, int k, int64_t ldw, const d
     return rc;
 }
 
+bool FmmTree::supports_gradients() const { return kernel_supports_gradients(kernel_.id); }
+
 int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
-                                    int64_t *bad_point_index) {
+                                    int64_t *bad_point_index, double *d_grad) {
     if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
     if (d_ != 3) return fail(BBFMM_BAD_ARGUMENT, "device-resident targets need d = 3");
     if (nrhs_ != 1 || !have_locals_) return fail(BBFMM_BAD_ARGUMENT, "set_local_coefficients (one column) must be called first");
     if (multipoles_partial_) return fail(BBFMM_BAD_ARGUMENT, kPartialMultipoles);
     if (m < 0 || (m > 0 && (!d_x0 || !d_x1 || !d_x2))) return fail(BBFMM_BAD_ARGUMENT, "bad device target arrays");
     if (m >= (int64_t(1) << 31)) return fail(BBFMM_BAD_ARGUMENT, "more than 2^31-1 target points");
+    if (d_grad && !d_out) return fail(BBFMM_BAD_ARGUMENT, "gradients at device targets need their values too");
+    if (d_grad && !kernel_supports_gradients(kernel_.id))
+        return fail(BBFMM_KERNEL_NO_GRADIENTS, "FMM evaluation failed: gradient evaluation requested but kernel does not support gradients");
     if (m == 0) return BBFMM_OK;
     part_pending_k_ = 0;
     last_eval_at_sources_ = last_eval_rows_of_sources_ = false;
@@ -1365,10 +1370,12 @@ int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, cons
     const double *dx[3] = {d_x0, d_x1, d_x2};
     int rc = build_target_set_device(nullptr, m, m, &ts, bad_point_index, nullptr, dx);
     if (rc == BBFMM_OK) rc = talloc(&ts.out, static_cast<size_t>(m));
-    if (rc == BBFMM_OK) rc = leaf_pass(ts, 1, false);
+    if (rc == BBFMM_OK && d_grad) rc = talloc(&ts.grad, static_cast<size_t>(d_) * m);
+    if (rc == BBFMM_OK) rc = leaf_pass(ts, 1, d_grad != nullptr);
     if (rc == BBFMM_OK) {
         phase_begin();
         launch_scatter_output(ts.out.p, m, 1, ts.perm.p, d_out, m, 0, stream_);
+        if (d_grad) launch_scatter_output(ts.grad.p, m, d_, ts.perm.p, d_grad, m, 0, stream_);
         phase_end(kPhScatter);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(stream_); // the target set's arena buffers are reused by the next call

@@ -166,9 +166,11 @@ class FmmTree {
     // Leaves mode (after set_local_coefficients, one column) at m targets that are already on the device (SoA, d == 3):
     // the target set, grouping and leaf pass of evaluate(..., leaves_only = true) with no host copy; values to d_out in
     // row order, on the handle's stream (isosurface lattice nodes).  d_out == nullptr: only checks that every target
-    // lies in the tree (BBFMM_POINT_OUTSIDE_TREE, *bad_point_index the first row that does not).
+    // lies in the tree (BBFMM_POINT_OUTSIDE_TREE, *bad_point_index the first row that does not).  d_grad (with d_out): the
+    // gradients too, component a of target t at d_grad[a * m + t] (isosurface seed projection).
     int evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
-                               int64_t *bad_point_index);
+                               int64_t *bad_point_index, double *d_grad = nullptr);
+    bool supports_gradients() const;
     int evaluate(const double *w, int64_t rows, int k, int64_t ldw, const double *x, int64_t m, int64_t ldx,
                  double *out, int64_t ldo, double *grad, int64_t ldg, bool with_grads, bool leaves_only,
                  int64_t *bad_point_index);                                             // bbfmm.rs:444-616

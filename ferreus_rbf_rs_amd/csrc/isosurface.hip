@@ -848,11 +848,17 @@ bool make_lattice(const double *extents, double resolution, Lattice *out, std::s
 
 int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t st, std::vector<Mesh> *meshes,
             std::string *err) {
+    if (req.follow == kFollowSurface) return extract_follow(lat, field, req, st, meshes, err);
+    if (req.follow != kFollowDense) {
+        *err = "isosurface: unknown follow mode " + std::to_string(req.follow);
+        return BBFMM_BAD_ARGUMENT;
+    }
     TetTables tt;
     if (!make_tet_tables(&tt)) {
         *err = "isosurface: internal error (a tetrahedron edge is not a lattice edge)";
         return BBFMM_BAD_ARGUMENT;
     }
+    const bool given = req.host_field || req.d_field_in; // the field is the caller's
     const int64_t ni = lat.dims[0], nj = lat.dims[1], nk = lat.dims[2], P = ni * nj;
     const int n_iso = req.n_iso;
     const bool cluster = req.cluster == kClusterAverage;
@@ -915,7 +921,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     ISO_HIP(pool.get(&fcnt, slab_nodes));
     ISO_HIP(pool.get(&voff, slab_nodes));
     ISO_HIP(pool.get(&foff, slab_nodes));
-    if (!req.host_field) {
+    if (!given) {
         for (auto &x : xs) ISO_HIP(pool.get(&x, slab_nodes / 2 + P));
         ISO_HIP(pool.get(&vals, slab_nodes / 2 + P));
     }
@@ -992,7 +998,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         ISO_HIP(hipMemcpyAsync(&last[1], flag + s.nodes - 1, 4, hipMemcpyDeviceToHost, st));
         ISO_HIP(hipStreamSynchronize(st));
         *m_out = static_cast<int64_t>(last[0]) + last[1];
-        if (!req.host_field) {
+        if (!given) {
             node_coords_kernel<<<g, kThreads, 0, st>>>(s, flag, idx, xs[0], xs[1], xs[2]);
             ISO_HIP(hipGetLastError());
         }
@@ -1000,7 +1006,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     };
 
     // every node must lie in the tree before any work is done (the reference pads its evaluator by 10 r, rbf.rs:992-998)
-    if (!req.host_field) {
+    if (!given) {
         for (int64_t k0 = 0; k0 < nk; k0 += nb) {
             const Slab s = slab_for(k0, std::min(nk, k0 + nb));
             int64_t m = 0;
@@ -1020,7 +1026,9 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         int64_t m = 0;
         int rc = gather_nodes(s, &m);
         if (rc != BBFMM_OK) return rc;
-        if (req.host_field) {
+        if (req.d_field_in) {
+            ISO_HIP(hipMemcpyAsync(f + P, req.d_field_in + k0 * P, s.nodes * sizeof(double), hipMemcpyDeviceToDevice, st));
+        } else if (req.host_field) {
             ISO_HIP(hipMemcpyAsync(f + P, req.host_field + k0 * P, s.nodes * sizeof(double), hipMemcpyHostToDevice, st));
         } else if (m > 0) {
             // one call per group of G planes: the group's nodes are a contiguous range of the compacted arrays
@@ -1034,7 +1042,7 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
                 if (c > 0 && (rc = field(xs[0] + b, xs[1] + b, xs[2] + b, c, vals + b)) != BBFMM_OK) return rc;
             }
         }
-        field_kernel<<<g, kThreads, 0, st>>>(s, flag, idx, req.host_field ? nullptr : vals, drift, da, db0, db1, db2, f);
+        field_kernel<<<g, kThreads, 0, st>>>(s, flag, idx, given ? nullptr : vals, drift, da, db0, db1, db2, f);
         ISO_HIP(hipGetLastError());
         if (req.d_field_out)
             ISO_HIP(hipMemcpyAsync(req.d_field_out + k0 * P, f + P, s.nodes * sizeof(double), hipMemcpyDeviceToDevice, st));

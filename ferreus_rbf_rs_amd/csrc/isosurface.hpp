@@ -3,9 +3,12 @@
 // ClusterMethod::Average (the intersections near a sample point merged where the topology tests allow it, with the
 // predicted-edge and non-manifold rollbacks and, where asked for, the self-intersection rollback), taken from every sample
 // point of the extraction domain in device passes instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
-// finished mesh of BoundaryClosure::None; boundary closure is not run).  Contract: DESIGN.md "Isosurfaces on the RMT
+// finished mesh of BoundaryClosure::None; boundary closure is not run).  With kFollowSurface the field is evaluated only in the
+// bricks of lattice nodes that a wavefront reaches from projected seed points (isosurface_follow.hip), as the reference
+// follows the surface, and the same passes run on that field.  Contract: DESIGN.md "Isosurfaces on the RMT
 // lattice"; numpy restatements: tests/isosurface_restatement.py, tests/isosurface_cluster_restatement.py,
-// tests/isosurface_finish_restatement.py and tests/isosurface_intersect_restatement.py.
+// tests/isosurface_finish_restatement.py, tests/isosurface_intersect_restatement.py and
+// tests/isosurface_follow_restatement.py.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -292,6 +295,10 @@ struct Mesh {
     int64_t stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // kStat*, all 0 without clustering
     int64_t finish_stats[kFinStats] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // FinishStat, all 0 with kFinishRaw
     int64_t isect_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // IntersectStat, all 0 without the detector
+    int64_t follow_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // FollowStat, all 0 with kFollowDense
+    double follow_ms[3] = {0, 0, 0};                                     // host time of the seed stage, the rounds, the extraction
+    int32_t follow_dims[4] = {0, 0, 0, 0};                               // B and the bricks per axis (x, y, z)
+    std::vector<uint8_t> follow_bricks;                                  // 1 per brick visited for this isovalue, x fastest
     std::vector<int64_t> isect_ids;                                      // the detector on a caller's mesh: the triangles found
 };
 
@@ -323,6 +330,40 @@ enum IntersectStat : int {
 // triangles has some hundreds per facet.
 constexpr int64_t kIsectPairFloor = int64_t(1) << 26, kIsectPairsPerFacet = 4096;
 
+// ---- following the surface (ferreus_rmt/src/seed_projection.rs, isosurface.rs:551-697; DESIGN.md "Following the surface")
+enum Follow : int { kFollowDense = 0, kFollowSurface = 1 };
+// Mesh::follow_stats
+enum FollowStat : int {
+    kFolSeeds = 0,      // seeds given
+    kFolCells = 1,      // distinct seed cells (after the clamp to the extents)
+    kFolNewton = 2,     // Newton steps run (evaluations of values and gradients)
+    kFolSeedBricks = 3, // bricks of the first frontier
+    kFolRounds = 4,     // rounds of the wavefront
+    kFolBricks = 5,     // bricks visited for this isovalue
+    kFolNodes = 6,      // nodes of E in them
+    kFolNodesE = 7,     // nodes of E
+    kFolStats = 8
+};
+// The halo of a crossed edge's ends, in (i, j, k): two edge steps (the topology test at an edge's near end reads that
+// sample point's 14 neighbours, and marching resolves every edge of a tetrahedron at its near end).
+constexpr int kFollowHalo[3] = {4, 2, 2};
+// seed_projection.rs:35-37
+constexpr int kSeedNewtonSteps = 30;
+constexpr double kSeedTol = 0.01, kSeedG2Min = 1.0e-20;
+
+// world_to_ijk (lattice.rs:98-121) of a point given in fine-grid coordinates p = (world - lo) / spacing: the origin of
+// its cell in the basis U, V, W = EDGE_DELTAS[0], [2], [6], whose inverse is written out here (the reference solves by LU).
+__host__ __device__ inline void seed_cell(const double p[3], int64_t ijk[3]) {
+#pragma clang fp contract(off)
+    const double eps = 1e-9;
+    const double qa = (p[1] - p[2] - p[0]) * 0.5, qb = (-p[2] - p[0] - p[1]) * 0.5, qc = -p[2];
+    const int64_t a = static_cast<int64_t>(floor(qa + eps)), b = static_cast<int64_t>(floor(qb + eps)),
+                  c = static_cast<int64_t>(floor(qc + eps));
+    ijk[0] = -a - b + c;
+    ijk[1] = a - b;
+    ijk[2] = -c;
+}
+
 // Finite extents with lo <= hi as a ClipBox with its eps; false with *err set otherwise.
 bool make_clip_box(const double *extents, ClipBox *out, std::string *err);
 
@@ -346,6 +387,8 @@ int self_intersections_device(const double *d_vertices, int64_t n_vertices, cons
 // Field values at m lattice nodes (SoA world coordinates on the device), written to d_vals[0..m) on the stream.
 // d_vals == nullptr: only check that every node can be evaluated (BBFMM_POINT_OUTSIDE_TREE otherwise).
 using FieldFn = std::function<int(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_vals)>;
+// The same with gradients: d_grad[a * m + t] = d f / d x_a at point t (seed projection).
+using GradFn = std::function<int(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_vals, double *d_grad)>;
 
 struct Request {
     const double *isovalues = nullptr;
@@ -358,6 +401,11 @@ struct Request {
     int finish = kFinishRaw;           // kFinishClipped: every mesh goes through finish_device before its download
     const double *extents = nullptr;   // the 6 extents of the lattice, needed with kFinishClipped and the rollback
     int self_intersections = kSelfIntersectionsIgnore; // kSelfIntersectionsRollback: with kClusterAverage, one round
+    const double *d_field_in = nullptr; // as host_field, already on the device (the field extract_follow filled)
+    int follow = kFollowDense;         // kFollowSurface: extract_follow evaluates the bricks a wavefront reaches from the seeds
+    const double *seeds = nullptr;     // host, coordinate a of seed s at seeds[a * seeds_ld + s]
+    int64_t n_seeds = 0, seeds_ld = 0;
+    GradFn grad;                       // values and gradients for the seed projection (empty: central differences of the FieldFn)
 };
 
 // Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.  With kClusterAverage
@@ -365,6 +413,12 @@ struct Request {
 // any work where that does not fit), and each isovalue is then clustered and marched over the whole lattice.
 int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t stream, std::vector<Mesh> *out,
             std::string *err);
+
+// extract() with kFollowSurface (isosurface_follow.hip): the field is evaluated brick by brick along a wavefront from
+// the seeds into an array over the box of E that is NaN everywhere else, and every isovalue then goes through the dense
+// extraction above on the bricks visited for it.  The brick side comes from BBFMM_ISO_BRICK (4, 8 or 16; default 8).
+int extract_follow(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t stream, std::vector<Mesh> *out,
+                   std::string *err);
 
 } // namespace iso
 } // namespace bbfmm

@@ -273,7 +273,8 @@ class FmmTree:
 
     # -- isosurfaces (isosurface.py)
     def build_isosurfaces(self, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes=0,
-                          cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
+                          cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
+                          seeds=None):
         """RBFInterpolator::build_isosurfaces (ferreus_rbf/src/rbf.rs:980-) on the device, one field evaluation for all
         isovalues: a list of (vertices (n, 3) f64, facets (m, 3) int64), the marching-tetrahedra mesh of ferreus_rmt
         (isosurface.rs:489-) over every sample point of the extraction domain.  finish: "raw" (the default) is that mesh
@@ -293,19 +294,24 @@ class FmmTree:
         (a, [b0, b1, b2]) added to the field as a + b . x (isosurface.affine_drift folds the reference's Constant /
         Linear drift with its translation and scale).  return_field: also the lattice field, shape
         isosurface.lattice_info(extents, resolution)["shape"], NaN off the evaluated nodes.  batch_bytes: device memory
-        for one batch of k-planes (0: the default); the meshes do not depend on it."""
+        for one batch of k-planes (0: the default); the meshes do not depend on it.  follow: "dense" (the default)
+        evaluates every node of the extraction domain; "surface" only the bricks of lattice nodes a wavefront reaches
+        from `seeds` ((n, 3) points, None: the source points, rbf.rs:1049) after they were projected onto the level set,
+        as the reference follows the surface (see isosurface.py); a component no seed reaches is then absent, the
+        returned field NaN where it was not evaluated, and the stats hold isosurface.FOLLOW_STATS under "follow"."""
         from . import isosurface as I
         return I.build_isosurfaces(self, extents, resolution, isovalues, drift=drift, return_field=return_field,
                                    batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish,
-                                   self_intersections=self_intersections)
+                                   self_intersections=self_intersections, follow=follow, seeds=seeds)
 
     def build_isosurface(self, extents, resolution, isovalue, *, drift=None, return_field=False, batch_bytes=0,
-                         cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
+                         cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
+                         seeds=None):
         """RBFInterpolator::build_isosurface (rbf.rs:954-) at one isovalue: (vertices, facets), then the stats when
         return_stats, then the lattice field when return_field; see build_isosurfaces."""
         out = self.build_isosurfaces(extents, resolution, [isovalue], drift=drift, return_field=return_field,
                                      batch_bytes=batch_bytes, cluster=cluster, return_stats=return_stats, finish=finish,
-                                     self_intersections=self_intersections)
+                                     self_intersections=self_intersections, follow=follow, seeds=seeds)
         if return_field:
             meshes, field = out
             return (*meshes[0], field)

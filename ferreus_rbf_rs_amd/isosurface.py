@@ -34,6 +34,19 @@ allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 f
   vertex of a group its representative; collapsed, zero-area (|ab x ac|^2 <= eps^4), repeated and lone facets dropped;
   vertices renumbered in order of first use.  `return_stats=True` then also holds the counts of `FINISH_STATS`.
 
+`follow="dense"` (the default) evaluates the field at every node of E.  `follow="surface"` follows the surface from seed
+points as the reference does (seed_projection.rs:29-130, isosurface.rs:551-697; DESIGN.md "Following the surface"): the
+box of E is cut into bricks of B x B x B nodes (B = 8; the environment variable BBFMM_ISO_BRICK takes 4, 8 or 16 and is
+read per call); `seeds` ((n, 3) world points; None with a tree: its source points) are clamped to the extents, kept one
+per lattice cell and, with a tree, moved onto the level set by at most 30 Newton steps (gradients from the leaf pass;
+BBFMM_ISO_SEED_GRADIENTS=differences takes the reference's central differences instead); the bricks that hold the 8
+corners of their cells are evaluated, and every lattice edge with both ends known and on opposite sides sends the wavefront into every brick
+within (4, 2, 2) nodes of its ends, until nothing new is reached.  The mesh is the dense extraction (every option
+above) of the field that is NaN outside the bricks visited for that isovalue: every component that passes through a
+seed's cell is complete and bit for bit the dense one on the same values, a component no seed reaches is absent,
+no seeds give an empty mesh.  `return_stats=True` then holds the counts of `FOLLOW_STATS`, the host times of the three
+stages, the brick side and the (nbz, nby, nbx) array of visited bricks under "follow".  Memory stays proportional to the box.
+
 Lattice fields are arrays of shape (nk, nj, ni) over the bounding box of E (`lattice_info(...)["shape"]`, entry
 [0, 0, 0] at ijk `lattice_info(...)["lo"]`); entries off E are ignored, and NaN in returned fields.
 """
@@ -143,8 +156,39 @@ def _finish(finish):
     return FINISH[finish]
 
 
-def _options(method, finish, batch_bytes, self_intersections=0):
-    return L.IsosurfaceOptions(ctypes.sizeof(L.IsosurfaceOptions), method, finish, int(batch_bytes), self_intersections)
+FOLLOW = {"dense": 0, "surface": 1}
+# return_stats with follow="surface" (bbfmm_isosurface_follow_stats)
+FOLLOW_STATS = ("seeds", "seed_cells", "newton_steps", "seed_bricks", "rounds", "bricks_visited", "nodes_evaluated", "nodes")
+
+
+def _follow(follow):
+    if follow not in FOLLOW:
+        raise ValueError(f"follow must be one of {sorted(FOLLOW)}, got {follow!r}")
+    return FOLLOW[follow]
+
+
+def _seeds(seeds):
+    """None, or the (n, 3) seed points as a column-major array (kept alive by the caller for the call)."""
+    if seeds is None:
+        return None
+    s = np.asarray(seeds, dtype=np.float64)
+    if s.size == 0:
+        return np.zeros((1, 3), order="F")[:0]
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError(f"seeds must have shape (n, 3), got {s.shape}")
+    if not np.all(np.isfinite(s)):
+        raise ValueError("seeds must be finite")
+    return np.asfortranarray(s)
+
+
+def _options(method, finish, batch_bytes, self_intersections=0, follow=0, seeds=None):
+    o = L.IsosurfaceOptions(ctypes.sizeof(L.IsosurfaceOptions), method, finish, int(batch_bytes), self_intersections)
+    o.follow = follow
+    if seeds is not None:
+        o.seeds = seeds.base.ctypes.data if len(seeds) == 0 else seeds.ctypes.data  # never null: an empty set of seeds is one
+        o.n_seeds = len(seeds)
+        o.seeds_ld = max(len(seeds), 1)
+    return o
 
 
 def _cluster(cluster):
@@ -195,13 +239,28 @@ def _finish_stats(lib, res, i):
     return {name: int(s[q]) for q, name in enumerate(FINISH_STATS)}
 
 
+def _follow_stats(lib, res, i):
+    s, ms = np.zeros(len(FOLLOW_STATS), dtype=np.int64), np.zeros(3)
+    lib.bbfmm_isosurface_follow_stats(res, i, s.ctypes.data)
+    lib.bbfmm_isosurface_follow_times(res, i, ms.ctypes.data)
+    out = {name: int(s[q]) for q, name in enumerate(FOLLOW_STATS)}
+    out.update(seed_ms=float(ms[0]), wavefront_ms=float(ms[1]), extract_ms=float(ms[2]))
+    dims = np.zeros(4, dtype=np.int32)
+    lib.bbfmm_isosurface_follow_bricks(res, i, dims.ctypes.data, None)
+    bricks = np.zeros(int(dims[1]) * int(dims[2]) * int(dims[3]), dtype=np.uint8)
+    if bricks.size:
+        lib.bbfmm_isosurface_follow_bricks(res, i, dims.ctypes.data, bricks.ctypes.data)
+    out.update(brick=int(dims[0]), visited=bricks.reshape(int(dims[3]), int(dims[2]), int(dims[1])).astype(bool))
+    return out
+
+
 def _intersection_stats(lib, res, i):
     s = np.zeros(8, dtype=np.int64)
     lib.bbfmm_isosurface_intersection_stats(res, i, s.ctypes.data)
     return {name: int(s[q]) for q, name in enumerate(INTERSECTION_STATS)}
 
 
-def _meshes(lib, res, stats=False, finish=0, self_intersections=0):
+def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0):
     out = []
     for i in range(lib.bbfmm_isosurface_count(res)):
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
@@ -215,6 +274,8 @@ def _meshes(lib, res, stats=False, finish=0, self_intersections=0):
                 st["finish"] = _finish_stats(lib, res, i)
             if self_intersections:
                 st["self_intersections"] = _intersection_stats(lib, res, i)
+            if follow:
+                st["follow"] = _follow_stats(lib, res, i)
             out.append((v, f, st))
         else:
             out.append((v, f))
@@ -233,11 +294,13 @@ def _raise(rc, msg, leaf=True):
 
 
 def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes: int = 0,
-                      cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
+                      cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
+                      seeds=None):
     """Meshes of the tree's field (set_local_coefficients first, one column) at each isovalue, one field evaluation
     for all of them; see FmmTree.build_isosurfaces."""
     lib = L.load()
     method, fin, isect = _cluster(cluster), _finish(finish), _self_intersections(self_intersections)
+    fol, sd = _follow(follow), _seeds(seeds)
     ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
     field_t = None
     if return_field:
@@ -247,8 +310,8 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
         field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
         torch.cuda.synchronize(field_t.device)
     res = ctypes.c_void_p()
-    if fin or isect:
-        opts = _options(method, fin, batch_bytes, isect)
+    if fin or isect or fol:
+        opts = _options(method, fin, batch_bytes, isect, fol, sd if fol else None)
         rc = lib.bbfmm_build_isosurfaces_opts(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
                                               d.ctypes.data if d is not None else None,
                                               field_t.data_ptr() if field_t is not None else None, ctypes.addressof(opts),
@@ -261,7 +324,7 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_last_error(tree._h).decode())
-        meshes = _meshes(lib, res, return_stats, fin, isect)
+        meshes = _meshes(lib, res, return_stats, fin, isect, fol)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
@@ -271,14 +334,19 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
 
 
 def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, batch_bytes: int = 0, tree=None,
-                            cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
+                            cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
+                            seeds=None):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
     current device (or the tree's).  cluster: "none" or "average", finish: "raw" or "clipped", self_intersections:
     "ignore" or "rollback" (see the module); return_stats: (vertices, facets, stats) per mesh, stats the clustering
     counts (all 0 with "none"), with finish="clipped" under "finish" the counts of FINISH_STATS and with
-    self_intersections="rollback" under "self_intersections" those of INTERSECTION_STATS."""
+    self_intersections="rollback" under "self_intersections" those of INTERSECTION_STATS.  follow="surface": only the
+    values in the bricks the wavefront reaches from `seeds` ((n, 3), required, used as they are) are looked at."""
     lib = L.load()
     method, fin, isect = _cluster(cluster), _finish(finish), _self_intersections(self_intersections)
+    fol, sd = _follow(follow), _seeds(seeds)
+    if fol and sd is None:
+        raise ValueError("follow='surface' of lattice values needs seeds")
     ext, iso = _ext(extents), _isovalues(isovalues)
     vals = np.ascontiguousarray(np.asarray(lattice_values, dtype=np.float64))
     info = lattice_info(ext, resolution, tree)
@@ -286,8 +354,8 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
         raise ValueError(f"lattice_values must have shape {info['shape']}, got {vals.shape}")
     res = ctypes.c_void_p()
     h = tree._h if tree is not None else None
-    if fin or isect:
-        opts = _options(method, fin, batch_bytes, isect)
+    if fin or isect or fol:
+        opts = _options(method, fin, batch_bytes, isect, fol, sd if fol else None)
         rc = lib.bbfmm_isosurfaces_from_values_opts(h, vals.ctypes.data, ext.ctypes.data, float(resolution),
                                                     iso.ctypes.data, len(iso), ctypes.addressof(opts), ctypes.byref(res))
     else:
@@ -296,19 +364,20 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
-        return _meshes(lib, res, return_stats, fin, isect)
+        return _meshes(lib, res, return_stats, fin, isect, fol)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
 
 
 def isosurface_from_values(lattice_values, extents, resolution, isovalue, *, batch_bytes: int = 0, tree=None,
-                           cluster="none", return_stats=False, finish="raw", self_intersections="ignore"):
+                           cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
+                           seeds=None):
     """(vertices (n, 3) f64, facets (m, 3) int64) of a caller's lattice field at one isovalue, and its stats when
     return_stats."""
     return isosurfaces_from_values(lattice_values, extents, resolution, [isovalue], batch_bytes=batch_bytes, tree=tree,
                                    cluster=cluster, return_stats=return_stats, finish=finish,
-                                   self_intersections=self_intersections)[0]
+                                   self_intersections=self_intersections, follow=follow, seeds=seeds)[0]
 
 
 def clip_mesh(vertices, facets, extents, return_stats=False, *, tree=None):

@@ -293,16 +293,45 @@ int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t 
  * refused. */
 #define BBFMM_SELF_INTERSECTIONS_IGNORE 0
 #define BBFMM_SELF_INTERSECTIONS_ROLLBACK 1
+/* Where the field is evaluated.  BBFMM_FOLLOW_DENSE: at every node of E (the entries above).  BBFMM_FOLLOW_SURFACE: only
+ * in the bricks of B x B x B lattice nodes (B from the environment variable BBFMM_ISO_BRICK: 4, 8 or 16, default 8, read
+ * per call) that a wavefront reaches from the seeds, as ferreus_rmt follows the surface from its seed points
+ * (seed_projection.rs:29-130, isosurface.rs:551-697): seeds are clamped to the extents, kept one per lattice cell and,
+ * with a handle's field, moved onto the level set by at most 30 Newton steps (gradients from the leaf pass, or central
+ * differences for a kernel without them, or with BBFMM_ISO_SEED_GRADIENTS=differences in the environment); the bricks
+ * that hold the 8 corners of their cells are evaluated, and every lattice edge with both ends
+ * known and on opposite sides of the isovalue sends the wavefront into every brick within (4, 2, 2) nodes in (i, j, k) of
+ * its ends, until nothing new is reached.  The mesh of an isovalue is the dense extraction, with every option above, of
+ * the field that is NaN outside the bricks visited for it: every surface component that passes through a seed's cell is
+ * complete and bit for bit that of BBFMM_FOLLOW_DENSE on the same values, a component no seed reaches is
+ * absent, and no seeds give empty meshes.  A returned field is NaN where it was not evaluated.  The field array over the
+ * box stays on the device (8 bytes per node, 16 with several isovalues, beside what clustering keeps); a lattice that does
+ * not fit is refused before any work.  seeds: n_seeds points, coordinate a of seed s at seeds[a * seeds_ld + s]; NULL with
+ * a handle's field: the handle's source points (rbf.rs:1049); a caller's values need seeds, which are then not moved. */
+#define BBFMM_FOLLOW_DENSE 0
+#define BBFMM_FOLLOW_SURFACE 1
 /* Options of the *_opts entries.  size: sizeof(bbfmm_isosurface_options) as the caller was compiled; fields beyond it
- * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0, SELF_INTERSECTIONS_IGNORE), as does every field with
- * options == NULL. */
+ * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0, SELF_INTERSECTIONS_IGNORE, FOLLOW_DENSE, no seeds), as
+ * does every field with options == NULL. */
 typedef struct bbfmm_isosurface_options {
     int64_t size;
     int32_t cluster_method; /* BBFMM_CLUSTER_* */
     int32_t finish;         /* BBFMM_FINISH_* */
     int64_t batch_bytes;    /* device memory for one batch of k-planes (<= 0: a default) */
     int32_t self_intersections; /* BBFMM_SELF_INTERSECTIONS_* */
+    int32_t follow;         /* BBFMM_FOLLOW_*; read only where size covers seeds_ld too (it lies in the former padding) */
+    const double *seeds;    /* host, n_seeds x 3 column-major with leading dimension seeds_ld, or NULL */
+    int64_t n_seeds;
+    int64_t seeds_ld;
 } bbfmm_isosurface_options;
+/* The counts of BBFMM_FOLLOW_SURFACE for mesh i, stats_out[8] (all 0 with BBFMM_FOLLOW_DENSE): seeds given, distinct seed
+ * cells, Newton steps run, seed bricks, rounds, bricks visited, nodes evaluated for this isovalue, nodes of E. */
+int bbfmm_isosurface_follow_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* The bricks visited for mesh i: dims_out[4] = B and the number of bricks along x, y and z (all 0 with BBFMM_FOLLOW_DENSE);
+ * bricks_out: NULL, or that many bytes (x fastest), 1 for a visited brick. */
+int bbfmm_isosurface_follow_bricks(const bbfmm_isosurface_result *r, int32_t i, int32_t *dims_out, uint8_t *bricks_out);
+/* Host wall time of its stages in milliseconds, ms_out[3]: seed stage, rounds of the wavefront, extraction. */
+int bbfmm_isosurface_follow_times(const bbfmm_isosurface_result *r, int32_t i, double *ms_out);
 int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                  int32_t n_isovalues, const double *drift, double *d_field_out,
                                  const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out);

@@ -9,10 +9,13 @@ with the mesh clipped to the extents and cleaned on the device: finish_ms is wha
 the finish counts are recorded.  With --self-intersections ignore,rollback the clustered raw call of every case is
 also timed with the self-intersection rollback on: rollback_ms is what it adds to the clustered call without it in the
 same run (the yardstick), and its counts are recorded; a third case, the noisy sphere (0.15 * standard_normal(seed 1) at
-resolution 0.1, a caller's field), is one where the rollback has sample points to roll back.
+resolution 0.1, a caller's field), is one where the rollback has sample points to roll back.  With --follow
+dense,surface the unclustered raw call of every case is also timed with follow="surface" from the default seeds (the
+source points), beside the dense call of the same run on the same tree, with brick sides 8 and 16: the whole call, the
+nodes evaluated of the nodes of E, the rounds, and the host time of the seed stage, the wavefront and the extraction.
 
     python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--finish raw,clipped]
-                                      [--self-intersections ignore,rollback] [--out FILE]
+                                      [--self-intersections ignore,rollback] [--follow dense,surface] [--out FILE]
 """
 import argparse
 import json
@@ -74,6 +77,27 @@ def measure_rollback(call, repeats, label, res, yardstick_ms=None):
     return rec
 
 
+def measure_follow(te, ext, res, iso, repeats, label, dense):
+    """follow="surface" with the default seeds beside the dense record of the same run, per brick side."""
+    recs = []
+    for brick in ("8", "16"):
+        os.environ["BBFMM_ISO_BRICK"] = brick
+        try:
+            t_all, (v, f, stats) = timed(lambda: te.build_isosurface(ext, res, iso, return_stats=True, follow="surface"), repeats)
+        finally:
+            del os.environ["BBFMM_ISO_BRICK"]
+        fol = {k: x for k, x in stats["follow"].items() if k != "visited"}
+        rec = {"case": label, "cluster": "none", "finish": "raw", "follow": "surface", "brick": int(brick), "resolution": res,
+               "vertices": int(len(v)), "facets": int(len(f)), "call_ms": t_all, "call_ms_dense": dense["call_ms"],
+               "facets_dense": dense["facets"], "nodes_evaluated": fol["nodes_evaluated"], "nodes": fol["nodes"],
+               "share_evaluated": fol["nodes_evaluated"] / max(fol["nodes"], 1), "rounds": fol["rounds"],
+               "seed_ms": fol["seed_ms"], "wavefront_ms": fol["wavefront_ms"], "extract_ms": fol["extract_ms"],
+               "follow_stats": fol}
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
 def measure_all(te, ext, res, iso, a, label):
     recs = []
     for method in a.clusters.split(","):
@@ -82,6 +106,8 @@ def measure_all(te, ext, res, iso, a, label):
             if finish == "raw":
                 raw = measure(te, ext, res, iso, a.repeats, label, method)
                 recs.append(raw[0])
+                if method == "none" and "surface" in a.follow.split(","):
+                    recs += measure_follow(te, ext, res, iso, a.repeats, label, raw[0])
                 if method == "average" and "rollback" in a.self_intersections.split(","):
                     recs.append(measure_rollback(lambda **kw: te.build_isosurface(ext, res, iso, **kw), a.repeats, label, res,
                                                  raw[0]["call_ms"]))
@@ -112,6 +138,7 @@ def main():
     ap.add_argument("--finish", default="raw", help="comma-separated finishes (raw first), each timed with every method")
     ap.add_argument("--self-intersections", default="ignore",
                     help="ignore,rollback: also time the clustered call with the self-intersection rollback")
+    ap.add_argument("--follow", default="dense", help="dense,surface: also time the raw call with follow='surface'")
     ap.add_argument("--out", default=None, help="JSON file for the list of results")
     a = ap.parse_args()
     import ferreus_rbf_rs_amd as F
