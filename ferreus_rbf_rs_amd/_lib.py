@@ -89,6 +89,9 @@ SIGNATURES = {
     "bbfmm_isosurface_clip_triangle": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_isosurface_topology": (ctypes.c_int, [ctypes.c_uint32, c_p, c_p, c_p]),
     "bbfmm_isosurface_cluster_tables": (ctypes.c_int, [c_p, c_p, c_p]),
+    "bbfmm_isosurface_curvature_tables": (ctypes.c_int, [c_p, c_p, c_p]),
+    "bbfmm_isosurface_curvature_weight": (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_p, c_p]),
+    "bbfmm_isosurface_curvature_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_isosurface_count": (c_i32, [c_p]),
     "bbfmm_isosurface_size": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),
     "bbfmm_isosurface_copy": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),

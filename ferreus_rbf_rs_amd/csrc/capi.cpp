@@ -15,6 +15,7 @@
 #include "ferreus_bbfmm_hip.h"
 #include "fmm_tree.hpp"
 #include "isosurface.hpp"
+#include "isosurface_curvature.hpp"
 #include "isosurface_intersect.hpp"
 #include "morton.hpp"
 
@@ -352,7 +353,7 @@ static bool iso_methods_ok(int32_t cluster, int32_t finish, int32_t self_interse
         *err = "isosurface: unknown self-intersection handling " + std::to_string(self_intersections);
         return false;
     }
-    if (cluster != BBFMM_CLUSTER_NONE && cluster != BBFMM_CLUSTER_AVERAGE) {
+    if (cluster != BBFMM_CLUSTER_NONE && cluster != BBFMM_CLUSTER_AVERAGE && cluster != BBFMM_CLUSTER_CURVATURE) {
         *err = "isosurface: unknown cluster method " + std::to_string(cluster);
         return false;
     }
@@ -418,6 +419,36 @@ int bbfmm_isosurface_cluster_tables(int32_t *neighbour_masks, int32_t *flat_hole
     for (int r = 0; r < 36; ++r)
         for (int a = 0; a < 2; ++a) flat_hole_masks[2 * r + a] = kFlatHoleMasks[r][a];
     *all14_mask = kAll14;
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_curvature_tables(int32_t *plane_pairs, int32_t *plane_phis, double *constants) {
+    using namespace bbfmm::iso;
+    if (!plane_pairs || !plane_phis || !constants) return BBFMM_BAD_ARGUMENT;
+    for (int l = 0; l < 7; ++l)
+        for (int p = 0; p < 3; ++p)
+            for (int side = 0; side < 2; ++side) {
+                const bool used = p < kCurvPlanes[l];
+                plane_pairs[(l * 3 + p) * 2 + side] = used ? kCurvPairs[l][p][side] : -1;
+                plane_phis[(l * 3 + p) * 2 + side] = used ? kCurvPhis[l][p][side] + 1 : -1;
+            }
+    constants[0] = kCurvPhi[0];
+    constants[1] = kCurvPhi[1];
+    constants[2] = kCurvEps;
+    constants[3] = kCurvMaxCot;
+    constants[4] = kCurvMaxWeight;
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_curvature_weight(const double *values, const int64_t *owner_ijk, int32_t label, const double *lo_world,
+                                      const double *spacing, double *weight_out, int32_t *fallback_out) {
+    using namespace bbfmm::iso;
+    if (!values || !owner_ijk || !lo_world || !spacing || !weight_out || label < 0 || label >= 7) return BBFMM_BAD_ARGUMENT;
+    const auto get = [values](int e) { return values[e + 1]; };
+    double w = 1.0;
+    const bool ok = curvature_weight(get, owner_ijk, label, lo_world, spacing, curvature_trig(), &w);
+    *weight_out = ok ? w : 1.0;
+    if (fallback_out) *fallback_out = ok ? 0 : 1;
     return BBFMM_OK;
 }
 
@@ -751,6 +782,12 @@ int bbfmm_isosurface_follow_bricks(const bbfmm_isosurface_result *r, int32_t i, 
 int bbfmm_isosurface_follow_times(const bbfmm_isosurface_result *r, int32_t i, double *ms_out) {
     if (!r || !ms_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
     std::memcpy(ms_out, r->meshes[i].follow_ms, sizeof(r->meshes[i].follow_ms));
+    return BBFMM_OK;
+}
+
+int bbfmm_isosurface_curvature_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    std::memcpy(stats_out, r->meshes[i].curv_stats, sizeof(r->meshes[i].curv_stats));
     return BBFMM_OK;
 }
 

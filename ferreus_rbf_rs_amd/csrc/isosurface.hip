@@ -2,6 +2,7 @@
 // grid-stride, i fastest so that neighbouring lanes read neighbouring doubles; placement by rocPRIM exclusive scans,
 // no atomics.
 #include "isosurface.hpp"
+#include "isosurface_curvature.hpp"
 
 #include <algorithm>
 #include <limits>
@@ -324,6 +325,122 @@ __global__ __launch_bounds__(kThreads) void candidates_kernel(Slab s, const doub
     }
 }
 
+// ---- curvature-weighted clusters (Request::cluster == kClusterCurvature; DESIGN.md "Curvature-weighted clusters").
+// A crossed edge is in exactly one near mask, at its near end, so the edges of all masks in node order are every crossed
+// edge once: ebase (the scan of the masks' sizes) numbers them, and their weights are computed once per isovalue, one
+// thread per edge, whatever the partition becomes afterwards.
+
+__global__ __launch_bounds__(kThreads) void edge_count_kernel(Slab s, const uint64_t *__restrict__ part, int32_t *__restrict__ ecnt) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads)
+        ecnt[n] = __popc(part_mask(part[n]));
+}
+
+// The list of crossed edges, node << 4 | edge, written where the edge's weight will be.
+__global__ __launch_bounds__(kThreads) void edge_list_kernel(Slab s, const uint64_t *__restrict__ part, const int64_t *__restrict__ ebase,
+                                                              int64_t *__restrict__ list) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        const uint64_t p = part[n];
+        if (p == kNoClusters) continue;
+        int64_t o = ebase[n];
+        for (int e = 0; e < 14; ++e)
+            if (part_label(p, e) != 15) list[o++] = (n << 4) | e;
+    }
+}
+
+// f - isovalue around one sample point of the resident field: NaN for a neighbour outside the box of E or off E (a node
+// of E that was not evaluated, or a non-finite value, is refused by the weight function itself).
+struct OwnerField {
+    const Slab &s;
+    const double *__restrict__ f;
+    double iso;
+    int64_t nk, n; // the owner's box index
+    int32_t i, j;
+    int64_t k;
+    __device__ double operator()(int e) const {
+        if (e < 0) return f[s.P + n] - iso;
+        const int32_t qi = i + kEdgeDeltas[e][0], qj = j + kEdgeDeltas[e][1];
+        const int64_t qk = k + kEdgeDeltas[e][2];
+        if (qi < 0 || qi >= s.ni || qj < 0 || qj >= s.nj || qk < 0 || qk >= nk || !in_range(s.e_rows, qk * s.nj + qj, qi))
+            return __builtin_nan("");
+        return f[s.P + n + edge_step(s, e)] - iso;
+    }
+};
+
+// One thread per crossed edge: its list entry becomes its weight (curvature_weight_for_edge(..).unwrap_or(1.0),
+// curvature_weighting.rs:259).  The owner of edge e of node n is n for e < 7 and the other end otherwise, which lies in
+// the box because the edge was crossed.
+__global__ __launch_bounds__(kThreads) void curvature_weights_kernel(Slab s, int64_t nk, const double *__restrict__ f, double iso, CurvTrig trig,
+                                                                      int64_t n_edges, double *__restrict__ weights,
+                                                                      unsigned long long *__restrict__ n_fallback) {
+    for (int64_t t = blockIdx.x * int64_t(kThreads) + threadIdx.x; t < n_edges; t += int64_t(gridDim.x) * kThreads) {
+        const int64_t entry = reinterpret_cast<const int64_t *>(weights)[t];
+        int e = static_cast<int>(entry & 15);
+        int64_t n = entry >> 4;
+        if (e >= 7) {
+            n += edge_step(s, e);
+            e = kReverseEdge[e];
+        }
+        const int64_t k = n / s.P, r = n % s.P;
+        const OwnerField get{s, f, iso, nk, n, static_cast<int32_t>(r % s.ni), static_cast<int32_t>(r / s.ni), k};
+        const int64_t ijk[3] = {s.lo[0] + r % s.ni, s.lo[1] + r / s.ni, s.lo[2] + k};
+        double w = 1.0;
+        if (!curvature_weight(get, ijk, e, s.lo_world, s.spacing, trig, &w)) {
+            w = 1.0;
+            atomicAdd(n_fallback, 1ull); // a count only
+        }
+        weights[t] = w;
+    }
+}
+
+// candidates_kernel with curvature_weighted_cluster_point (curvature_weighting.rs:242-276) for every cluster, those of
+// one edge too: the sum of w * p and of w in ascending edge order, then the sum times 1 / sum of w; a sum of w of EPS or
+// less falls back to the candidate of candidates_kernel.
+__global__ __launch_bounds__(kThreads) void candidates_curvature_kernel(Slab s, const double *__restrict__ f, double iso,
+                                                                         const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase,
+                                                                         const int64_t *__restrict__ ebase, const double *__restrict__ weights,
+                                                                         double *__restrict__ out, int64_t *__restrict__ vinfo,
+                                                                         unsigned long long *__restrict__ n_fallback) {
+    for (int64_t n = blockIdx.x * int64_t(kThreads) + threadIdx.x; n < s.nodes; n += int64_t(gridDim.x) * kThreads) {
+        int64_t v = vbase[n];
+        const uint64_t p = part[n];
+        if (p == kNoClusters) continue;
+        const int64_t k = n / s.P, r = n % s.P;
+        const int64_t ijk[3] = {s.lo[0] + r % s.ni, s.lo[1] + r / s.ni, s.lo[2] + k};
+        const double gp = f[s.P + n] - iso;
+        const uint32_t mask = part_mask(p);
+        const int64_t eb = ebase[n];
+        for (int lead = 0; lead < 14; ++lead) {
+            if (part_label(p, lead) != lead) continue;
+            double sum[3] = {0.0, 0.0, 0.0}, one[3] = {0.0, 0.0, 0.0}, wsum[3] = {0.0, 0.0, 0.0}, total = 0.0;
+            int cnt = 0;
+            for (int e = lead; e < 14; ++e) {
+                if (part_label(p, e) != lead) continue;
+                const double gq = f[s.P + n + edge_step(s, e)] - iso;
+                const double alpha = lerp_alpha(gp, gq);
+                const double w = weights[eb + __popc(mask & ((1u << e) - 1u))];
+                for (int a = 0; a < 3; ++a) {
+                    const double wu = world(s, a, ijk[a]), ww = world(s, a, ijk[a] + kEdgeDeltas[e][a]);
+                    one[a] = wu + alpha * (ww - wu);
+                    sum[a] = sum[a] + one[a];
+                    wsum[a] = wsum[a] + one[a] * w;
+                }
+                total = total + w;
+                ++cnt;
+            }
+            if (total <= kCurvEps) {
+                const double inv = 1.0 / static_cast<double>(cnt);
+                for (int a = 0; a < 3; ++a) out[3 * v + a] = cnt == 1 ? one[a] : sum[a] * inv;
+                atomicAdd(n_fallback, 1ull); // a count only
+            } else {
+                const double inv = 1.0 / total;
+                for (int a = 0; a < 3; ++a) out[3 * v + a] = wsum[a] * inv;
+            }
+            vinfo[v] = (n << 5) | (int64_t(lead) << 1) | (cnt > 1 ? 1 : 0);
+            ++v;
+        }
+    }
+}
+
 // The vertex of the cluster that holds the owned edge `lab` of node `on` at its near end; -1: none.
 __device__ __forceinline__ int64_t resolve_cluster(const Slab &s, const uint64_t *__restrict__ part, const int64_t *__restrict__ vbase,
                                                    int64_t on, int lab) {
@@ -562,8 +679,8 @@ struct IsoState {
     } while (0)
 
 // Bytes per box node of the clustered extraction: the field (8), the partition (8), cluster and facet counts (4 + 4),
-// their scans (8 + 8).
-constexpr int64_t kClusterNodeBytes = 40;
+// their scans (8 + 8); with kClusterCurvature also the scan that numbers the crossed edges (8).
+constexpr int64_t kClusterNodeBytes = 40, kCurvatureNodeBytes = 48;
 
 // The per-node state of the clustered extraction, shared by the isovalues of a call.
 struct ClusterState {
@@ -573,9 +690,11 @@ struct ClusterState {
     int64_t *vbase = nullptr, *foff = nullptr;
     void *scan_tmp = nullptr;
     size_t scan_bytes = 0;
-    unsigned long long *d_stats = nullptr; // 16 counters, then kIsectVertices and kIsectRolled of the rollback
+    unsigned long long *d_stats = nullptr; // 16 counters, then kIsectVertices and kIsectRolled of the rollback, then CurvStat
     int32_t *d_found = nullptr;
+    int64_t *ebase = nullptr; // kClusterCurvature: the first crossed edge of every node
 };
+constexpr int kStatCurv = 18, kStatCount = kStatCurv + kCurvStats;
 
 // The clustered mesh of one isovalue of the resident field (DESIGN.md "Isosurfaces on the RMT lattice", clustering).
 // inside: the extents of the self-intersection rollback, nullptr without it.
@@ -583,9 +702,32 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
                     const ClipBox *inside, Pool &pool, hipStream_t st, Mesh *mesh, std::string *err) {
     const int g = grid_for(s.nodes);
     const size_t nodes = static_cast<size_t>(s.nodes);
-    ISO_HIP(hipMemsetAsync(c.d_stats, 0, 18 * sizeof(unsigned long long), st));
+    ISO_HIP(hipMemsetAsync(c.d_stats, 0, kStatCount * sizeof(unsigned long long), st));
     near_topology_kernel<<<g, kThreads, 0, st>>>(s, nk, c.f, iso, c.part, c.ccnt, c.d_stats);
     ISO_HIP(hipGetLastError());
+    // the weights of the crossed edges: once, the near masks do not change below
+    double *weights = nullptr;
+    int64_t n_edges = 0;
+    if (c.ebase) {
+        edge_count_kernel<<<g, kThreads, 0, st>>>(s, c.part, c.fcnt);
+        ISO_HIP(hipGetLastError());
+        size_t bytes = c.scan_bytes;
+        ISO_HIP(rocprim::exclusive_scan(c.scan_tmp, bytes, c.fcnt, c.ebase, int64_t(0), nodes, rocprim::plus<int64_t>(), st));
+        int64_t last = 0;
+        int32_t lastc = 0;
+        ISO_HIP(hipMemcpyAsync(&last, c.ebase + s.nodes - 1, 8, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipMemcpyAsync(&lastc, c.fcnt + s.nodes - 1, 4, hipMemcpyDeviceToHost, st));
+        ISO_HIP(hipStreamSynchronize(st));
+        n_edges = last + lastc;
+        ISO_HIP(pool.get(&weights, static_cast<size_t>(n_edges)));
+        if (n_edges > 0) {
+            edge_list_kernel<<<g, kThreads, 0, st>>>(s, c.part, c.ebase, reinterpret_cast<int64_t *>(weights));
+            ISO_HIP(hipGetLastError());
+            curvature_weights_kernel<<<grid_for(n_edges), kThreads, 0, st>>>(s, nk, c.f, iso, curvature_trig(), n_edges, weights,
+                                                                             c.d_stats + kStatCurv + kCurvEdgeFallback);
+            ISO_HIP(hipGetLastError());
+        }
+    }
     double *verts = nullptr;
     int64_t *vinfo = nullptr, *facets = nullptr;
     uint8_t *vflag = nullptr;
@@ -611,7 +753,13 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
         ISO_HIP(pool.get(&verts, 3 * static_cast<size_t>(nv)));
         ISO_HIP(pool.get(&vinfo, static_cast<size_t>(nv)));
         ISO_HIP(pool.get(&vflag, static_cast<size_t>(nv)));
-        candidates_kernel<<<g, kThreads, 0, st>>>(s, c.f, iso, c.part, c.vbase, verts, vinfo);
+        if (c.ebase) {
+            ISO_HIP(hipMemsetAsync(c.d_stats + kStatCurv + kCurvClusterFallback, 0, sizeof(unsigned long long), st));
+            candidates_curvature_kernel<<<g, kThreads, 0, st>>>(s, c.f, iso, c.part, c.vbase, c.ebase, weights, verts, vinfo,
+                                                                c.d_stats + kStatCurv + kCurvClusterFallback);
+        } else {
+            candidates_kernel<<<g, kThreads, 0, st>>>(s, c.f, iso, c.part, c.vbase, verts, vinfo);
+        }
         ISO_HIP(hipGetLastError());
         cluster_count_kernel<<<g, kThreads, 0, st>>>(s, tt, c.f, iso, c.part, c.vbase, c.fcnt);
         ISO_HIP(hipGetLastError());
@@ -696,13 +844,22 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
             pool.put(tri_flag);
         }
     }
-    unsigned long long h_stats[18];
+    unsigned long long h_stats[kStatCount];
     ISO_HIP(hipMemcpyAsync(h_stats, c.d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+    const auto curvature_stats = [&]() { // after the stream is synchronised
+        if (!c.ebase) return;
+        mesh->curv_stats[kCurvEdges] = n_edges;
+        mesh->curv_stats[kCurvEdgeFallback] = static_cast<int64_t>(h_stats[kStatCurv + kCurvEdgeFallback]);
+        mesh->curv_stats[kCurvClusters] = nv;
+        mesh->curv_stats[kCurvClusterFallback] = static_cast<int64_t>(h_stats[kStatCurv + kCurvClusterFallback]);
+    };
     if (clip) { // clipped and cleaned while still on the device
         ISO_HIP(hipStreamSynchronize(st));
         for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
         mesh->isect_stats[kIsectVertices] = static_cast<int64_t>(h_stats[16]);
         mesh->isect_stats[kIsectRolled] = static_cast<int64_t>(h_stats[17]);
+        curvature_stats();
+        pool.put(weights);
         pool.put(vinfo);
         pool.put(vflag);
         rc = finish_device(verts, nv, facets, nf, *clip, st, mesh, err);
@@ -718,6 +875,8 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
     for (int q = 0; q < 16; ++q) mesh->stats[q] = static_cast<int64_t>(h_stats[q]);
     mesh->isect_stats[kIsectVertices] = static_cast<int64_t>(h_stats[16]);
     mesh->isect_stats[kIsectRolled] = static_cast<int64_t>(h_stats[17]);
+    curvature_stats();
+    pool.put(weights);
     pool.put(verts);
     pool.put(vinfo);
     pool.put(facets);
@@ -861,8 +1020,8 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     const bool given = req.host_field || req.d_field_in; // the field is the caller's
     const int64_t ni = lat.dims[0], nj = lat.dims[1], nk = lat.dims[2], P = ni * nj;
     const int n_iso = req.n_iso;
-    const bool cluster = req.cluster == kClusterAverage;
-    if (req.cluster != kClusterNone && !cluster) {
+    const bool cluster = req.cluster != kClusterNone, curvature = req.cluster == kClusterCurvature;
+    if (cluster && req.cluster != kClusterAverage && !curvature) {
         *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
         return BBFMM_BAD_ARGUMENT;
     }
@@ -895,10 +1054,11 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
     if (cluster) {
         size_t free_b = 0, total_b = 0;
         ISO_HIP(hipMemGetInfo(&free_b, &total_b));
-        const double need = static_cast<double>(kClusterNodeBytes) * static_cast<double>(nk + 2) * static_cast<double>(P) +
+        const int64_t node_bytes = curvature ? kCurvatureNodeBytes : kClusterNodeBytes;
+        const double need = static_cast<double>(node_bytes) * static_cast<double>(nk + 2) * static_cast<double>(P) +
                             static_cast<double>(per_plane) * static_cast<double>(nb);
         if (need > static_cast<double>(free_b)) {
-            *err = "isosurface: cluster=average keeps " + std::to_string(kClusterNodeBytes) + " bytes per node of the " +
+            *err = std::string("isosurface: cluster=") + (curvature ? "curvature" : "average") + " keeps " + std::to_string(node_bytes) + " bytes per node of the " +
                    std::to_string(ni) + " x " + std::to_string(nj) + " x " + std::to_string(nk) + " lattice box on the device, about " +
                    std::to_string(static_cast<int64_t>(need / 1048576.0)) + " MiB with one batch; " +
                    std::to_string(free_b / 1048576) + " MiB are free (use a coarser resolution or smaller extents)";
@@ -940,7 +1100,8 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         ISO_HIP(pool.get(&cs.fcnt, box));
         ISO_HIP(pool.get(&cs.vbase, box));
         ISO_HIP(pool.get(&cs.foff, box));
-        ISO_HIP(pool.get(&cs.d_stats, 18));
+        ISO_HIP(pool.get(&cs.d_stats, kStatCount));
+        if (curvature) ISO_HIP(pool.get(&cs.ebase, box));
         ISO_HIP(pool.get(&cs.d_found, 1));
         ISO_HIP(rocprim::exclusive_scan(nullptr, cs.scan_bytes, cs.ccnt, cs.vbase, int64_t(0), box, rocprim::plus<int64_t>(), st));
         ISO_HIP(pool.get(reinterpret_cast<uint8_t **>(&cs.scan_tmp), cs.scan_bytes));

@@ -1,6 +1,6 @@
 // Dense marching tetrahedra on the regularised-marching-tetrahedra (RMT) sampling lattice: the triangles of
 // ferreus_rmt's build_isosurface with ClusterMethod::None (raw, one vertex per crossed lattice edge) or
-// ClusterMethod::Average (the intersections near a sample point merged where the topology tests allow it, with the
+// ClusterMethod::Average or ClusterMethod::CurvatureWeighted (the intersections near a sample point merged where the topology tests allow it, with the
 // predicted-edge and non-manifold rollbacks and, where asked for, the self-intersection rollback), taken from every sample
 // point of the extraction domain in device passes instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
 // finished mesh of BoundaryClosure::None; boundary closure is not run).  With kFollowSurface the field is evaluated only in the
@@ -295,6 +295,7 @@ struct Mesh {
     int64_t stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // kStat*, all 0 without clustering
     int64_t finish_stats[kFinStats] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // FinishStat, all 0 with kFinishRaw
     int64_t isect_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};                   // IntersectStat, all 0 without the detector
+    int64_t curv_stats[4] = {0, 0, 0, 0};                                // CurvStat (isosurface_curvature.hpp), all 0 without kClusterCurvature
     int64_t follow_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // FollowStat, all 0 with kFollowDense
     double follow_ms[3] = {0, 0, 0};                                     // host time of the seed stage, the rounds, the extraction
     int32_t follow_dims[4] = {0, 0, 0, 0};                               // B and the bricks per axis (x, y, z)
@@ -307,7 +308,7 @@ struct Mesh {
 // the mesh edges with more than 2 faces it found.
 constexpr int kStatOverA = 6, kStatSplitA = 7, kStatRolledB = 8, kStatOverB = 12, kRoundsB = 4;
 
-enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1 };
+enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1, kClusterCurvature = 2 };
 enum Finish : int { kFinishRaw = 0, kFinishClipped = 1 };
 enum SelfIntersections : int { kSelfIntersectionsIgnore = 0, kSelfIntersectionsRollback = 1 };
 
@@ -397,10 +398,10 @@ struct Request {
     const double *host_field = nullptr; // caller's field over the box of E (then no FieldFn is used)
     double *d_field_out = nullptr;     // device array over the box of E receiving the field (NaN off E), or null
     int64_t budget_bytes = 0;          // device memory for one batch of k-planes (<= 0: the default)
-    int cluster = kClusterNone;        // kClusterAverage: the whole lattice field stays on the device (see extract)
+    int cluster = kClusterNone;        // kClusterAverage, kClusterCurvature: the whole lattice field stays on the device (see extract)
     int finish = kFinishRaw;           // kFinishClipped: every mesh goes through finish_device before its download
     const double *extents = nullptr;   // the 6 extents of the lattice, needed with kFinishClipped and the rollback
-    int self_intersections = kSelfIntersectionsIgnore; // kSelfIntersectionsRollback: with kClusterAverage, one round
+    int self_intersections = kSelfIntersectionsIgnore; // kSelfIntersectionsRollback: with clustering, one round
     const double *d_field_in = nullptr; // as host_field, already on the device (the field extract_follow filled)
     int follow = kFollowDense;         // kFollowSurface: extract_follow evaluates the bricks a wavefront reaches from the seeds
     const double *seeds = nullptr;     // host, coordinate a of seed s at seeds[a * seeds_ld + s]
@@ -411,6 +412,8 @@ struct Request {
 // Runs the extraction on `stream`.  Returns a bbfmm_status; *err holds the message of a failure.  With kClusterAverage
 // the field is evaluated in the same batches but kept over the whole box (40 bytes of state per box node, refused before
 // any work where that does not fit), and each isovalue is then clustered and marched over the whole lattice.
+// kClusterCurvature is the same with the cluster points weighted by the curvature estimate of every crossed edge
+// (isosurface_curvature.hpp; 48 bytes per box node and 8 per crossed edge).
 int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStream_t stream, std::vector<Mesh> *out,
             std::string *err);
 

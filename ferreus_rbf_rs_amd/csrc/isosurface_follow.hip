@@ -337,9 +337,9 @@ int extract_follow(const Lattice &lat, const FieldFn &field, const Request &req,
                    std::string *err) {
     const int64_t ni = lat.dims[0], nj = lat.dims[1], nk = lat.dims[2], P = ni * nj, box = P * nk;
     const int n_iso = req.n_iso;
-    const bool cluster = req.cluster == kClusterAverage;
+    const bool cluster = req.cluster != kClusterNone;
     // everything is checked before any work
-    if (req.cluster != kClusterNone && !cluster) {
+    if (cluster && req.cluster != kClusterAverage && req.cluster != kClusterCurvature) {
         *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
         return BBFMM_BAD_ARGUMENT;
     }
@@ -403,7 +403,7 @@ int extract_follow(const Lattice &lat, const FieldFn &field, const Request &req,
         ISO_HIP(hipMemGetInfo(&free_b, &total_b));
         const double fields = 8.0 * static_cast<double>(box) * (1 + (req.host_field ? 1 : 0) + (n_iso > 1 ? 1 : 0));
         const double bricks = static_cast<double>(nbr) * (17.0 + 2.0 * n_iso), chunk = static_cast<double>(chunk_nodes) * (8 + 5 * 8 + 128);
-        const double dense = (cluster ? 40.0 * static_cast<double>(nk + 2) * static_cast<double>(P) : 0.0) +
+        const double dense = (cluster ? (req.cluster == kClusterCurvature ? 48.0 : 40.0) * static_cast<double>(nk + 2) * static_cast<double>(P) : 0.0) +
                              std::min(static_cast<double>(req.budget_bytes > 0 ? req.budget_bytes : (int64_t(1) << 31)),
                                       64.0 * static_cast<double>(box));
         const double need = fields + bricks + chunk + dense;

@@ -285,8 +285,12 @@ class FmmTree:
         tests allow it, with the predicted-edge and non-manifold rollbacks (isosurface.rs:715-930); its
         self-intersection rollback (isosurface.rs:932-1007) runs with self_intersections="rollback" ("ignore", the
         default, leaves it out; see isosurface.py); the lattice field then stays on the device (40 bytes per node of the lattice
-        box), and a lattice that does not fit is refused before any work.  return_stats: (vertices, facets, stats) per
-        isovalue, stats the clustering counts of isosurface.STATS and of the rollback passes, and with finish="clipped"
+        box), and a lattice that does not fit is refused before any work; "curvature" is ClusterMethod::CurvatureWeighted,
+        the same clusters placed at the mean weighted by the curvature estimate of every crossed edge
+        (curvature_weighting.rs; 48 bytes per node; vertices agree with a host computation to rounding, not bit for bit).
+        return_stats: (vertices, facets, stats) per
+        isovalue, stats the clustering counts of isosurface.STATS and of the rollback passes, with cluster="curvature"
+        under "curvature" the counts of isosurface.CURVATURE_STATS, and with finish="clipped"
         under "finish" the counts of isosurface.FINISH_STATS, with self_intersections="rollback" under
         "self_intersections" those of isosurface.INTERSECTION_STATS.  Needs set_local_coefficients (one column) first, like
         evaluate_leaves, and a tree whose extents hold the lattice (the reference pads its evaluator by 10 resolutions,

@@ -5,12 +5,14 @@ over every sample point of the extraction domain instead of the sample points a 
 "Isosurfaces on the RMT lattice").  `finish="raw"` (the default) is that mesh as it is, before `clip_mesh_to_aabb` and
 `clean_mesh`: it reaches two lattice cells past the extents.  `finish="clipped"` runs both on the device before the
 download (isosurface.rs:1009-1021): the reference's finished mesh for `BoundaryClosure::None`.  Boundary closure
-(`ClosePositive` / `CloseNegative`), `CurvatureWeighted` clustering and vertex gradients are not implemented.  `cluster="none"` (the
+(`ClosePositive` / `CloseNegative`) and vertex gradients are not implemented.  `cluster="none"` (the
 default) is its `ClusterMethod::None`, one vertex per crossed lattice edge; `cluster="average"` its
 `ClusterMethod::Average`: the intersections near a sample point are merged into their mean where the topology tests
 allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 faces are split again
 (isosurface.rs:798-930); the reference's later self-intersection rollback (isosurface.rs:932-1007) is run with
-`self_intersections="rollback"` and left out with `"ignore"` (the default).
+`self_intersections="rollback"` and left out with `"ignore"` (the default).  `cluster="curvature"` is its
+`ClusterMethod::CurvatureWeighted`, the method its interpolator always uses (rbf.rs:1054-1064): the same clusters and
+facets, every cluster placed at the mean of its intersections weighted by the curvature estimate of their lattice edges.
 
 * lattice (lattice.rs:55-96): spacing [r/2, r*sqrt2/2, r/sqrt2], max_ijk = ceil((hi - lo) / spacing), max_ijk[0] += 1,
   world(ijk) = lo + ijk * spacing;
@@ -22,7 +24,14 @@ allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 f
 * facets: march_tets (isosurface.rs:224-283) over the keys, in key order, tetrahedra 0..5, table rows in order;
 * cluster="average": one vertex per cluster, ordered by sample point and lowest edge; triangles that two corners of
   share a vertex are dropped; `return_stats=True` adds the counts of `STATS` per mesh;
-* self_intersections="rollback", with cluster="average", after the two passes above and before the clip, one round: the
+* cluster="curvature" (curvature_weighting.rs:48-276): the weight of a crossed edge comes from the field at the 14
+  neighbours of the sample point that owns it (1 where one of them is off E, not evaluated or not finite, or the stencil
+  is degenerate), computed on the device once per isovalue; every cluster, those of one edge too, is placed at the sum
+  of w * p in ascending edge order times 1 / sum of w, or where that sum is 1e-12 or less as "average" places it.
+  Facets, vertex order and the counts of `STATS` are those of "average"; the device's trigonometric functions differ
+  from a host's in their last bits, so vertices agree with the numpy restatement to about 1e-13 of the resolution and
+  not bit for bit.  `return_stats=True` then holds the counts of `CURVATURE_STATS` under "curvature";
+* self_intersections="rollback", with cluster="average" or "curvature", after the two passes above and before the clip, one round: the
   triangles on true self-intersections (mesh_intersections.rs:125-208; `triangle_pair` is the predicate) among the
   facets with every corner inside the extents, found on the device through a uniform grid over their bounding boxes;
   their vertices that are clusters of several lattice edges; the sample points that own those go back to one vertex
@@ -125,7 +134,9 @@ def tables() -> dict:
             "MT_TABLE": [mt[c, 1:1 + 3 * mt[c, 0]].reshape(-1, 3).tolist() for c in range(16)]}
 
 
-CLUSTER_METHODS = {"none": 0, "average": 1}
+CLUSTER_METHODS = {"none": 0, "average": 1, "curvature": 2}
+# return_stats with cluster="curvature" (bbfmm_isosurface_curvature_stats)
+CURVATURE_STATS = ("edges", "edge_fallbacks", "clusters", "cluster_fallbacks")
 # return_stats: sample points per topology case, then the two rollback passes (bbfmm_isosurface_stats)
 STATS = ("closed", "multi_hole", "flat_hole", "multi_surface", "simple", "incomplete")
 
@@ -206,6 +217,41 @@ def cluster_tables() -> dict:
     return {"NEIGHBOUR_MASKS": nb.tolist(), "FLAT_HOLE_MASKS": fh.reshape(36, 2).tolist(), "ALL14_MASK": all14.value}
 
 
+def curvature_tables() -> dict:
+    """The curvature-weighting tables the library holds (ferreus_rmt/src/constants.rs, curvature_weighting.rs): the rows
+    of the 7 owned edges, the angles written out as numbers."""
+    lib = L.load()
+    pairs, phis, c = np.zeros(42, np.int32), np.zeros(42, np.int32), np.zeros(5)
+    rc = lib.bbfmm_isosurface_curvature_tables(pairs.ctypes.data, phis.ctypes.data, c.ctypes.data)
+    assert rc == L.OK
+    pairs, phis = pairs.reshape(7, 3, 2), phis.reshape(7, 3, 2)
+    rows = [[p for p in range(3) if pairs[l, p, 0] >= 0] for l in range(7)]
+    return {"NEIGHBOUR_EDGE_PLANE_PAIRS": [[pairs[l, p].tolist() for p in rows[l]] for l in range(7)],
+            "NEIGHBOUR_EDGE_PLANE_PHIS": [[[float(c[q - 1]) for q in phis[l, p]] for p in rows[l]] for l in range(7)],
+            "PHI_1": float(c[0]), "PHI_2": float(c[1]), "EPS": float(c[2]), "MAX_COT_THETA": float(c[3]),
+            "MAX_CURVATURE_WEIGHT": float(c[4])}
+
+
+def curvature_weight(values, owner_ijk, label, lo_world, spacing):
+    """(weight, fallback) of one crossed edge by the function the device runs (host only; curvature_weight_for_edge,
+    curvature_weighting.rs:48-234): the owned edge `label` (0..6) of the sample point owner_ijk on the lattice
+    world(ijk) = lo_world + ijk * spacing.  values: f - isovalue at the owner, then at its 14 neighbours, NaN for a
+    missing one.  fallback True: the reference gives None and the weight is 1."""
+    lib = L.load()
+    v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+    o = np.ascontiguousarray(np.asarray(owner_ijk, dtype=np.int64).reshape(-1))
+    lo = np.ascontiguousarray(np.asarray(lo_world, dtype=np.float64).reshape(-1))
+    sp = np.ascontiguousarray(np.asarray(spacing, dtype=np.float64).reshape(-1))
+    if v.shape != (15,) or o.shape != (3,) or lo.shape != (3,) or sp.shape != (3,):
+        raise ValueError("values must hold 15 numbers, owner_ijk, lo_world and spacing 3 each")
+    w, back = ctypes.c_double(), ctypes.c_int32()
+    rc = lib.bbfmm_isosurface_curvature_weight(v.ctypes.data, o.ctypes.data, int(label), lo.ctypes.data, sp.ctypes.data,
+                                               ctypes.byref(w), ctypes.byref(back))
+    if rc != L.OK:
+        raise ValueError("label must be one of the 7 owned edges, 0..6")
+    return w.value, bool(back.value)
+
+
 def topology(near_mask, neighbour_values=None):
     """(case, cluster_of_edge[14]) of a 14-bit near mask by the function the device runs (test_topology,
     topology.rs:232-314): case 0 closed, 1 multi-hole, 2 flat-hole, 3 multi-surface, 4 simple; cluster_of_edge the lowest
@@ -260,7 +306,13 @@ def _intersection_stats(lib, res, i):
     return {name: int(s[q]) for q, name in enumerate(INTERSECTION_STATS)}
 
 
-def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0):
+def _curvature_stats(lib, res, i):
+    s = np.zeros(len(CURVATURE_STATS), dtype=np.int64)
+    lib.bbfmm_isosurface_curvature_stats(res, i, s.ctypes.data)
+    return {name: int(s[q]) for q, name in enumerate(CURVATURE_STATS)}
+
+
+def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0, method=0):
     out = []
     for i in range(lib.bbfmm_isosurface_count(res)):
         nv, nf = ctypes.c_int64(), ctypes.c_int64()
@@ -276,6 +328,8 @@ def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0):
                 st["self_intersections"] = _intersection_stats(lib, res, i)
             if follow:
                 st["follow"] = _follow_stats(lib, res, i)
+            if method == CLUSTER_METHODS["curvature"]:
+                st["curvature"] = _curvature_stats(lib, res, i)
             out.append((v, f, st))
         else:
             out.append((v, f))
@@ -324,7 +378,7 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_last_error(tree._h).decode())
-        meshes = _meshes(lib, res, return_stats, fin, isect, fol)
+        meshes = _meshes(lib, res, return_stats, fin, isect, fol, method)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
@@ -337,9 +391,10 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
                             cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
                             seeds=None):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
-    current device (or the tree's).  cluster: "none" or "average", finish: "raw" or "clipped", self_intersections:
+    current device (or the tree's).  cluster: "none", "average" or "curvature", finish: "raw" or "clipped", self_intersections:
     "ignore" or "rollback" (see the module); return_stats: (vertices, facets, stats) per mesh, stats the clustering
-    counts (all 0 with "none"), with finish="clipped" under "finish" the counts of FINISH_STATS and with
+    counts (all 0 with "none"), with cluster="curvature" under "curvature" the counts of CURVATURE_STATS, with
+    finish="clipped" under "finish" the counts of FINISH_STATS and with
     self_intersections="rollback" under "self_intersections" those of INTERSECTION_STATS.  follow="surface": only the
     values in the bricks the wavefront reaches from `seeds` ((n, 3), required, used as they are) are looked at."""
     lib = L.load()
@@ -364,7 +419,7 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
     try:
         if rc != L.OK:
             _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface extraction failed")
-        return _meshes(lib, res, return_stats, fin, isect, fol)
+        return _meshes(lib, res, return_stats, fin, isect, fol, method)
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)

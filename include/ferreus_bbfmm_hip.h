@@ -223,7 +223,8 @@ int bbfmm_evaluate_leaves_with_gradients(bbfmm_handle *h, const double *w, int64
                                          int64_t *bad_point_index);
 
 /* ---- Isosurfaces: dense marching tetrahedra on the RMT sampling lattice (ferreus_rmt build_isosurface with
- * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE its ClusterMethod::Average; the raw mesh
+ * ClusterMethod::None, or with the *_ex entries and BBFMM_CLUSTER_AVERAGE / BBFMM_CLUSTER_CURVATURE its
+ * ClusterMethod::Average / CurvatureWeighted; the raw mesh
  * before clipping and cleaning, or with the *_opts entries and BBFMM_FINISH_CLIPPED the mesh clipped to the extents and
  * cleaned on the device, which is the reference's finished mesh for BoundaryClosure::None; its self-intersection
  * rollback is run with BBFMM_SELF_INTERSECTIONS_ROLLBACK in the options.  Boundary closure (ClosePositive /
@@ -262,6 +263,16 @@ int bbfmm_isosurfaces_from_values(bbfmm_handle *h, const double *values, const d
  * work with BBFMM_BAD_ARGUMENT.  The meshes do not depend on batch_bytes. */
 #define BBFMM_CLUSTER_NONE 0
 #define BBFMM_CLUSTER_AVERAGE 1
+/* BBFMM_CLUSTER_CURVATURE: ClusterMethod::CurvatureWeighted, the method the reference's interpolator always uses
+ * (rbf.rs:1054-1064).  Clusters, facets and the counts above are those of BBFMM_CLUSTER_AVERAGE; the point of every
+ * cluster, those of one edge too, is the sum of w * p over its intersections in ascending edge order times 1 / sum of w
+ * (curvature_weighting.rs:242-276), w the curvature weight of the crossed edge (curvature_weighting.rs:48-234) from the
+ * field at the 14 neighbours of the edge's owner, 1 where that stencil is incomplete (a neighbour outside the extraction
+ * nodes, not evaluated or not finite) or degenerate; a sum of w of 1e-12 or less gives the point of
+ * BBFMM_CLUSTER_AVERAGE.  The weights are computed on the device once per isovalue.  The device's trigonometric functions
+ * differ from a host's in their last bits, so vertices agree with a host computation to some 1e-13 of the resolution, not
+ * bit for bit; facets are exact.  48 bytes per node of the box and 8 per crossed edge stay on the device. */
+#define BBFMM_CLUSTER_CURVATURE 2
 int bbfmm_build_isosurfaces_ex(bbfmm_handle *h, const double *extents, double resolution, const double *isovalues,
                                int32_t n_isovalues, const double *drift, double *d_field_out, int64_t batch_bytes,
                                int32_t cluster_method, bbfmm_isosurface_result **out);
@@ -273,6 +284,10 @@ int bbfmm_isosurfaces_from_values_ex(bbfmm_handle *h, const double *values, cons
  * clustered)]; [6] mesh edges with more than 2 faces before pass A, [7] clusters pass A split; [8..12) sample points
  * rolled back in rounds 1..4 of pass B, [12..16) mesh edges with more than 2 faces those rounds found. */
 int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* The counts of BBFMM_CLUSTER_CURVATURE for mesh i, stats_out[4] (all 0 with the other methods): crossed edges weighted,
+ * of those the edges with the fallback weight 1, clusters placed (the vertices before the clip), of those the clusters
+ * whose weights summed to 1e-12 or less. */
+int bbfmm_isosurface_curvature_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
 /* Finishing.  BBFMM_FINISH_RAW: the marching-tetrahedra mesh as it is (the entries above): it reaches two lattice cells
  * past the extents and ends in open triangles there.  BBFMM_FINISH_CLIPPED: clip_mesh_to_aabb (aabb_clipping.rs:55-105)
  * and clean_mesh (mesh_cleanup.rs:32-96) of ferreus_rmt run on the device before the one download, with
@@ -284,7 +299,7 @@ int bbfmm_isosurface_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t 
 #define BBFMM_FINISH_CLIPPED 1
 /* Self-intersections.  BBFMM_SELF_INTERSECTIONS_IGNORE: the clustered mesh as the two passes above leave it (averaging can
  * pull two sheets of a complex surface through each other).  BBFMM_SELF_INTERSECTIONS_ROLLBACK, with
- * BBFMM_CLUSTER_AVERAGE (nothing is done with BBFMM_CLUSTER_NONE: the mesh and the counts are those without it): after
+ * BBFMM_CLUSTER_AVERAGE or BBFMM_CLUSTER_CURVATURE (nothing is done with BBFMM_CLUSTER_NONE: the mesh and the counts are those without it): after
  * pass B and before the clip, one round of the reference's third guard.  The triangles on true self-intersections
  * (is_true_self_intersection, mesh_intersections.rs:125-159) among the facets with every corner inside the extents are
  * found on the device, by a uniform grid over the facets' bounding boxes instead of an R-tree; their vertices that are
@@ -384,6 +399,16 @@ int bbfmm_isosurface_topology(uint32_t near_mask, const double *neighbour_values
                               int32_t *cluster_of_edge);
 /* The clustering tables as the product holds them: NEIGHBOUR_MASKS (14), FLAT_HOLE_MASKS (36 x 2), ALL14_MASK. */
 int bbfmm_isosurface_cluster_tables(int32_t *neighbour_masks, int32_t *flat_hole_masks, int32_t *all14_mask);
+/* The curvature-weighting tables as the product holds them: rows 0..6 of NEIGHBOUR_EDGE_PLANE_PAIRS (7 x 3 x 2 edge
+ * labels, an unused third plane -1) and of NEIGHBOUR_EDGE_PLANE_PHIS (7 x 3 x 2: 1 for PHI_1, 2 for PHI_2, -1 unused);
+ * constants[5]: PHI_1, PHI_2, EPS, MAX_COT_THETA, MAX_CURVATURE_WEIGHT. */
+int bbfmm_isosurface_curvature_tables(int32_t *plane_pairs, int32_t *plane_phis, double *constants);
+/* Host only: the weight function the device runs (curvature_weight_for_edge, curvature_weighting.rs:48-234), for the
+ * owned edge `label` (0..6) of the sample point owner_ijk[3] on the lattice world(ijk) = lo_world + ijk * spacing.
+ * values[15]: f - isovalue at the owner, then at its 14 neighbours (EDGE_DELTAS order), NaN for a missing one.
+ * weight_out: the weight, 1 where the reference gives None; fallback_out (may be NULL): 1 in that case. */
+int bbfmm_isosurface_curvature_weight(const double *values, const int64_t *owner_ijk, int32_t label, const double *lo_world,
+                                      const double *spacing, double *weight_out, int32_t *fallback_out);
 int32_t bbfmm_isosurface_count(const bbfmm_isosurface_result *r);
 int bbfmm_isosurface_size(const bbfmm_isosurface_result *r, int32_t i, int64_t *n_vertices, int64_t *n_facets);
 int bbfmm_isosurface_copy(const bbfmm_isosurface_result *r, int32_t i, double *vertices, int64_t *facets);

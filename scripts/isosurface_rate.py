@@ -13,9 +13,15 @@ resolution 0.1, a caller's field), is one where the rollback has sample points t
 dense,surface the unclustered raw call of every case is also timed with follow="surface" from the default seeds (the
 source points), beside the dense call of the same run on the same tree, with brick sides 8 and 16: the whole call, the
 nodes evaluated of the nodes of E, the rounds, and the host time of the seed stage, the wavefront and the extraction.
+With "curvature" among the --clusters the field of every case is also fetched once and each clustered method is timed on
+it as a caller's field (source "values": the upload and the extraction, no field pass, so the methods differ by what
+their kernels cost): curvature_ms is what "curvature" adds to "average" in the same run (the yardstick: the parent's
+path), and its counts are recorded.  --cases picks the cases, --values-only leaves the calls on the tree out (the run to
+put under a kernel trace for the share of curvature_weights_kernel).
 
     python scripts/isosurface_rate.py [--repeats 3] [--clusters none,average] [--finish raw,clipped]
                                       [--self-intersections ignore,rollback] [--follow dense,surface] [--out FILE]
+                                      [--cases albatite,cloud] [--values-only]
 """
 import argparse
 import json
@@ -98,9 +104,33 @@ def measure_follow(te, ext, res, iso, repeats, label, dense):
     return recs
 
 
+def measure_values(te, ext, res, iso, repeats, label, methods):
+    """The clustered methods on the tree's field taken as a caller's field: the extraction without the field pass."""
+    from ferreus_rbf_rs_amd import isosurface as I
+    _, field = te.build_isosurfaces(ext, res, [iso], return_field=True)
+    recs, yardstick = [], None
+    for method in methods:
+        t, (v, f, stats) = timed(lambda: I.isosurface_from_values(field, ext, res, iso, tree=te, cluster=method, return_stats=True),
+                                 repeats)
+        rec = {"case": label, "source": "values", "cluster": method, "resolution": res, "lattice_shape": list(field.shape),
+               "vertices": int(len(v)), "facets": int(len(f)), "call_ms": t, "stats": stats}
+        if method == "average":
+            yardstick = t
+        if method == "curvature" and yardstick is not None:
+            rec["call_ms_average"], rec["curvature_ms"] = yardstick, t - yardstick
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
 def measure_all(te, ext, res, iso, a, label):
     recs = []
-    for method in a.clusters.split(","):
+    methods = a.clusters.split(",")
+    if "curvature" in methods:
+        recs += measure_values(te, ext, res, iso, a.repeats, label, [m for m in methods if m != "none"])
+    if a.values_only:
+        return recs
+    for method in methods:
         raw = None
         for finish in a.finish.split(","):
             if finish == "raw":
@@ -140,43 +170,47 @@ def main():
                     help="ignore,rollback: also time the clustered call with the self-intersection rollback")
     ap.add_argument("--follow", default="dense", help="dense,surface: also time the raw call with follow='surface'")
     ap.add_argument("--out", default=None, help="JSON file for the list of results")
+    ap.add_argument("--cases", default="albatite,cloud", help="comma-separated cases to run")
+    ap.add_argument("--values-only", action="store_true", help="with curvature among the clusters: only the caller's-field timings")
     a = ap.parse_args()
     import ferreus_rbf_rs_amd as F
     from ferreus_rbf_rs_amd import solvers as S
     from ferreus_rbf_rs_amd.ddm import DDMParams, InterpolantSettings, SchwarzPreconditioner
     from oracle import bbfmm_oracle as O
     recs = []
-    # albatite, Spheroidal order 3, range 50, sill 10, fitted on the device
-    z = np.load(os.path.join(ROOT, "tests", "golden", "albatite_SD_points.npz"))
-    pts, vals = np.ascontiguousarray(z["rows"][:, :3]), z["rows"][:, 3].copy()
-    kid = O.KERNEL_IDS["Spheroidal3Rbf"]
-    kp = F.KernelParams(F.KernelType(kid), base_range=50.0, total_sill=10.0)
-    tree = F.FmmTree(pts, 7, kp, True, True)
-    pre = SchwarzPreconditioner(tree, pts, InterpolantSettings(kid, 3, None, 0.0, 50.0, 10.0), DDMParams())
-    op = S.RbfSystemOperator(tree, 0, pre.monomial_matrix, 0.0)
-    x, _ = S.fgmres(op, vals.copy(), pre, None, 20, 5, S.FittingAccuracy(0.01, S.FittingAccuracyType.Absolute))
-    res = 5.0
-    ext = np.concatenate([pts.min(0), pts.max(0)])
-    te = F.FmmTree(pts, 7, kp, True, False, extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
-    te.set_weights(x[:, None].copy())
-    te.set_local_coefficients(x[:, None].copy())
-    recs += measure_all(te, ext, res, 0.0, a, "albatite_spheroidal_r5")
-    del te, tree, pre
-    # 1M points on and around a sphere of radius 1, Linear kernel, random weights (a smooth field, not a fit)
-    rng = np.random.default_rng(1)
-    n = 1_000_000
-    p = rng.normal(size=(n, 3))
-    p = p / np.linalg.norm(p, axis=1)[:, None] * rng.uniform(0.5, 1.5, (n, 1))
-    w = rng.standard_normal((n, 1)) / n
-    res = 0.02
-    ext = np.concatenate([p.min(0), p.max(0)])
-    t1 = F.FmmTree(p, 7, F.KernelParams(F.FmmKernelType.LinearRbf), True, False,
-                   extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
-    t1.set_weights(w)
-    t1.set_local_coefficients(w)
-    fmid = float(np.median(t1.evaluate_leaves(None, p[:2000])))
-    recs += measure_all(t1, ext, res, fmid, a, "cloud_1M_linear")
-    del t1
+    if "albatite" in a.cases.split(","):
+        # albatite, Spheroidal order 3, range 50, sill 10, fitted on the device
+        z = np.load(os.path.join(ROOT, "tests", "golden", "albatite_SD_points.npz"))
+        pts, vals = np.ascontiguousarray(z["rows"][:, :3]), z["rows"][:, 3].copy()
+        kid = O.KERNEL_IDS["Spheroidal3Rbf"]
+        kp = F.KernelParams(F.KernelType(kid), base_range=50.0, total_sill=10.0)
+        tree = F.FmmTree(pts, 7, kp, True, True)
+        pre = SchwarzPreconditioner(tree, pts, InterpolantSettings(kid, 3, None, 0.0, 50.0, 10.0), DDMParams())
+        op = S.RbfSystemOperator(tree, 0, pre.monomial_matrix, 0.0)
+        x, _ = S.fgmres(op, vals.copy(), pre, None, 20, 5, S.FittingAccuracy(0.01, S.FittingAccuracyType.Absolute))
+        res = 5.0
+        ext = np.concatenate([pts.min(0), pts.max(0)])
+        te = F.FmmTree(pts, 7, kp, True, False, extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
+        te.set_weights(x[:, None].copy())
+        te.set_local_coefficients(x[:, None].copy())
+        recs += measure_all(te, ext, res, 0.0, a, "albatite_spheroidal_r5")
+        del te, tree, pre
+    if "cloud" in a.cases.split(","):
+        # 1M points on and around a sphere of radius 1, Linear kernel, random weights (a smooth field, not a fit)
+        rng = np.random.default_rng(1)
+        n = 1_000_000
+        p = rng.normal(size=(n, 3))
+        p = p / np.linalg.norm(p, axis=1)[:, None] * rng.uniform(0.5, 1.5, (n, 1))
+        w = rng.standard_normal((n, 1)) / n
+        res = 0.02
+        ext = np.concatenate([p.min(0), p.max(0)])
+        t1 = F.FmmTree(p, 7, F.KernelParams(F.FmmKernelType.LinearRbf), True, False,
+                       extents=list(ext[:3] - 10 * res) + list(ext[3:] + 10 * res))
+        t1.set_weights(w)
+        t1.set_local_coefficients(w)
+        fmid = float(np.median(t1.evaluate_leaves(None, p[:2000])))
+        recs += measure_all(t1, ext, res, fmid, a, "cloud_1M_linear")
+        del t1
     if "rollback" in a.self_intersections.split(",") and "average" in a.clusters.split(","):
         recs += noisy_sphere(a)
     if a.out:
