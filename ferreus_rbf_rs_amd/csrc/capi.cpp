@@ -1327,6 +1327,16 @@ int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int6
     return BBFMM_OK;
 }
 
+// The stage-1 operators with their x pairs, y pairs and column-block kinds (FmmTree::debug_m2l_pairs_axes).
+int bbfmm_debug_m2l_pairs_axes(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out) {
+    if (!h || !n_out) return BBFMM_BAD_ARGUMENT;
+    std::vector<int32_t> v;
+    h->tree.debug_m2l_pairs_axes(&v);
+    *n_out = static_cast<int64_t>(v.size());
+    if (out) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap, *n_out), out);
+    return BBFMM_OK;
+}
+
 // The same for the stage-2 operators (FmmTree::debug_m2l_pairs_stage2).
 int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on) {
     if (!h || !n_out) return BBFMM_BAD_ARGUMENT;

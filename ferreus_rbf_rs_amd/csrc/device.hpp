@@ -50,6 +50,8 @@ struct M2lClass {
     const int32_t *row_dst2; // parity-basis stage 1: the same for the partner Rt of the row's transfer vector, which
                              // receives a - b where row_dst receives a + b; -1: the row belongs to a single
     const int32_t *blk_t0;   // r_pad16 / kM2lS1Block: first tpos of each column block (| kM2lBlkTwoDst)
+    int32_t yb0;             // parity basis of two axes: the column blocks from yb0 on walk the contraction in y order
+                             // ([ee | oe | eo | oo]: their pairs are (t, R_y t)); r_pad16 / kM2lS1BlockPairs when there are none
     int32_t n_rows;          // exact number of tall rows
     int32_t r_pad16;         // n_rows rounded up to a multiple of kM2lS1Block
     int32_t n_t;             // number of transfer vectors of this class (189 in 3-D)
@@ -113,11 +115,21 @@ int launch_l2l(const ChebRef &ch, int K, int64_t C, const int32_t *cells, int n_
 // (tile.first indexes tile_idx; a partition's compact source tiles)
 void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int max_slot_t, int K, int64_t C, const double *M, double *cbuf,
-                       int64_t cbuf_len, hipStream_t s, bool own_blocks = false, int max_blocks = 8, int ne16 = 0);
+                       int64_t cbuf_len, hipStream_t s, bool own_blocks = false, int max_blocks = 8, int ne16 = 0, int s_ee = 0,
+                       int s_eo = 0);
 // Stage 1 in the parity basis (ne16 > 0 above: M is Mp, n_pad is n_par, the first ne16 contraction indices are the even
 // part): Mp[cell] = [M_e | pad | M_o | pad] of every cell and right-hand side; the pads are never written.
+// (s_ee, s_eo > 0: the basis of two axes, [ee | eo | oe | oo] with s_ee and s_eo = s_oe steps of 16 in the first three parts;
+// the blocks from M2lClass::yb0 on walk it as [ee | oe | eo | oo])
 void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne16, int n_e, int n_o, int p, int64_t rows,
                        hipStream_t s);
+// The same for the parity basis of axes 0 and 1: Mp[row] = [M_ee | M_eo | M_oe | M_oo], part ab at off.v[2 a + b] (each padded to
+// 16); p2 = nodes per value of the second digit (n / p^2).
+struct M2lParityOffsets {
+    int32_t v[4];
+};
+void launch_m2l_parity2(const double *M, int n_pad, double *Mp, int n_par, M2lParityOffsets off, int p, int p2, int64_t rows,
+                        hipStream_t s);
 void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
                        const uint16_t *qlist, double *L, hipStream_t s, bool allow_ksplit = true);
@@ -162,6 +174,8 @@ struct M2lAssembleClass {
     // parity basis of stage 2 (u_npar > 0): tgt lists the transfer vectors that own operator rows (row = operator row),
     // u_all is u_rows x u_npar with the odd part from column u_ne16; u_ne / u_no as n_e / n_o
     int32_t u_npar, u_ne16, u_rows, u_ne, u_no;
+    int32_t s1_axes;         // 2: stage 1 in the parity basis of axes 0 and 1, its four parts at the rows s1_off of vt_all
+    M2lParityOffsets s1_off;
 };
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s);

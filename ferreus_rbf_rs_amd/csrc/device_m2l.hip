@@ -100,6 +100,10 @@ __device__ inline void dma16s(const double *sbase, unsigned voff_bytes, unsigned
 // cell), OP = [Vt_e | pad | Vt_o | pad]; the first in_len / 16 steps of a column block are the even part a, the rest
 // the odd part b.  At the boundary the accumulators move to a second set, and the epilogue stores a + b through
 // row_dst and, for the blocks that hold pairs, a - b through row_dst2: one product serves t and Rt.
+// Two axes (in_len also carries s_ee and s_eo): IN = [M_ee | M_eo | M_oe | M_oo], each part padded to 16.  A block below
+// cls.yb0 walks the parts in storage order (a over the x-even parts ee, eo: its pairs are (t, R_x t)); a block from yb0 on
+// walks ee, oe, eo, oo (a over the y-even parts: its pairs are (t, R_y t)).  eo and oe are equally long, so the boundary
+// between a and b is the same step in both orders; a single's a + b does not depend on the order.
 template <int NG16, int STAGE, int MINW, bool PAIRS = false>
 __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restrict__ classes,
                                                   const M2lTileDesc *__restrict__ tiles, int n_pad, int g16_0,
@@ -134,7 +138,8 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     const int q_lo = STAGE == 2 ? tile.q_count * zk / ksplit : 0;
     const int nq = STAGE == 1 ? n_pad / 16 : STAGE == 2 ? tile.q_count * (zk + 1) / ksplit - q_lo : (int)(in_len / 16);
     const uint16_t *ql = qlist + tile.q_first + q_lo;
-    const int nq_e = PAIRS ? (int)(in_len / 16) : 0;
+    const int nq_e = PAIRS ? (int)(in_len & 0xffffffff) / 16 : 0;
+    const int s_ee = PAIRS ? (int)(in_len >> 32) & 0xffff : 0, s_eo = PAIRS ? (int)(in_len >> 48) : 0; // (0, 0: one axis)
     if (zb0 >= zb1) return;
     // stage 2 with gridDim.z > 1: the z workgroups of a tile take adjacent chunks of NG16 column groups
     const int g16 = g16_0 + (STAGE >= 2 ? zc * NG16 : 0);
@@ -186,7 +191,13 @@ __global__ __launch_bounds__(512, MINW) void m2l_gemm_k4(const M2lClass *__restr
     // step s of the flattened (column block, contraction step) loop
     auto stage = [&](int sidx, int buf) {
         const int zb = zb0 + sidx / nq, qi = sidx - (sidx / nq) * nq;
-        const int q = STAGE == 2 ? (int)ql[qi] : qi;
+        int q = STAGE == 2 ? (int)ql[qi] : qi;
+        if constexpr (PAIRS) {
+            if (zb >= cls.yb0) { // y order: the parts eo and oe change places (wave-uniform, scalar arithmetic)
+                if (qi >= s_ee && qi < s_ee + s_eo) q = qi + s_eo;
+                else if (qi >= s_ee + s_eo && qi < s_ee + 2 * s_eo) q = qi - s_eo;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < NCH; ++i)
             if (wave + 8 * i < OP_CHUNKS)
@@ -510,7 +521,7 @@ static void m2l_dispatch_chunks(int total_groups, const M2lClass *classes, const
 // blockIdx.z walks the column blocks, the chunk plan splits a block.
 void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                        int n_pad, int max_slot_t, int K, int64_t C, const double *M, double *cbuf, int64_t cbuf_len,
-                       hipStream_t s, bool own_blocks, int max_blocks, int ne16) {
+                       hipStream_t s, bool own_blocks, int max_blocks, int ne16, int s_ee, int s_eo) {
     if (n_tiles == 0) return;
     int slot_t = 16; // LDS slot-table width: power of two covering the transfer vectors of any block
     while (slot_t < max_slot_t) slot_t *= 2;
@@ -535,8 +546,10 @@ void launch_m2l_stage1(const M2lClass *classes, const M2lTileDesc *tiles, const 
         }
     }
     const int n_colblocks = own_blocks ? 1 : zsplit; // tiles that name their own blocks are not split further
-    if (ne16 > 0) { // parity basis: one instance, a whole column block per walk step (in_len carries the even part's length)
-        m2l_gemm_launch<kM2lS1BlockPairs / 16, 1, 1, true>(classes, tiles, n_tiles, n_pad, 0, n_colblocks, K, C, M, ne16, cbuf, cbuf_len,
+    if (ne16 > 0) { // parity basis: one instance, a whole column block per walk step (in_len carries the even part's length
+        // and, for two axes, the steps of the parts ee and eo)
+        const int64_t packed = static_cast<int64_t>(ne16) | (static_cast<int64_t>(s_ee & 0xffff) << 32) | (static_cast<int64_t>(s_eo & 0x7fff) << 48);
+        m2l_gemm_launch<kM2lS1BlockPairs / 16, 1, 1, true>(classes, tiles, n_tiles, n_pad, 0, n_colblocks, K, C, M, packed, cbuf, cbuf_len,
                                                       nullptr, slot_t, tile_idx, s);
         return;
     }
@@ -876,6 +889,40 @@ void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne
                        n_o, p, p1, rows);
 }
 
+// The multipoles in the parity basis of axes 0 and 1, the two-level butterfly in one pass: a representative (i0, i1 <
+// ceil(p/2), r < p2) with node m = (i0 p + i1) p2 + r reads M at m, rho_x m, rho_y m, rho_x rho_y m and writes
+// ee = (m + x) + (y + xy), eo = (m + x) - (y + xy), oe = (m - x) + (y - xy), oo = (m - x) - (y - xy); on a centre plane of an
+// odd order the reflected node is the node itself and the part that is odd along that axis does not exist (the even
+// part keeps the value once, as m2l_parity_kernel does).  Part ab holds its representatives in the order (i0, i1, r).
+__global__ __launch_bounds__(256) void m2l_parity2_kernel(const double *__restrict__ M, int n_pad, double *__restrict__ Mp, int n_par,
+                                                          M2lParityOffsets off, int p, int p2, int64_t rows) {
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double *src = M + row * n_pad;
+    double *dst = Mp + row * n_par;
+    const int h = (p + 1) / 2, f = p / 2;
+    for (int e = threadIdx.x & 63; e < h * h * p2; e += 64) {
+        const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
+        const int m = (i0 * p + i1) * p2 + r;
+        const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2; // 0 on the centre planes
+        const bool cx = i0 >= f, cy = i1 >= f;
+        const double v = src[m], vx = src[m + dx], vy = src[m + dy], vxy = src[m + dx + dy];
+        const double e0 = cx ? v : v + vx, e1 = cx ? vy : vy + vxy, o0 = v - vx, o1 = vy - vxy;
+        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r; // position among the y-even / y-odd representatives
+        dst[off.v[0] + je] = cy ? e0 : e0 + e1;
+        if (!cy) dst[off.v[1] + jo] = e0 - e1;
+        if (!cx) dst[off.v[2] + je] = cy ? o0 : o0 + o1;
+        if (!cx && !cy) dst[off.v[3] + jo] = o0 - o1;
+    }
+}
+
+void launch_m2l_parity2(const double *M, int n_pad, double *Mp, int n_par, M2lParityOffsets off, int p, int p2, int64_t rows,
+                        hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(m2l_parity2_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, M, n_pad, Mp, n_par, off, p, p2,
+                       rows);
+}
+
 // Slot segments of absent pairs: 16 lanes per segment, 16 bytes per lane and round.
 __global__ __launch_bounds__(256) void m2l_zero_segments_kernel(const int32_t *__restrict__ segs, int64_t n_segs,
                                                                 double *__restrict__ cbuf, int64_t cbuf_len) {
@@ -1001,6 +1048,40 @@ __global__ __launch_bounds__(256) void assemble_vt_parity_kernel(M2lAssembleClas
     }
 }
 
+// The same in the parity basis of axes 0 and 1 (m2l_parity2_kernel's enumeration): one thread per (row-owning transfer
+// vector, representative of ee); the factors 1/2 and 1/4 are exact.
+__global__ __launch_bounds__(256) void assemble_vt_parity2_kernel(M2lAssembleClass c, int n, const double *__restrict__ ops,
+                                                                  const int32_t *__restrict__ invperm, double *__restrict__ vt_all) {
+    const int p = c.p, p2 = n / (p * p), h = (p + 1) / 2, f = p / 2, n_ee = h * h * p2;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(c.n_src) * n_ee) return;
+    const int pos = static_cast<int>(t / n_ee), e = static_cast<int>(t % n_ee);
+    const M2lAssembleTv tv = c.src[pos];
+    const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
+    const int m = (i0 * p + i1) * p2 + r;
+    const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2;
+    const bool cx = i0 >= f, cy = i1 >= f;
+    const int32_t *inv = invperm + static_cast<int64_t>(tv.perm) * n;
+    const double *s0 = ops + tv.vt_off + static_cast<int64_t>(inv[m]) * tv.rank;
+    const double *sx = ops + tv.vt_off + static_cast<int64_t>(inv[m + dx]) * tv.rank;
+    const double *sy = ops + tv.vt_off + static_cast<int64_t>(inv[m + dy]) * tv.rank;
+    const double *sxy = ops + tv.vt_off + static_cast<int64_t>(inv[m + dx + dy]) * tv.rank;
+    const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
+    double *dee = vt_all + static_cast<int64_t>(c.s1_off.v[0] + je) * c.r_pad16 + tv.row;
+    double *deo = vt_all + static_cast<int64_t>(c.s1_off.v[1] + jo) * c.r_pad16 + tv.row;
+    double *doe = vt_all + static_cast<int64_t>(c.s1_off.v[2] + je) * c.r_pad16 + tv.row;
+    double *doo = vt_all + static_cast<int64_t>(c.s1_off.v[3] + jo) * c.r_pad16 + tv.row;
+    const double wx = cx ? 1.0 : 0.5, wy = cy ? 1.0 : 0.5;
+    for (int kk = 0; kk < tv.rank; ++kk) {
+        const double v = s0[kk], vx = sx[kk], vy = sy[kk], vxy = sxy[kk];
+        const double e0 = cx ? v : v + vx, e1 = cx ? vy : vy + vxy, o0 = v - vx, o1 = vy - vxy;
+        dee[kk] = wx * wy * (cy ? e0 : e0 + e1);
+        if (!cy) deo[kk] = wx * wy * (e0 - e1);
+        if (!cx) doe[kk] = wx * wy * (cy ? o0 : o0 + o1);
+        if (!cx && !cy) doo[kk] = wx * wy * (o0 - o1);
+    }
+}
+
 __global__ __launch_bounds__(256) void assemble_u_kernel(M2lAssembleClass c, int n, int n_pad, const double *__restrict__ ops,
                                                          const int32_t *__restrict__ invperm, double *__restrict__ u_all) {
     const int pos = blockIdx.y;
@@ -1038,7 +1119,11 @@ void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compr
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s) {
     (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(c.n_e > 0 ? c.n_par : n_pad) * c.r_pad16 * sizeof(double), s);
     (void)hipMemsetAsync(u_all, 0, (c.u_npar > 0 ? static_cast<size_t>(c.u_rows) * c.u_npar : static_cast<size_t>(c.k_pad) * n_pad) * sizeof(double), s);
-    if (c.n_src > 0 && c.n_e > 0)
+    if (c.n_src > 0 && c.n_e > 0 && c.s1_axes == 2) {
+        const int h = (c.p + 1) / 2, n_ee = h * h * (n / (c.p * c.p));
+        hipLaunchKernelGGL(assemble_vt_parity2_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * n_ee + 255) / 256)), dim3(256),
+                           0, s, c, n, ops, invperm, vt_all);
+    } else if (c.n_src > 0 && c.n_e > 0)
         hipLaunchKernelGGL(assemble_vt_parity_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * c.n_e + 255) / 256)), dim3(256),
                            0, s, c, n, ops, invperm, vt_all);
     else if (c.n_src > 0)

@@ -40,7 +40,28 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
     }
     // Parity basis: rows [0, ne16) hold Vt_e[kk][j] = (Vt_t[kk][j] + Vt_t[kk][rho j]) / 2 (the centre plane of an odd
     // order: Vt_t[kk][j]), rows [ne16, n_par) hold Vt_o[kk][j] = (Vt_t[kk][j] - Vt_t[kk][rho j]) / 2
-    if (m2l_pairs_) {
+    // Two axes: row k of the part ab holds (1 / orbit) sum over the orbit of +- Vt_t[kk][.] (m2l_par_node_ / m2l_par_sign_;
+    // the orbit has 1, 2 or 4 nodes, so the factor is exact)
+    if (m2l_pairs_ && m2l_axes_ == 2) {
+        parallel_for(m2l_npar_, 8, [&](int64_t k) {
+            const int32_t *nd = &m2l_par_node_[static_cast<size_t>(4 * k)];
+            const int8_t *sg = &m2l_par_sign_[static_cast<size_t>(4 * k)];
+            int cnt = 0;
+            for (int g = 0; g < 4; ++g) cnt += nd[g] >= 0;
+            if (cnt == 0) return; // padding
+            const double w = 1.0 / cnt;
+            double *dst = vt_all + static_cast<size_t>(k) * hc.r_pad16;
+            for (const RowSrc &rs : row_src) {
+                const int r = rs.op->rank;
+                for (int kk = 0; kk < r; ++kk) {
+                    double v = 0.0;
+                    for (int g = 0; g < 4; ++g)
+                        if (nd[g] >= 0) v += sg[g] * rs.op->vt[static_cast<size_t>(rs.inv[nd[g]]) * r + kk];
+                    dst[rs.first_row + kk] = w * v;
+                }
+            }
+        });
+    } else if (m2l_pairs_) {
         parallel_for(m2l_ne_, 8, [&](int64_t j) {
             const bool centre = j >= m2l_no_;
             const int rj = m2l_rho(static_cast<int>(j));
@@ -180,6 +201,24 @@ int FmmTree::build_m2l_tables() {
             for (int m = 0; m < n && ok; ++m) ok = ir[m] == it[m2l_rho(m)];
             if (ok) m2l_partner_[static_cast<size_t>(tv)] = rt;
         }
+        // The same along axis 1 for stage 1: t and R_y t (component 1 negated) share the reference operator and
+        // invperm_{R_y t}[m] = invperm_t[rho_y m].  Only vectors that no x pair of the list at hand holds pair this way.
+        m2l_partner_y_.assign(static_cast<size_t>(nvec), -1);
+        for (int tv = 0; tv < nvec && m2l_pairs_; ++tv) {
+            if (comp(tv, 1) == 0) continue;
+            int rt = -1;
+            for (int u = 0; u < nvec && rt < 0; ++u) {
+                bool same = comp(u, 1) == -comp(tv, 1);
+                for (int a = 0; a < d; ++a) same = same && (a == 1 || comp(u, a) == comp(tv, a));
+                if (same) rt = u;
+            }
+            if (rt < 0 || ops_.ref_lookup[rt] != ops_.ref_lookup[tv]) continue;
+            const int32_t *it = &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[tv]) * n];
+            const int32_t *ir = &ops_.invperm[static_cast<size_t>(ops_.perm_lookup[rt]) * n];
+            bool ok = true;
+            for (int m = 0; m < n && ok; ++m) ok = ir[m] == it[m2l_rho_y(m)];
+            if (ok) m2l_partner_y_[static_cast<size_t>(tv)] = rt;
+        }
     }
     auto far = [&](int tv) {
         int mx = 0;
@@ -231,6 +270,158 @@ int FmmTree::build_m2l_tables() {
     for (int o = 0; o < ncls; ++o) {
         if (m2l_pairs_) pairs_first(&src_list[o], &tpos_src[o]);
         if (m2l_pairs2_) pairs_first(&tgt_list[o], &tpos_tgt[o]);
+    }
+    // Two axes: a list in the order [x pairs | singles | y pairs], the y pairs among the vectors that no x pair of this
+    // list holds (R_y t directly behind t, t1 > 0 first).  `carry` (may be NULL) is permuted along with the list.
+    auto order_axes = [&](std::vector<int> *list, std::vector<int> *carry) {
+        const size_t nl = list->size();
+        std::vector<int> where(static_cast<size_t>(nvec), -1);
+        for (size_t i = 0; i < nl; ++i) where[static_cast<size_t>((*list)[i])] = static_cast<int>(i);
+        std::vector<uint8_t> used(nl, 0);
+        std::vector<size_t> order, ypairs;
+        for (int pass = 0; pass < 2; ++pass) {
+            const std::vector<int32_t> &partner = pass == 0 ? m2l_partner_ : m2l_partner_y_;
+            for (size_t i = 0; i < nl; ++i) {
+                if (used[i]) continue;
+                const int tv = (*list)[i], rt = partner[static_cast<size_t>(tv)];
+                const int j = rt >= 0 ? where[static_cast<size_t>(rt)] : -1;
+                if (j < 0 || used[static_cast<size_t>(j)] || partner[static_cast<size_t>(rt)] != tv) continue;
+                const bool lead = comp(tv, pass) > 0;
+                std::vector<size_t> &dst = pass == 0 ? order : ypairs;
+                dst.push_back(lead ? i : static_cast<size_t>(j));
+                dst.push_back(lead ? static_cast<size_t>(j) : i);
+                used[i] = used[static_cast<size_t>(j)] = 1;
+            }
+        }
+        for (size_t i = 0; i < nl; ++i)
+            if (!used[i]) order.push_back(i);
+        order.insert(order.end(), ypairs.begin(), ypairs.end());
+        std::vector<int> l2(nl), c2(nl);
+        for (size_t i = 0; i < nl; ++i) {
+            l2[i] = (*list)[order[i]];
+            if (carry) c2[i] = (*carry)[order[i]];
+        }
+        *list = l2;
+        if (carry) *carry = c2;
+    };
+    // Pairs of a list by adjacency (an x pair: Rt directly behind t; with two axes a y pair the same way), and the stacked
+    // rows of the list at `level`: every vector that owns rows starts at an even row.  The kernel's slot table holds
+    // kM2lSlotWindow list positions per column block: where the ranks are so low that a block would span more (160 columns
+    // of rank-2 pairs: 160 positions), the next vector starts a new block and the rest of the old one stays padding.  A
+    // column block walks the contraction in one order, so the first y pair starts a new block when the block at hand
+    // holds columns of an x pair (the singles between them fill the straddling block where there are enough of them).
+    // Returns the stacked rows; *yb = the first block of a y pair or -1, *pad = the rows left empty for that.
+    auto mark_pairs_at = [&](int level, int axes, const std::vector<int> &tvs, std::vector<int32_t> *src_pair, std::vector<int32_t> *row0,
+                             std::vector<int8_t> *kind, int *yb, int *pad) {
+        const auto &lops = ops_.m2l[level];
+        src_pair->assign(tvs.size(), -1);
+        std::vector<int8_t> kd(tvs.size(), 0);
+        for (size_t pos = 0; m2l_pairs_ && pos + 1 < tvs.size(); ++pos) {
+            const size_t a = static_cast<size_t>(tvs[pos]), b = static_cast<size_t>(tvs[pos + 1]);
+            const bool px = m2l_partner_[a] == tvs[pos + 1] && m2l_partner_[b] == tvs[pos];
+            const bool py = !px && axes == 2 && m2l_partner_y_[a] == tvs[pos + 1] && m2l_partner_y_[b] == tvs[pos];
+            if (px || py) {
+                (*src_pair)[pos] = static_cast<int32_t>(pos + 1);
+                (*src_pair)[pos + 1] = -2;
+                kd[pos] = kd[pos + 1] = px ? 1 : 2;
+                ++pos;
+            }
+        }
+        if (row0) row0->assign(tvs.size(), 0);
+        int rows = 0, blk = -1, blk_first = 0; // blk_first: first list position with rows in block blk
+        int last_x_blk = -1, y_blk = -1, pad_rows = 0;
+        for (size_t pos = 0; pos < tvs.size(); ++pos) {
+            if ((*src_pair)[pos] == -2) continue;
+            const int r = lops[ops_.ref_lookup[tvs[pos]]].rank;
+            if (r == 0) continue;
+            if (kd[pos] == 2 && y_blk < 0) {
+                if (rows / m2l_s1_block_ <= last_x_blk) {
+                    pad_rows = round_up(rows, m2l_s1_block_) - rows;
+                    rows += pad_rows;
+                }
+                y_blk = rows / m2l_s1_block_;
+            }
+            const int last = (*src_pair)[pos] >= 0 ? static_cast<int>(pos) + 1 : static_cast<int>(pos);
+            if (rows / m2l_s1_block_ == blk && last - blk_first + 1 > kM2lSlotWindow) rows = round_up(rows, m2l_s1_block_);
+            if (row0) (*row0)[pos] = rows;
+            const int b1 = (rows + r - 1) / m2l_s1_block_; // the last block the vector's rows reach
+            if (rows / m2l_s1_block_ != blk || b1 != blk) {
+                blk = b1;
+                blk_first = static_cast<int>(pos); // (also of a block the vector only reaches into: it is the first there)
+            }
+            if (kd[pos] == 1) last_x_blk = b1;
+            rows = round_up(rows + r, 2);
+        }
+        if (kind) *kind = kd;
+        if (yb) *yb = y_blk;
+        if (pad) *pad = pad_rows;
+        return rows;
+    };
+    // BBFMM_M2L_S1_AXES (read per handle): 1 the x pairs alone, 2 also the y pairs; unset: by executed work, the sum over
+    // the level classes of column blocks x contraction steps -- two axes only where that is strictly smaller (the four
+    // parts pad to 16 each: at low orders that costs more steps than the pairs save columns).
+    m2l_axes_ = 1;
+    m2l_s_ee_ = m2l_s_eo_ = 0;
+    m2l_s1_off_ = M2lParityOffsets{{0, m2l_ne16_, m2l_ne16_, m2l_npar_}};
+    m2l_work_[0] = m2l_work_[1] = 0;
+    m2l_par_node_.clear();
+    m2l_par_sign_.clear();
+    if (m2l_pairs_) {
+        const int p = ops_.p, p2 = n / (p * p), h = (p + 1) / 2, f = p / 2;
+        const int len[4] = {h * h * p2, h * f * p2, f * h * p2, f * f * p2};
+        M2lParityOffsets off2{{0, 0, 0, 0}};
+        for (int i = 1; i < 4; ++i) off2.v[i] = off2.v[i - 1] + round_up(len[i - 1], 16);
+        const int npar2 = off2.v[3] + round_up(len[3], 16);
+        std::vector<std::vector<int>> src_xy = src_list;
+        for (int o = 0; o < ncls; ++o) order_axes(&src_xy[o], nullptr);
+        for (int level = 2; level <= t.depth; ++level) {
+            std::vector<uint8_t> has(static_cast<size_t>(ncls), 0);
+            for (int64_t c = t.level_ptr[level]; c < t.level_ptr[level + 1]; ++c) has[t.octant[c]] = 1;
+            for (int o = 0; o < ncls; ++o) {
+                if (!has[static_cast<size_t>(o)]) continue;
+                std::vector<int32_t> marks;
+                const int rows1 = mark_pairs_at(level, 1, src_list[o], &marks, nullptr, nullptr, nullptr, nullptr);
+                const int rows2 = mark_pairs_at(level, 2, src_xy[o], &marks, nullptr, nullptr, nullptr, nullptr);
+                m2l_work_[0] += static_cast<int64_t>(round_up(std::max(rows1, 1), m2l_s1_block_) / m2l_s1_block_) * (m2l_npar_ / 16);
+                m2l_work_[1] += static_cast<int64_t>(round_up(std::max(rows2, 1), m2l_s1_block_) / m2l_s1_block_) * (npar2 / 16);
+            }
+        }
+        const char *e = std::getenv("BBFMM_M2L_S1_AXES");
+        const int want = e ? std::atoi(e) : 0;
+        if (want == 2 || (want != 1 && m2l_work_[1] < m2l_work_[0])) {
+            m2l_axes_ = 2;
+            m2l_s1_off_ = off2;
+            m2l_ne16_ = off2.v[2];
+            m2l_npar_ = npar2;
+            m2l_s_ee_ = off2.v[1] / 16;
+            m2l_s_eo_ = (off2.v[2] - off2.v[1]) / 16;
+            for (int o = 0; o < ncls; ++o) {
+                src_list[o] = src_xy[o];
+                for (size_t i = 0; i < src_list[o].size(); ++i) tpos_src[o][src_list[o][i]] = static_cast<int>(i);
+            }
+            // basis index -> the nodes of its orbit under {rho_x, rho_y} and their signs (device: m2l_parity2_kernel)
+            m2l_par_node_.assign(static_cast<size_t>(npar2) * 4, -1);
+            m2l_par_sign_.assign(static_cast<size_t>(npar2) * 4, 0);
+            for (int i0 = 0; i0 < h; ++i0)
+                for (int i1 = 0; i1 < h; ++i1)
+                    for (int r = 0; r < p2; ++r) {
+                        const int m = (i0 * p + i1) * p2 + r;
+                        const bool cx = i0 >= f, cy = i1 >= f;
+                        const int nodes[4] = {m, m2l_rho(m), m2l_rho_y(m), m2l_rho_y(m2l_rho(m))};
+                        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
+                        for (int part = 0; part < 4; ++part) {
+                            const bool ox = part >= 2, oy = part & 1; // odd along x / y
+                            if ((ox && cx) || (oy && cy)) continue;
+                            const size_t k = static_cast<size_t>(off2.v[part] + (oy ? jo : je));
+                            for (int g = 0; g < 4; ++g) {
+                                const bool gx = g & 1, gy = g & 2; // the node reflected along x / y
+                                if ((gx && cx) || (gy && cy)) continue;
+                                m2l_par_node_[4 * k + g] = nodes[g];
+                                m2l_par_sign_[4 * k + g] = static_cast<int8_t>(((gx && ox) != (gy && oy)) ? -1 : 1);
+                            }
+                        }
+                    }
+        }
     }
     // per target position: the partner's position (leader of a pair), -1 (single), -2 (partner)
     std::vector<std::vector<int32_t>> tgt_pair(ncls);
@@ -360,42 +551,17 @@ int FmmTree::build_m2l_tables() {
         // list for the class itself, the present ones for a boundary variant): every transfer vector's rows
         // start at an even stacked row (the scatter stores pairs of adjacent rows as 16 bytes).
         // a pair: Rt directly behind t in the list, the identity verified (a variant or a group operator that lost
-        // one of the two keeps the other as a single).  Returns the stacked rows of the list and the first row of every
-        // vector that owns rows.  The kernel's slot table holds kM2lSlotWindow list positions per column block: where
-        // the ranks are so low that a block would span more (160 columns of rank-2 pairs: 160 positions), the next
-        // vector starts a new block and the rest of the old one stays padding.
-        auto mark_pairs = [&](const std::vector<int> &tvs, std::vector<int32_t> *src_pair, std::vector<int32_t> *row0 = nullptr) {
-            src_pair->assign(tvs.size(), -1);
-            for (size_t pos = 0; m2l_pairs_ && pos + 1 < tvs.size(); ++pos)
-                if (m2l_partner_[static_cast<size_t>(tvs[pos])] == tvs[pos + 1] && m2l_partner_[static_cast<size_t>(tvs[pos + 1])] == tvs[pos]) {
-                    (*src_pair)[pos] = static_cast<int32_t>(pos + 1);
-                    (*src_pair)[pos + 1] = -2;
-                    ++pos;
-                }
-            if (row0) row0->assign(tvs.size(), 0);
-            int rows = 0, blk = -1, blk_first = 0; // blk_first: first list position with rows in block blk
-            for (size_t pos = 0; pos < tvs.size(); ++pos) {
-                if ((*src_pair)[pos] == -2) continue;
-                const int r = rank_of(tvs[pos]);
-                if (r == 0) continue;
-                const int last = (*src_pair)[pos] >= 0 ? static_cast<int>(pos) + 1 : static_cast<int>(pos);
-                if (rows / m2l_s1_block_ == blk && last - blk_first + 1 > kM2lSlotWindow) rows = round_up(rows, m2l_s1_block_);
-                if (row0) (*row0)[pos] = rows;
-                const int b1 = (rows + r - 1) / m2l_s1_block_; // the last block the vector's rows reach
-                if (rows / m2l_s1_block_ != blk || b1 != blk) {
-                    blk = b1;
-                    blk_first = static_cast<int>(pos); // (also of a block the vector only reaches into: it is the first there)
-                }
-                rows = round_up(rows + r, 2);
-            }
-            return rows;
+        // one of the two keeps the other as a single): mark_pairs_at above.
+        auto mark_pairs = [&](const std::vector<int> &tvs, std::vector<int32_t> *src_pair) {
+            return mark_pairs_at(level, m2l_axes_, tvs, src_pair, nullptr, nullptr, nullptr, nullptr);
         };
         auto stage1_rows = [&](int o, const std::vector<int> &tvs, HostM2lClass *hcp) {
             HostM2lClass &hc = *hcp;
             hc.n_t = static_cast<int>(tvs.size());
             std::vector<int32_t> first_row;
-            hc.n_rows = mark_pairs(tvs, &hc.src_pair, &first_row);
+            hc.n_rows = mark_pairs_at(level, m2l_axes_, tvs, &hc.src_pair, &first_row, &hc.src_kind, &hc.yb0, &hc.pad_cols);
             hc.r_pad16 = round_up(std::max(hc.n_rows, 1), m2l_s1_block_);
+            if (hc.yb0 < 0) hc.yb0 = hc.r_pad16 / m2l_s1_block_; // no y pairs: every block walks in x order
             hc.row_tpos.assign(hc.r_pad16, -1);
             hc.row_off.assign(hc.r_pad16, 0);
             hc.row_tpos2.assign(hc.r_pad16, -1);
@@ -646,6 +812,7 @@ int FmmTree::build_m2l_tables() {
                     }
                 }
                 if (tvs.empty()) continue;
+                if (m2l_axes_ == 2) order_axes(&tvs, &keep); // (t and R_y t end in the same target class, hence group)
                 HostM2lClass v;
                 v.level = level;
                 v.octant = o;
@@ -713,9 +880,14 @@ int FmmTree::build_m2l_tables() {
                 while (j < nc && same_pattern(i, j)) ++j;
                 size_t full = 0;
                 if (variants_on && j - i >= static_cast<size_t>(variant_min_tiles) * kM2lTile) {
-                    std::vector<int> tvs;
+                    std::vector<int> tvs, keep;
                     for (int ps = 0; ps < nt; ++ps)
-                        if (hc.cslot[i * nt + ps] >= 0) tvs.push_back(hc.src_tv[ps]);
+                        if (hc.cslot[i * nt + ps] >= 0) {
+                            tvs.push_back(hc.src_tv[ps]);
+                            keep.push_back(ps);
+                        }
+                    // (two axes: vectors whose x partner is absent may pair along y among themselves)
+                    if (m2l_axes_ == 2) order_axes(&tvs, &keep);
                     std::vector<int32_t> marks;
                     const int present_rows = mark_pairs(tvs, &marks);
                     // worth a variant: at least one column block saved -- or, in the parity basis, pairs that lost their
@@ -732,9 +904,6 @@ int FmmTree::build_m2l_tables() {
                         v.cells.assign(hc.cells.begin() + static_cast<std::ptrdiff_t>(i), hc.cells.begin() + static_cast<std::ptrdiff_t>(i + full));
                         v.cslot.resize(full * tvs.size());
                         size_t pv = 0;
-                        std::vector<int> keep;
-                        for (int ps = 0; ps < nt; ++ps)
-                            if (hc.cslot[i * nt + ps] >= 0) keep.push_back(ps);
                         for (size_t k = 0; k < full; ++k)
                             for (int ps : keep) v.cslot[pv++] = hc.cslot[(i + k) * nt + ps];
                         for (size_t f = 0; f < full; f += kM2lTile) {
@@ -1095,7 +1264,11 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
         for (int64_t c = 0; c < tree_.n_cells(); ++c) {
             const double *Mv = M + static_cast<size_t>(c) * n;
             double *mp = &Mp[static_cast<size_t>(c) * m2l_npar_];
-            for (int j = 0; j < m2l_ne_; ++j) {
+            for (int k = 0; m2l_axes_ == 2 && k < m2l_npar_; ++k) // [M_ee | M_eo | M_oe | M_oo]: the signed sums over the orbits
+                for (int g = 0; g < 4; ++g)
+                    if (m2l_par_node_[static_cast<size_t>(4 * k + g)] >= 0)
+                        mp[k] += m2l_par_sign_[static_cast<size_t>(4 * k + g)] * Mv[m2l_par_node_[static_cast<size_t>(4 * k + g)]];
+            for (int j = 0; m2l_axes_ == 1 && j < m2l_ne_; ++j) {
                 if (j < m2l_no_) {
                     mp[j] = Mv[j] + Mv[m2l_rho(j)];
                     mp[m2l_ne16_ + j] = Mv[j] - Mv[m2l_rho(j)];
@@ -1137,8 +1310,15 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
                         if (slot < 0 && slot2 < 0) continue;
                         const double *mp = &Mp[static_cast<size_t>(hc.cells[pos]) * m2l_npar_];
                         double a = 0.0, bsum = 0.0;
-                        for (int j = 0; j < m2l_ne16_; ++j) a += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
-                        for (int j = m2l_ne16_; j < m2l_npar_; ++j) bsum += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                        if (row / m2l_s1_block_ >= hc.yb0) { // a block in y order: a over the y-even parts ee and oe, b over eo and oo
+                            for (int j = 0; j < m2l_npar_; ++j) {
+                                const bool y_odd = (j >= m2l_s1_off_.v[1] && j < m2l_s1_off_.v[2]) || j >= m2l_s1_off_.v[3];
+                                (y_odd ? bsum : a) += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                            }
+                        } else {
+                            for (int j = 0; j < m2l_ne16_; ++j) a += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                            for (int j = m2l_ne16_; j < m2l_npar_; ++j) bsum += hc.vt_all[static_cast<size_t>(j) * hc.r_pad16 + row] * mp[j];
+                        }
                         if (slot >= 0) cbuf[static_cast<size_t>(slot) * 2 + hc.row_off[row]] = a + bsum;
                         if (slot2 >= 0) cbuf[static_cast<size_t>(slot2) * 2 + hc.row_off2[row]] = a - bsum;
                         continue;
@@ -1212,9 +1392,43 @@ void FmmTree::debug_m2l_pairs(std::vector<int32_t> *out) const {
         const size_t n_at = out->size();
         out->push_back(0);
         int32_t n_entries = 0;
+        for (size_t pos = 0; pos < h.src_tv.size(); ++pos) { // (the members of a y pair are listed as two singles)
+            const bool x_pair = h.src_pair[pos] >= 0 && h.src_kind[pos] == 1;
+            if (h.src_pair[pos] == -2 && h.src_kind[pos] == 1) continue;
+            out->push_back(x_pair ? 1 : 0);
+            for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.src_tv[pos]) * d + a]);
+            ++n_entries;
+        }
+        (*out)[n_at] = n_entries;
+    }
+}
+
+void FmmTree::debug_m2l_pairs_axes(std::vector<int32_t> *out) const {
+    out->clear();
+    const int d = d_;
+    out->push_back(m2l_pairs_ ? m2l_axes_ : 0);
+    out->push_back(static_cast<int32_t>(m2l_work_[0]));
+    out->push_back(static_cast<int32_t>(m2l_work_[1]));
+    for (size_t i = 0; i < m2l_host_.size() + m2l_variants_.size(); ++i) {
+        const HostM2lClass &h = i < m2l_host_.size() ? m2l_host_[i] : m2l_variants_[i - m2l_host_.size()];
+        if (h.cells.empty()) continue;
+        const int n_blk = h.r_pad16 / m2l_s1_block_;
+        out->push_back(h.level);
+        out->push_back(h.octant);
+        out->push_back(i < m2l_host_.size() ? 0 : 1);
+        out->push_back(h.pad_cols);
+        out->push_back(h.yb0);
+        out->push_back(n_blk);
+        const size_t n_at = out->size();
+        out->push_back(0);
+        for (int b = 0; b < n_blk; ++b) out->push_back(b >= h.yb0 ? 1 : 0);
+        int32_t n_entries = 0;
         for (size_t pos = 0; pos < h.src_tv.size(); ++pos) {
             if (h.src_pair[pos] == -2) continue;
-            out->push_back(h.src_pair[pos] >= 0 ? 1 : 0);
+            out->push_back(h.src_pair[pos] >= 0 ? h.src_kind[pos] : 0);
+            const bool rows = h.src_row1[pos] > h.src_row0[pos]; // (a vector of rank 0 owns no column: -1, -1)
+            out->push_back(rows ? h.src_row0[pos] / m2l_s1_block_ : -1);
+            out->push_back(rows ? (h.src_row1[pos] - 1) / m2l_s1_block_ : -1);
             for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.src_tv[pos]) * d + a]);
             ++n_entries;
         }

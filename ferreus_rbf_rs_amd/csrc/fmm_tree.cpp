@@ -499,6 +499,7 @@ int FmmTree::upload() {
         c.n_t = h.n_t;
         c.k_pad = h.k_pad;
         c.kp = h.kp;
+        c.yb0 = h.yb0;
         c.n_cells = static_cast<int32_t>(h.cells.size());
         if (h.cells.empty()) continue;
         DevBuf<double> vt, ua;
@@ -533,7 +534,8 @@ int FmmTree::upload() {
             const M2lAssembleClass ac{d_src.p, d_tgt.p, static_cast<int32_t>(src_tv.size()), static_cast<int32_t>(tgt_tv.size()),
                                       h.r_pad16, h.k_pad, max_rank,
                                       m2l_pairs_ ? m2l_ne_ : 0, m2l_no_, m2l_ne16_, m2l_npar_, ops_.p,
-                                      m2l_pairs2_ ? m2l_s2_plan_.n_par() : 0, m2l_s2_plan_.ne16(), h.k_pad - h.kp, m2l_ne_, m2l_no_};
+                                      m2l_pairs2_ ? m2l_s2_plan_.n_par() : 0, m2l_s2_plan_.ne16(), h.k_pad - h.kp, m2l_ne_, m2l_no_,
+                                      m2l_axes_, m2l_s1_off_};
             static const bool host_fill = std::getenv("BBFMM_M2L_ASSEMBLE_HOST") != nullptr; // checker: the host fill of round 1
             if (host_fill) {
                 std::vector<double> hv, hu;
@@ -931,7 +933,10 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     const int s1_len = m2l_pairs_ ? m2l_npar_ : m2l_len, s1_ne16 = m2l_pairs_ ? m2l_ne16_ : 0; // stage 1's contraction
     if (m2l_pairs_ && !m2l_batches_.empty()) { // the multipoles in the parity basis, once per matvec (part of stage 1's time)
         phase_begin();
-        launch_m2l_parity(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_ne16_, m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(k) * C, stream_);
+        if (m2l_axes_ == 2)
+            launch_m2l_parity2(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_s1_off_, ops_.p, ops_.n / (ops_.p * ops_.p), static_cast<int64_t>(k) * C, stream_);
+        else
+            launch_m2l_parity(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_ne16_, m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(k) * C, stream_);
         phase_end(kPhM2L1);
     }
     double *l_out = shared_basis_ ? d_Lc_.p : s2_pairs ? d_Lp_.p : d_L_.p;
@@ -961,12 +966,12 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
                                          cbuf_batch_len_, stream_);
             if (dp) { // whole-operator tiles, then the tiles of single column blocks (sources in the halo of the target set)
                 launch_m2l_stage1(d_m2l_classes_.p, dp->d_tiles1.p + t1_first, dp->d_tile_idx.p, t1_count, s1_len, m2l_slot_t_, kb,
-                                  C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16);
+                                  C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16, m2l_s_ee_, m2l_s_eo_);
                 launch_m2l_stage1(d_m2l_classes_.p, dp->d_tiles1.p + dp->batch_t1[4 * b + 2], dp->d_tile_idx.p, dp->batch_t1[4 * b + 3],
-                                  s1_len, m2l_slot_t_, kb, C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, true, m2l_max_blocks_, s1_ne16);
+                                  s1_len, m2l_slot_t_, kb, C, m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, true, m2l_max_blocks_, s1_ne16, m2l_s_ee_, m2l_s_eo_);
             } else
                 launch_m2l_stage1(d_m2l_classes_.p, d_m2l_tiles1_.p + t1_first, d_tile_idx1_.p, t1_count, s1_len, m2l_slot_t_, kb, C,
-                                  m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16);
+                                  m_chunk, d_cbuf_.p, cbuf_batch_len_, stream_, false, m2l_max_blocks_, s1_ne16, m2l_s_ee_, m2l_s_eo_);
             phase_end(kPhM2L1);
             phase_begin();
             if (s2_pairs) {

@@ -46,6 +46,10 @@ struct HostM2lClass {
     // for Rt, which owns no rows of its own (its src_row0 / src_row1 repeat those of t)
     std::vector<int32_t> row_tpos2, row_off2, row_dst2; // as row_tpos / row_off / row_dst for the difference a - b; -1: none
     std::vector<int32_t> src_pair;                      // per source position: partner's position (first of a pair), -1 (single), -2 (second of a pair)
+    // two axes (FmmTree::m2l_axes_ == 2): the list is [x pairs | singles | y pairs], a y pair (t, R_y t) uses the same tables
+    std::vector<int8_t> src_kind; // per source position: 0 single, 1 member of an x pair, 2 member of a y pair
+    int yb0 = 0;                  // first column block that walks the contraction in y order (M2lClass::yb0)
+    int pad_cols = 0;             // stacked rows left empty so that no block holds columns of an x pair and of a y pair
     // x-reflected pairs of stage 2 (FmmTree::m2l_pairs2_): the slot is [A | B | S] -- the leaders' segments, their partners'
     // at the same offsets kp further on, the singles from 2 kp; the operator has k_pad - kp rows (M2lClass::kp)
     int kp = 0;
@@ -252,6 +256,12 @@ class FmmTree {
     // single), then the d components of t.
     void debug_m2l_pairs(std::vector<int32_t> *out) const;
     bool m2l_pairs() const { return m2l_pairs_; }
+    // Test hook: the stage-1 operators with both kinds of pairs.  Header: axes in force, executed work (column blocks x
+    // contraction steps over the level classes) of the one-axis and of the two-axis layout.  Per operator with cells: level,
+    // octant, kind, padding columns, yb0, number of column blocks, number of entries; per column block 0 (x order) or 1
+    // (y order); per entry: 0 (single), 1 (x pair, listed by the member with t0 > 0) or 2 (y pair, t1 > 0), its first and
+    // last column block, then the d components of t.
+    void debug_m2l_pairs_axes(std::vector<int32_t> *out) const;
     // The same for the stage-2 operators (the target lists of the classes; kind is always 0).
     void debug_m2l_pairs_stage2(std::vector<int32_t> *out) const;
     bool m2l_pairs_stage2() const { return m2l_pairs2_; }
@@ -355,6 +365,19 @@ class FmmTree {
     int m2l_ne_ = 0, m2l_no_ = 0;        // even / odd representatives: ceil(p/2) p^(d-1), floor(p/2) p^(d-1)
     int m2l_ne16_ = 0, m2l_npar_ = 0;    // round_up(m2l_ne_, 16), + round_up(m2l_no_, 16)
     std::vector<int32_t> m2l_partner_;   // per transfer vector: Rt when the pair identity was verified, else -1
+    // The parity basis of axes 0 and 1 (BBFMM_M2L_S1_AXES): [M_ee | M_eo | M_oe | M_oo], each part padded
+    // to 16, m2l_ne16_ = the x-even parts ee + eo, m2l_npar_ all four; the vectors the x pairing leaves alone pair by R_y.
+    int m2l_axes_ = 1;                   // reflection axes of stage 1's pairs: 1 (x) or 2 (x, and y for the x singles)
+    M2lParityOffsets m2l_s1_off_{{0, 0, 0, 0}}; // first index of the parts ee, eo, oe, oo
+    int m2l_s_ee_ = 0, m2l_s_eo_ = 0;    // contraction steps of ee and of eo (= oe); 0 with one axis
+    int64_t m2l_work_[2] = {0, 0};       // executed work of the one-axis / two-axis layout: the unset switch takes the smaller
+    std::vector<int32_t> m2l_partner_y_; // per transfer vector: R_y t when the identity was verified along axis 1, else -1
+    std::vector<int32_t> m2l_par_node_;  // two axes: per basis index the up to four nodes of its orbit (-1: none) ...
+    std::vector<int8_t> m2l_par_sign_;   // ... and their signs
+    int m2l_rho_y(int m) const { // reflection of node m along axis 1 (the second digit)
+        const int p2 = ops_.n / (ops_.p * ops_.p);
+        return m + (ops_.p - 1 - 2 * ((m / p2) % ops_.p)) * p2;
+    }
     int m2l_rho(int m) const { // reflection of node m along axis 0 (the slowest digit)
         const int p1 = ops_.n / ops_.p;
         return m + (ops_.p - 1 - 2 * (m / p1)) * p1;

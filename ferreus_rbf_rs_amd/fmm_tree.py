@@ -594,6 +594,29 @@ class FmmTree:
             i += 4 + ne * (d + 1)
         return bool(on.value), ops
 
+    def debug_m2l_pairs_axes(self):
+        """(info, operators) of stage 1 with both kinds of pairs.  info: axes in force (0: no pairs) and the executed work
+        (column blocks x contraction steps over the level classes) of the one-axis and the two-axis layout.  Per operator:
+        level, octant, kind, pad_cols (columns left empty to keep the kinds apart), yb0, block_kinds (per column block 0:
+        x order, 1: y order), and x_pairs (listed by the member with t0 > 0), y_pairs (t1 > 0), singles as dicts
+        vector -> (first, last) column block of its columns ((-1, -1): rank 0)."""
+        fn = self._lib.bbfmm_debug_m2l_pairs_axes
+        n = ctypes.c_int64()
+        self._raise(fn(self._h, None, 0, ctypes.byref(n)))
+        buf = np.zeros(max(n.value, 1), dtype=np.int32)
+        self._raise(fn(self._h, buf.ctypes.data, n.value, ctypes.byref(n)))
+        info = {"axes": int(buf[0]), "work_x": int(buf[1]), "work_xy": int(buf[2])}
+        d, ops, i = self.dim, [], 3
+        while i < n.value:
+            level, octant, kind, pad_cols, yb0, n_blk, ne = (int(v) for v in buf[i:i + 7])
+            kinds = [int(v) for v in buf[i + 7:i + 7 + n_blk]]
+            ent = buf[i + 7 + n_blk:i + 7 + n_blk + ne * (d + 3)].reshape(ne, d + 3)
+            by_kind = [{tuple(int(x) for x in e[3:]): (int(e[1]), int(e[2])) for e in ent if e[0] == k} for k in range(3)]
+            ops.append({"level": level, "octant": octant, "kind": kind, "pad_cols": pad_cols, "yb0": yb0, "block_kinds": kinds,
+                        "singles": by_kind[0], "x_pairs": by_kind[1], "y_pairs": by_kind[2]})
+            i += 7 + n_blk + ne * (d + 3)
+        return info, ops
+
     def debug_m2l_s2_last_ksplit(self) -> int:
         """Parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet)."""
         ks = ctypes.c_int32()

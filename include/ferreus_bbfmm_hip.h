@@ -639,6 +639,7 @@ int bbfmm_debug_apply_m2l_tables_host(const bbfmm_handle *h, const double *M, do
  * out, fmm_m2l_tables.cpp build_m2l_tables) and of source cells that use one. */
 int bbfmm_debug_m2l_variants(const bbfmm_handle *h, int64_t *n_variants, int64_t *n_cells);
 int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
+int bbfmm_debug_m2l_pairs_axes(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
 int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit); /* debug only */
 
