@@ -186,6 +186,17 @@ SIGNATURES = {
     "bbfmm_ddm_debug_level_assembled": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_ddm_debug_level_factor": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_ddm_debug_level_solve": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32]),
+    "bbfmm_schwarz_create_ex": (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "bbfmm_schwarz_create_sharded_ex": (ctypes.c_int, [c_p, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_p, c_i64,
+                                                       c_p, c_p, c_p]),
+    "bbfmm_ddm_debug_level_create_ex": (ctypes.c_int, [c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32,
+                                                       c_p]),
+    "bbfmm_global_trend_transform": (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_p]),
+    "bbfmm_duplicate_cutoff_distance": (ctypes.c_int, [c_p, c_f64, c_p]),
+    "bbfmm_remove_duplicates": (ctypes.c_int, [c_p, c_i64, c_i32, c_i64, c_f64, c_i32, c_p, c_p, c_p]),
+    "bbfmm_debug_interpolant_terms": (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
+    "bbfmm_evaluate_interpolant": (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_f64,
+                                                  c_p, c_i64, c_p, c_i64, c_p]),
 }
 
 
@@ -202,7 +213,14 @@ class IsosurfaceOptions(ctypes.Structure):
     """bbfmm_isosurface_options"""
     _fields_ = [("size", c_i64), ("cluster_method", c_i32), ("finish", c_i32), ("batch_bytes", c_i64),
                 ("self_intersections", c_i32), ("follow", c_i32), ("seeds", ctypes.c_void_p), ("n_seeds", c_i64),
-                ("seeds_ld", c_i64)]
+                ("seeds_ld", c_i64), ("terms", ctypes.c_void_p)]
+
+
+class InterpolantTerms(ctypes.Structure):
+    """bbfmm_interpolant_terms"""
+    _fields_ = [("size", c_i64), ("d", c_i32), ("polynomial_degree", c_i32), ("k", c_i32), ("has_affine", c_i32),
+                ("coefficients", ctypes.c_void_p), ("ld_coefficients", c_i64), ("translation", c_f64 * 3), ("scale", c_f64 * 3),
+                ("B", c_f64 * 9), ("b", c_f64 * 3)]
 
 
 class DdmParams(ctypes.Structure):

@@ -14,6 +14,7 @@
 #include "device_group.hpp"
 #include "ferreus_bbfmm_hip.h"
 #include "fmm_tree.hpp"
+#include "interpolant_terms.hpp"
 #include "isosurface.hpp"
 #include "isosurface_curvature.hpp"
 #include "isosurface_intersect.hpp"
@@ -32,6 +33,12 @@ static int group_rc(bbfmm_handle *h, int rc) {
     if (rc != BBFMM_OK) h->err = h->group->last_error();
     return rc;
 }
+
+namespace bbfmm {
+void set_handle_error(bbfmm_handle *h, const char *message) { // interpolant.cpp: entry points outside this file
+    if (h) h->err = message;
+}
+} // namespace bbfmm
 
 #define GUARD(h)                              \
     if (!(h)) return BBFMM_BAD_ARGUMENT;      \
@@ -301,6 +308,32 @@ struct IsoFollow {
     int32_t follow = BBFMM_FOLLOW_DENSE;
     const double *seeds = nullptr;
     int64_t n_seeds = 0, seeds_ld = 0;
+    const bbfmm_interpolant_terms *terms = nullptr;
+};
+
+// The field terms of one extraction on the device: the coefficients and the transformed copies of the targets of one
+// field evaluation (grown on demand; every evaluation ends with its stream idle, so they are free to reuse).
+struct IsoFieldTerms {
+    bbfmm::InterpolantTerms t;
+    bool on = false;
+    double *d_lambda = nullptr, *xt[3] = {nullptr, nullptr, nullptr};
+    int64_t cap = 0;
+    ~IsoFieldTerms() {
+        (void)hipFree(d_lambda);
+        for (double *p : xt) (void)hipFree(p);
+    }
+    bool reserve(int64_t m) {
+        if (m <= cap) return true;
+        for (double *&p : xt) {
+            (void)hipFree(p);
+            p = nullptr;
+        }
+        cap = 0;
+        for (double *&p : xt)
+            if (hipMalloc(reinterpret_cast<void **>(&p), static_cast<size_t>(m) * sizeof(double)) != hipSuccess) return false;
+        cap = m;
+        return true;
+    }
 };
 
 static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int32_t *finish, int64_t *batch_bytes,
@@ -327,6 +360,7 @@ static bool iso_options(const bbfmm_isosurface_options *o, int32_t *cluster, int
         fol->n_seeds = o->n_seeds;
         fol->seeds_ld = o->seeds_ld;
     }
+    if (fol && o->size >= static_cast<int64_t>(offsetof(bbfmm_isosurface_options, terms) + sizeof(void *))) fol->terms = o->terms;
     return true;
 }
 
@@ -496,13 +530,48 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
         if (rc != BBFMM_OK) return rc;
     }
     FmmTree &t = h->tree;
+    IsoFieldTerms ft;
+    if (fol.terms) {
+        if (drift) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: give the drift or the field terms, not both");
+        if (!bbfmm::terms_from_abi(fol.terms, &ft.t) || ft.t.d != 3 || ft.t.k != 1)
+            return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: bad field terms (d = 3, k = 1, degree -1 .. 2, coefficients, scale != 0)");
+        const int nb = bbfmm::terms_basis_size(3, ft.t.degree);
+        for (int q = 0; q < nb; ++q)
+            if (!std::isfinite(ft.t.lambda[q])) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: field terms must be finite");
+        for (int q = 0; q < 9 && ft.t.has_affine; ++q)
+            if (!std::isfinite(ft.t.B[q]) || !std::isfinite(ft.t.b[q / 3])) return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: field terms must be finite");
+        if (ft.t.has_affine && fol.follow == BBFMM_FOLLOW_SURFACE && !fol.seeds)
+            return iso_fail(h, nullptr, BBFMM_BAD_ARGUMENT, "isosurface: with a global trend the seeds must be given (world points)");
+        ft.on = nb > 0 || ft.t.has_affine;
+    }
     // every node of E inside the tree's cube (points_to_leaves saturates coordinates below the tree, as the reference's
-    // Morton encoding does, so the bounds are checked here); the device pass of extract() then finds every leaf
+    // Morton encoding does, so the bounds are checked here); the device pass of extract() then finds every leaf.
+    // With a global trend: the extents of the 8 transformed corners of the lattice box (rbf.rs:599-613).
+    double box_lo[3], box_hi[3];
+    for (int a = 0; a < 3; ++a) {
+        box_lo[a] = lat.lo_world[a] + static_cast<double>(lat.lo[a]) * lat.spacing[a];
+        box_hi[a] = lat.lo_world[a] + static_cast<double>(lat.lo[a] + lat.dims[a] - 1) * lat.spacing[a];
+    }
+    if (ft.on && ft.t.has_affine) {
+        double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+        for (int c = 0; c < 8; ++c) {
+            const double p[3] = {(c & 1) ? box_hi[0] : box_lo[0], (c & 2) ? box_hi[1] : box_lo[1], (c & 4) ? box_hi[2] : box_lo[2]};
+            double q[3];
+            bbfmm::affine_point(ft.t, p, q);
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = c == 0 ? q[a] : std::min(lo[a], q[a]);
+                hi[a] = c == 0 ? q[a] : std::max(hi[a], q[a]);
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            box_lo[a] = lo[a];
+            box_hi[a] = hi[a];
+        }
+    }
     for (int a = 0; a < 3; ++a) {
         const auto &tr = t.tree();
-        const double w0 = lat.lo_world[a] + static_cast<double>(lat.lo[a]) * lat.spacing[a];
-        const double w1 = lat.lo_world[a] + static_cast<double>(lat.lo[a] + lat.dims[a] - 1) * lat.spacing[a];
-        if (w0 < tr.center[a] - tr.radius || w1 > tr.center[a] + tr.radius)
+        const double w0 = box_lo[a], w1 = box_hi[a];
+        if (!(w0 >= tr.center[a] - tr.radius) || !(w1 <= tr.center[a] + tr.radius))
             return iso_fail(h, nullptr, BBFMM_POINT_OUTSIDE_TREE,
                             "isosurface: lattice nodes on axis " + std::to_string(a) + " span [" + std::to_string(w0) + ", " +
                                 std::to_string(w1) + "], outside the tree extents [" + std::to_string(tr.center[a] - tr.radius) +
@@ -512,6 +581,35 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
         int64_t bad = -1;
         return t.evaluate_leaves_device(x0, x1, x2, m, vals, &bad);
     };
+    // with field terms: the tree is asked at x B + b, the polynomial (and for the seeds the gradients) are added at x
+    auto with_terms = [&t, &ft](const double *x0, const double *x1, const double *x2, int64_t m, double *vals, double *grad) -> int {
+        const double *q[3] = {x0, x1, x2};
+        if (ft.t.has_affine && m > 0) {
+            if (!ft.reserve(m)) return BBFMM_DEVICE_ERROR;
+            if (bbfmm::terms_affine_soa_device(ft.t, x0, x1, x2, m, ft.xt[0], ft.xt[1], ft.xt[2], t.stream()) != 0) return BBFMM_DEVICE_ERROR;
+            for (int a = 0; a < 3; ++a) q[a] = ft.xt[a];
+        }
+        int64_t bad = -1;
+        // a deterministic handle gets the same double in every batching; a default one has f64 atomics between its M2P
+        // jobs anyway and keeps the tuned plan
+        const int rc = t.evaluate_leaves_device(q[0], q[1], q[2], m, vals, &bad, grad, t.deterministic());
+        if (rc != BBFMM_OK || !vals) return rc;
+        return bbfmm::terms_field_soa_device(ft.t, x0, x1, x2, m, vals, grad, t.stream()) == 0 ? BBFMM_OK : BBFMM_DEVICE_ERROR;
+    };
+    if (ft.on) {
+        t.bind_device();
+        const int nb = bbfmm::terms_basis_size(3, ft.t.degree);
+        if (nb > 0) {
+            if (hipMalloc(reinterpret_cast<void **>(&ft.d_lambda), nb * sizeof(double)) != hipSuccess ||
+                hipMemcpy(ft.d_lambda, ft.t.lambda, nb * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+                return iso_fail(h, nullptr, BBFMM_DEVICE_ERROR, "isosurface: upload of the field terms");
+            ft.t.lambda = ft.d_lambda;
+            ft.t.ld_lambda = nb;
+        }
+        fn = [&with_terms](const double *x0, const double *x1, const double *x2, int64_t m, double *vals) {
+            return with_terms(x0, x1, x2, m, vals, nullptr);
+        };
+    }
     bbfmm::iso::Request req;
     req.isovalues = isovalues;
     req.n_iso = n_isovalues;
@@ -542,6 +640,7 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
                 int64_t bad = -1;
                 return t.evaluate_leaves_device(x0, x1, x2, m, vals, &bad, grad);
             };
+        if (req.grad && ft.on) req.grad = with_terms;
     }
     std::unique_ptr<bbfmm_isosurface_result> r(new bbfmm_isosurface_result());
     const int rc = bbfmm::iso::extract(lat, fn, req, t.stream(), &r->meshes, &err);

@@ -95,7 +95,7 @@ bool invert_small(const std::vector<double> &m, int k, std::vector<double> *inv)
 } // namespace
 
 int prepare_domain(const double *pts, int64_t ld, int d, int degree, int basis_size, DdmDomain *dom, DomainPrep *out,
-                   const double *scaling) {
+                   const double *scaling, const double *mono_pts, int64_t ld_mono) {
     *out = DomainPrep();
     if (basis_size == 0) return BBFMM_OK;
     const int n = static_cast<int>(dom->idx.size());
@@ -122,7 +122,8 @@ int prepare_domain(const double *pts, int64_t ld, int d, int degree, int basis_s
     std::vector<double> mono(static_cast<size_t>(n) * basis_size, 0.0);
     for (int i = 0; i < n; ++i) {
         double sx[3] = {0, 0, 0};
-        for (int a = 0; a < d; ++a) sx[a] = (loc[static_cast<size_t>(a) * n + i] - out->tr[a]) / out->sc[a];
+        for (int a = 0; a < d; ++a)
+            sx[a] = ((mono_pts ? mono_pts[a * ld_mono + dom->idx[i]] : loc[static_cast<size_t>(a) * n + i]) - out->tr[a]) / out->sc[a];
         monomial_row(sx, d, degree, &mono[static_cast<size_t>(i) * basis_size], 1);
     }
     // rank and unisolvent columns (domain.rs:186-212)
@@ -364,7 +365,7 @@ void big_lu_release(DdmLevelSolver *lv) {
 
 int ddm_level_build(const double *pts, int64_t ld, int d, DdmLevel *level, const KernelSpec &ks, double nugget,
                     int degree, int basis_size, bool solve_for_poly, hipStream_t s, DdmLevelSolver *lv,
-                    const double *scaling) {
+                    const double *scaling, const double *mono_pts, int64_t ld_mono) {
     *lv = DdmLevelSolver();
     lv->d = d;
     lv->solve_for_poly = solve_for_poly;
@@ -382,7 +383,7 @@ int ddm_level_build(const double *pts, int64_t ld, int d, DdmLevel *level, const
     lv->prep.resize(static_cast<size_t>(nd));
     std::vector<int> rcs(static_cast<size_t>(nd), BBFMM_OK);
     parallel_for(nd, 1, [&](int64_t i) {
-        rcs[i] = prepare_domain(pts, ld, d, degree, basis_size, &level->leaves[i], &lv->prep[i], scaling);
+        rcs[i] = prepare_domain(pts, ld, d, degree, basis_size, &level->leaves[i], &lv->prep[i], scaling, mono_pts, ld_mono);
     });
     for (int rc : rcs)
         if (rc != BBFMM_OK) return rc;

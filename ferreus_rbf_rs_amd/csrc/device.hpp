@@ -193,7 +193,7 @@ struct DirectJobs {
 };
 void launch_p2p(const KernelSpec &ks, int d, const DirectJobs &jobs, const double *const *tgt_xyz,
                 int64_t n_tgt, const double *const *src_xyz, const double *w_sorted, int64_t N, int K,
-                double *out_sorted, double *grad_sorted, hipStream_t s);
+                double *out_sorted, double *grad_sorted, hipStream_t s, bool fixed_plan = false);
 // P2P for targets that are (a contiguous sorted range of) the sources: every unordered pair once, one rhs.
 // Job i holds the target positions [tgt_begin[i], tgt_end[i]) -- at most p2p_sym_rows_per_job() of them, all of
 // one leaf; position p is sorted source tgt_off + p; its leaf's runs are runs3[3 * run_range[2i] .. 3 * run_range[2i+1])
@@ -237,7 +237,7 @@ void launch_m2p(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32
                 const int32_t *w_cells,
                 const double *centers, const double *lengths, const double *const *tgt_xyz,
                 int64_t n_tgt, int K, int64_t C, const double *M, double *out_sorted,
-                double *grad_sorted, hipStream_t s);
+                double *grad_sorted, hipStream_t s, bool fixed_plan = false);
 // P2L: targets are the Chebyshev nodes of the cell, sources the points of the X-list leaves.
 void launch_p2l(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32_t *cells,
                 const int64_t *run_ptr, const int32_t *runs, const double *centers,

@@ -57,7 +57,10 @@ __device__ inline void direct_tile(const KernelSpec &ks, const SrcTile<KB> &tile
 struct TargetPlan {
     int n_c, pairs, S;
 };
-__device__ inline TargetPlan plan_targets(int nt) {
+// fixed: passes of 64 targets in 8 source slices whatever nt is, so that the order in which a target's sum is formed does
+// not depend on how many other targets of the call share its leaf (FmmTree::evaluate_leaves_device, batch_independent).
+__device__ inline TargetPlan plan_targets(int nt, int fixed = 0) {
+    if (fixed) return TargetPlan{64, 32, 8};
     const int m0 = (nt + 511) / 512;
     TargetPlan best{nt, 256, 1};
     float best_cost = 1e30f;

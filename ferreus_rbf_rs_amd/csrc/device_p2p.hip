@@ -8,7 +8,7 @@ namespace bbfmm {
 template <int KID, bool GRAD, int KB>
 __global__ __launch_bounds__(256) void p2p_kernel(KernelSpec ks, int d, DirectJobs jobs, Xyz tgt, int64_t n_tgt,
                                                   Xyz src, const double *__restrict__ ws, int64_t N, int k0, int kb,
-                                                  double *__restrict__ out, double *__restrict__ grad) {
+                                                  double *__restrict__ out, double *__restrict__ grad, int fixed_plan) {
     __shared__ SrcTile<KB> tile;
     __shared__ double red[256];
     const int tid = threadIdx.x;
@@ -16,7 +16,7 @@ __global__ __launch_bounds__(256) void p2p_kernel(KernelSpec ks, int d, DirectJo
     const int t0 = jobs.tgt_begin[job], t1 = jobs.tgt_end[job];
     const int jcell = jobs.job_cell[job];
     const int64_t r0 = jobs.run_ptr[jcell], r1 = jobs.run_ptr[jcell + 1];
-    const TargetPlan tp = plan_targets(t1 - t0);
+    const TargetPlan tp = plan_targets(t1 - t0, fixed_plan);
     for (int tc = t0; tc < t1; tc += tp.n_c) {
         const int nt = min(tp.n_c, t1 - tc);
         const int ti = tid % tp.pairs, sl = tid / tp.pairs;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(64 * SYM2_WAVES) void p2p_sym2_kernel(KernelSpec ks
 // ------------------------------------------------------------------ launchers and job-size knobs
 void launch_p2p(const KernelSpec &ks, int d, const DirectJobs &jobs, const double *const *tgt_xyz, int64_t n_tgt,
                 const double *const *src_xyz, const double *w_sorted, int64_t N, int K, double *out_sorted,
-                double *grad_sorted, hipStream_t s) {
+                double *grad_sorted, hipStream_t s, bool fixed_plan) {
     if (jobs.n_jobs == 0) return;
     dispatch_kernel_id(ks.id, [&](auto idc) {
         constexpr int ID = decltype(idc)::value;
@@ -502,7 +502,8 @@ void launch_p2p(const KernelSpec &ks, int d, const DirectJobs &jobs, const doubl
             const int kb = std::min(wide ? DIRECT_KB_WIDE : DIRECT_KB, K - k0);
             auto go = [&](auto grad, auto kbv) {
                 hipLaunchKernelGGL((p2p_kernel<ID, decltype(grad)::value, decltype(kbv)::value>), dim3(jobs.n_jobs), dim3(256), 0, s, ks,
-                                   d, jobs, make_xyz(tgt_xyz), n_tgt, make_xyz(src_xyz), w_sorted, N, k0, kb, out_sorted, grad_sorted);
+                                   d, jobs, make_xyz(tgt_xyz), n_tgt, make_xyz(src_xyz), w_sorted, N, k0, kb, out_sorted, grad_sorted,
+                                   fixed_plan ? 1 : 0);
             };
             if (grad_sorted && kb == 1) go(std::true_type{}, int_c<1>{}); // single right-hand side: a quarter of the accumulators
             else if (grad_sorted) go(std::true_type{}, int_c<DIRECT_KB>{});

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void m2p_kernel(KernelSpec ks, const DevCheb *
                                                   const double *__restrict__ centers,
                                                   const double *__restrict__ lengths, Xyz tgt, int64_t n_tgt, int k0,
                                                   int kb, int64_t C, const double *__restrict__ M,
-                                                  double *__restrict__ out, double *__restrict__ grad) {
+                                                  double *__restrict__ out, double *__restrict__ grad, int fixed_plan) {
     __shared__ SrcTile<KB> tile;
     __shared__ double red[256];
     const int p = chp->p, d = chp->d, n = chp->n, n_pad = chp->n_pad;
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void m2p_kernel(KernelSpec ks, const DevCheb *
     const int job = blockIdx.x;
     const int t0 = tgt_begin[job], t1 = tgt_end[job];
     const int64_t r0 = w_begin[job], r1 = w_end[job]; // a chunk of the leaf's W list
-    const TargetPlan tp = plan_targets(t1 - t0);
+    const TargetPlan tp = plan_targets(t1 - t0, fixed_plan);
     for (int tc = t0; tc < t1; tc += tp.n_c) {
         const int nt = min(tp.n_c, t1 - tc);
         const int ti = tid % tp.pairs, sl = tid / tp.pairs;
@@ -382,7 +382,7 @@ void launch_m2p(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32
                 const int32_t *tgt_end, const int64_t *w_begin, const int64_t *w_end,
                 const int32_t *w_cells, const double *centers,
                 const double *lengths, const double *const *tgt_xyz, int64_t n_tgt, int K, int64_t C,
-                const double *M, double *out_sorted, double *grad_sorted, hipStream_t s) {
+                const double *M, double *out_sorted, double *grad_sorted, hipStream_t s, bool fixed_plan) {
     if (n_jobs == 0) return;
     dispatch_kernel_id(ks.id, [&](auto idc) {
         constexpr int ID = decltype(idc)::value;
@@ -391,7 +391,7 @@ void launch_m2p(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32
             auto go = [&](auto grad, auto kbv) {
                 hipLaunchKernelGGL((m2p_kernel<ID, decltype(grad)::value, decltype(kbv)::value>), dim3(n_jobs), dim3(256), 0, s, ks, ch.dev,
                                    tgt_begin, tgt_end, w_begin, w_end, w_cells, centers, lengths, make_xyz(tgt_xyz), n_tgt, k0, kb, C, M,
-                                   out_sorted, grad_sorted);
+                                   out_sorted, grad_sorted, fixed_plan ? 1 : 0);
             };
             if (grad_sorted && kb == 1) go(std::true_type{}, int_c<1>{});
             else if (grad_sorted) go(std::true_type{}, int_c<DIRECT_KB>{});

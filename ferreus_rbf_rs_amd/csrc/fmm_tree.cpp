@@ -1053,14 +1053,15 @@ hipError_t FmmTree::columns_to_host(double *dst, int64_t ld, const double *d_src
     return hipSuccess;
 }
 
-int FmmTree::leaf_pass(const TargetSet &ts, int k, bool with_grads) {
-    CHK(leaf_pass_near(ts, k, with_grads, stream_, 3));
+int FmmTree::leaf_pass(const TargetSet &ts, int k, bool with_grads, bool fixed_plan) {
+    CHK(leaf_pass_near(ts, k, with_grads, stream_, 3, false, fixed_plan));
     return leaf_pass_far(ts, k, with_grads);
 }
 
 // P2P + M2P: need the weights and the multipoles only (can run beside the downward pass)
 // parts: 1 = zero the outputs + P2P (needs the sorted weights), 2 = M2P (needs the multipoles)
-int FmmTree::leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStream_t st, int parts, bool wx_done) {
+int FmmTree::leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStream_t st, int parts, bool wx_done,
+                            bool fixed_plan) {
     const HostTree &t = tree_;
     const int64_t C = t.n_cells();
     double *grad = with_grads ? ts.grad.p : nullptr;
@@ -1080,14 +1081,15 @@ int FmmTree::leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStre
                            ts.syml_ptr.p, ts.n_symw_jobs, ts.symw_tb.p, ts.symw_te.p,
                            ts.symw_ptr.p, ts.sym_runs.p, ts.sym_off, src_ptr_, d_w_sorted_.p, t.n_points, k, ts.out.p, ts.m, st);
         else
-            launch_p2p(kernel_, d_, jobs, ts.xyz_ptr, ts.m, src_ptr_, d_w_sorted_.p, t.n_points, k, ts.out.p, grad, st);
+            launch_p2p(kernel_, d_, jobs, ts.xyz_ptr, ts.m, src_ptr_, d_w_sorted_.p, t.n_points, k, ts.out.p, grad, st,
+                       fixed_plan);
         if (timed) phase_end(kPhP2P);
     }
     if (parts & 2) {
         if (timed) phase_begin();
         if (t.adaptive && !wx_done)
             launch_m2p(kernel_, cheb_, ts.n_w_jobs, ts.w_tgt_begin.p, ts.w_tgt_end.p, ts.w_begin.p, ts.w_end.p,
-                       d_w_idx_.p, d_centers_.p, d_lengths_.p, ts.xyz_ptr, ts.m, k, C, d_M_.p, ts.out.p, grad, st);
+                       d_w_idx_.p, d_centers_.p, d_lengths_.p, ts.xyz_ptr, ts.m, k, C, d_M_.p, ts.out.p, grad, st, fixed_plan);
         if (timed) phase_end(kPhM2P);
     }
     HIPCHK(hipGetLastError());
@@ -1328,7 +1330,7 @@ int FmmTree::evaluate(const double *w, int64_t rows, int k, int64_t ldw, const d
 bool FmmTree::supports_gradients() const { return kernel_supports_gradients(kernel_.id); }
 
 int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
-                                    int64_t *bad_point_index, double *d_grad) {
+                                    int64_t *bad_point_index, double *d_grad, bool batch_independent) {
     if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
     if (d_ != 3) return fail(BBFMM_BAD_ARGUMENT, "device-resident targets need d = 3");
     if (nrhs_ != 1 || !have_locals_) return fail(BBFMM_BAD_ARGUMENT, "set_local_coefficients (one column) must be called first");
@@ -1376,7 +1378,7 @@ int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, cons
     int rc = build_target_set_device(nullptr, m, m, &ts, bad_point_index, nullptr, dx);
     if (rc == BBFMM_OK) rc = talloc(&ts.out, static_cast<size_t>(m));
     if (rc == BBFMM_OK && d_grad) rc = talloc(&ts.grad, static_cast<size_t>(d_) * m);
-    if (rc == BBFMM_OK) rc = leaf_pass(ts, 1, d_grad != nullptr);
+    if (rc == BBFMM_OK) rc = leaf_pass(ts, 1, d_grad != nullptr, batch_independent);
     if (rc == BBFMM_OK) {
         phase_begin();
         launch_scatter_output(ts.out.p, m, 1, ts.perm.p, d_out, m, 0, stream_);

@@ -172,8 +172,13 @@ class FmmTree {
     // row order, on the handle's stream (isosurface lattice nodes).  d_out == nullptr: only checks that every target
     // lies in the tree (BBFMM_POINT_OUTSIDE_TREE, *bad_point_index the first row that does not).  d_grad (with d_out): the
     // gradients too, component a of target t at d_grad[a * m + t] (isosurface seed projection).
+    // batch_independent: the near field and M2P split every leaf's targets the same way whatever their number
+    // (plan_targets(nt, fixed)), so on a BBFMM_FLAG_DETERMINISTIC handle the value at a target is the same double
+    // whichever other targets share the call; the default plan sizes itself to the leaf's targets and leaves 3e-16
+    // between two batchings.  Used for the lattice field with interpolant terms, whose dense and followed passes batch
+    // differently; every other caller keeps the default and its bits.
     int evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
-                               int64_t *bad_point_index, double *d_grad = nullptr);
+                               int64_t *bad_point_index, double *d_grad = nullptr, bool batch_independent = false);
     bool supports_gradients() const;
     int evaluate(const double *w, int64_t rows, int k, int64_t ldw, const double *x, int64_t m, int64_t ldx,
                  double *out, int64_t ldo, double *grad, int64_t ldg, bool with_grads, bool leaves_only,
@@ -219,6 +224,7 @@ class FmmTree {
     const char *last_error() const { return err_.c_str(); }
     hipStream_t stream() const { return stream_; }
     bool host_only() const { return host_only_; }
+    bool deterministic() const { return deterministic_; }
     // The handle may be used from any host thread (a solver's worker threads start with device 0 current):
     // the C entry points call this first.
     void bind_device() const {
@@ -287,8 +293,10 @@ class FmmTree {
     int downward(int k, const DownwardPlan *dp = nullptr, const TargetSet *wx = nullptr);
     int downward_m2l(int k, const DownwardPlan *dp);                          // its M2L part (reads M only)
     int downward_tail(int k, const DownwardPlan *dp, const TargetSet *wx);    // P2L (+ M2P when wx) and L2L
-    int leaf_pass(const TargetSet &ts, int k, bool with_grads);
-    int leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStream_t st, int parts, bool wx_done = false);
+    // fixed_plan: plan_targets(nt, fixed) in the ordered-pair P2P and the M2P kernel (evaluate_leaves_device, batch_independent)
+    int leaf_pass(const TargetSet &ts, int k, bool with_grads, bool fixed_plan = false);
+    int leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStream_t st, int parts, bool wx_done = false,
+                       bool fixed_plan = false);
     int leaf_pass_far(const TargetSet &ts, int k, bool with_grads);
     int build_target_set(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                          std::vector<int32_t> *leaves_out = nullptr);

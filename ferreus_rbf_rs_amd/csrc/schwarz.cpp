@@ -227,8 +227,10 @@ struct bbfmm_schwarz {
 };
 
 namespace {
-int schwarz_create_impl(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
-                        const bbfmm_interpolant *settings, const bbfmm_ddm_params *params, Schwarz &S) {
+// mono_points: NULL, or the points the monomials are evaluated at (a global trend's world points) with the cube scaling
+// of `points`, which give the geometry and the kernel blocks (rbf.rs:418-421, 476-491; domain.rs:161-184)
+int schwarz_create_impl(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld, const double *mono_points,
+                        int64_t ld_mono, const bbfmm_interpolant *settings, const bbfmm_ddm_params *params, Schwarz &S) {
     // (S.rank / S.world / the exchange were set by the caller for a sharded preconditioner)
     S.tree = tree;
     S.n = n;
@@ -301,7 +303,7 @@ int schwarz_create_impl(bbfmm_handle *tree, const double *points, int64_t n, int
         parallel_for_chunks(n, kBlk, [&](int64_t i0, int64_t i1) {
             for (int64_t i = i0; i < i1; ++i) {
                 double sx[3] = {0, 0, 0};
-                for (int a = 0; a < d; ++a) sx[a] = (points[a * ld + i] - tr[a]) / sc[a];
+                for (int a = 0; a < d; ++a) sx[a] = ((mono_points ? mono_points[a * ld_mono + i] : points[a * ld + i]) - tr[a]) / sc[a];
                 monomial_row(sx, d, S.degree, &S.mono[static_cast<size_t>(i)], static_cast<size_t>(n));
             }
         });
@@ -353,7 +355,7 @@ int schwarz_create_impl(bbfmm_handle *tree, const double *points, int64_t n, int
         const bool global_scaling = (settings->flags & BBFMM_FLAG_GLOBAL_SCALING) != 0;
         if (S.ddm.levels[li].leaves.empty()) continue; // (a level with fewer domains than ranks: nothing to factorise here)
         rc = ddm_level_build(points, ld, d, &S.ddm.levels[li], S.ks, S.nugget, S.degree, S.basis, coarse && S.basis != 0,
-                             S.stream, &S.levels[li], (coarse && S.basis != 0 && global_scaling) ? gscale : nullptr);
+                             S.stream, &S.levels[li], (coarse && S.basis != 0 && global_scaling) ? gscale : nullptr, mono_points, ld_mono);
         if (rc) return rc;
         lap("level prepared + factorised", static_cast<int>(li));
     }
@@ -419,13 +421,15 @@ int schwarz_create_impl(bbfmm_handle *tree, const double *points, int64_t n, int
 
 extern "C" {
 
-int bbfmm_schwarz_create_sharded(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
-                                 const bbfmm_interpolant *settings, const bbfmm_ddm_params *params, int32_t rank,
-                                 int32_t world, double *d_exchange, int64_t exchange_capacity,
-                                 bbfmm_allreduce_fn allreduce, void *allreduce_user, bbfmm_schwarz **out) {
+int bbfmm_schwarz_create_sharded_ex(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
+                                    const double *monomial_points, int64_t ld_monomial, const bbfmm_interpolant *settings,
+                                    const bbfmm_ddm_params *params, int32_t rank, int32_t world, double *d_exchange,
+                                    int64_t exchange_capacity, bbfmm_allreduce_fn allreduce, void *allreduce_user,
+                                    bbfmm_schwarz **out) {
     if (!out) return BBFMM_BAD_ARGUMENT;
     *out = nullptr;
-    if (!tree || !points || !settings || n < 1 || d < 1 || d > 3 || ld < n) return BBFMM_BAD_ARGUMENT;
+    if (!tree || !points || !settings || n < 1 || d < 1 || d > 3 || ld < n || (monomial_points && ld_monomial < n))
+        return BBFMM_BAD_ARGUMENT;
     if (settings->kernel_type < 0 || settings->kernel_type > 6 || settings->polynomial_degree < -1 ||
         settings->polynomial_degree > 2)
         return BBFMM_BAD_ARGUMENT;
@@ -439,11 +443,26 @@ int bbfmm_schwarz_create_sharded(bbfmm_handle *tree, const double *points, int64
     h->s.xchg_cap = exchange_capacity;
     h->s.allreduce = allreduce;
     h->s.allreduce_user = allreduce_user;
-    const int rc = schwarz_create_impl(tree, points, n, d, ld, settings, params, h->s);
+    const int rc = schwarz_create_impl(tree, points, n, d, ld, monomial_points, ld_monomial, settings, params, h->s);
     if (rc) return rc;
     *out = h.release();
     return BBFMM_OK;
     SCHWARZ_END_GUARD
+}
+
+int bbfmm_schwarz_create_sharded(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
+                                 const bbfmm_interpolant *settings, const bbfmm_ddm_params *params, int32_t rank,
+                                 int32_t world, double *d_exchange, int64_t exchange_capacity,
+                                 bbfmm_allreduce_fn allreduce, void *allreduce_user, bbfmm_schwarz **out) {
+    return bbfmm_schwarz_create_sharded_ex(tree, points, n, d, ld, nullptr, 0, settings, params, rank, world, d_exchange,
+                                           exchange_capacity, allreduce, allreduce_user, out);
+}
+
+int bbfmm_schwarz_create_ex(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
+                            const double *monomial_points, int64_t ld_monomial, const bbfmm_interpolant *settings,
+                            const bbfmm_ddm_params *params, bbfmm_schwarz **out) {
+    return bbfmm_schwarz_create_sharded_ex(tree, points, n, d, ld, monomial_points, ld_monomial, settings, params, 0, 1, nullptr, 0,
+                                           nullptr, nullptr, out);
 }
 
 int bbfmm_schwarz_create(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
@@ -529,8 +548,17 @@ int bbfmm_ddm_debug_level_create(const double *points, int64_t n, int32_t d, int
                                  const int64_t *dom_ptr, const int64_t *dom_idx, const uint8_t *dom_internal,
                                  const bbfmm_interpolant *settings, int32_t basis_size, int32_t solve_for_poly,
                                  bbfmm_ddm_debug_level **out) {
+    return bbfmm_ddm_debug_level_create_ex(points, n, d, ld, nullptr, 0, n_dom, dom_ptr, dom_idx, dom_internal, settings, basis_size,
+                                           solve_for_poly, out);
+}
+
+int bbfmm_ddm_debug_level_create_ex(const double *points, int64_t n, int32_t d, int64_t ld, const double *monomial_points,
+                                    int64_t ld_monomial, int64_t n_dom, const int64_t *dom_ptr, const int64_t *dom_idx,
+                                    const uint8_t *dom_internal, const bbfmm_interpolant *settings, int32_t basis_size,
+                                    int32_t solve_for_poly, bbfmm_ddm_debug_level **out) {
     if (!out) return BBFMM_BAD_ARGUMENT;
     *out = nullptr;
+    if (monomial_points && ld_monomial < n) return BBFMM_BAD_ARGUMENT;
     if (!points || !dom_ptr || !dom_idx || !dom_internal || !settings || n < 1 || d < 1 || d > 3 || ld < n || n_dom < 1)
         return BBFMM_BAD_ARGUMENT;
     if (settings->kernel_type < 0 || settings->kernel_type > 6 || settings->polynomial_degree < -1 ||
@@ -554,7 +582,7 @@ int bbfmm_ddm_debug_level_create(const double *points, int64_t n, int32_t d, int
         level.leaves[i].internal.assign(dom_internal + dom_ptr[i], dom_internal + dom_ptr[i + 1]);
     }
     const int rc = ddm_level_build(points, ld, d, &level, h->ks, h->nugget, settings->polynomial_degree, basis_size,
-                                   solve_for_poly != 0, nullptr, &h->lv);
+                                   solve_for_poly != 0, nullptr, &h->lv, nullptr, monomial_points, ld_monomial);
     if (rc) return rc;
     *out = h.release();
     return BBFMM_OK;

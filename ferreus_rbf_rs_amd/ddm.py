@@ -103,6 +103,15 @@ class InterpolantSettings:
         self.nugget, self.base_range, self.total_sill = float(nugget), float(base_range), float(total_sill)
 
 
+def _monomial_points(monomial_points, n, d):
+    if monomial_points is None:
+        return None
+    mpts = np.asfortranarray(np.atleast_2d(np.asarray(monomial_points, dtype=np.float64)))
+    if mpts.shape != (n, d):
+        raise ValueError("monomial_points must have the shape of points")
+    return mpts
+
+
 class DebugLevel:
     """Test hook (bbfmm_ddm_debug_level_*): the device's local solvers of one level on prescribed domains.
     `domains`: a list of (point indices, internal mask) over `points`.  After the build:
@@ -114,9 +123,12 @@ class DebugLevel:
       is_big, lu_taken  one large domain on the multi-launch path / factorised by the pivoted LU
     assembled() / factor(): per domain the packed lower triangle (column by column) before / after the factorisation."""
 
-    def __init__(self, points, domains, settings: InterpolantSettings, solve_for_poly: bool = False):
+    def __init__(self, points, domains, settings: InterpolantSettings, solve_for_poly: bool = False, monomial_points=None):
+        """monomial_points: with a global trend the world points, at which the monomials are evaluated with the cube
+        scaling of `points` (the transformed points: geometry and kernel blocks), domain.rs:161-184; None: `points`."""
         pts = np.asfortranarray(np.atleast_2d(np.asarray(points, dtype=np.float64)))
         n, d = pts.shape
+        mpts = _monomial_points(monomial_points, n, d)
         lib = L.load()
         ptr = np.zeros(len(domains) + 1, dtype=np.int64)
         ptr[1:] = np.cumsum([len(ix) for ix, _ in domains])
@@ -128,9 +140,9 @@ class DebugLevel:
                            settings.total_sill, 0)
         h = ctypes.c_void_p()
         self._h, self._lib = None, lib
-        rc = lib.bbfmm_ddm_debug_level_create(pts.ctypes.data, n, d, n, len(domains), ptr.ctypes.data, idx.ctypes.data,
-                                              internal.ctypes.data, ctypes.byref(st), settings.basis_size,
-                                              int(solve_for_poly), ctypes.byref(h))
+        rc = lib.bbfmm_ddm_debug_level_create_ex(pts.ctypes.data, n, d, n, None if mpts is None else mpts.ctypes.data, n,
+                                                 len(domains), ptr.ctypes.data, idx.ctypes.data, internal.ctypes.data,
+                                                 ctypes.byref(st), settings.basis_size, int(solve_for_poly), ctypes.byref(h))
         if rc != L.OK:
             raise ValueError(f"bbfmm_ddm_debug_level_create failed with status {rc}")
         self._h, self.n = h, n
@@ -193,16 +205,20 @@ class SchwarzPreconditioner:
     as the `m` of solvers.fgmres, or call it on a residual of N + basis_size values."""
 
     def __init__(self, tree, points, settings: InterpolantSettings, ddm_params: Optional[DDMParams] = None,
-                 global_scaling: bool = False, shard_group=None):
+                 global_scaling: bool = False, shard_group=None, monomial_points=None):
         """global_scaling: scale the coarse domain's monomials by the extents of all points (the basis of the
         system's monomial matrix) instead of by its own extents as the reference does (domain.rs:171-172);
         see csrc/schwarz.cpp.
         shard_group: a torch.distributed process group (True: the default group): the factors are sharded over its ranks
         (bbfmm_schwarz_create_sharded: every rank factorises and solves a contiguous share of each fine level's domains,
         a level's corrections are summed over the ranks -- RCCL all-reduce on the exchange tensor, staged through the host
-        when the group's backend is gloo); every rank must create it and call it in step."""
+        when the group's backend is gloo); every rank must create it and call it in step.
+        monomial_points: with a global trend, `points` are the transformed points (geometry, kernel blocks, cube scaling
+        factors) and these the world points at which every monomial basis is evaluated (bbfmm_schwarz_create_ex)."""
         pts = np.asfortranarray(np.atleast_2d(np.asarray(points, dtype=np.float64)))
         n, d = pts.shape
+        mpts = _monomial_points(monomial_points, n, d)
+        mp_arg = None if mpts is None else mpts.ctypes.data
         lib = L.load()
         st = L.Interpolant(settings.kernel_type, settings.polynomial_degree, settings.nugget, settings.base_range,
                            settings.total_sill, L.FLAG_GLOBAL_SCALING if global_scaling else 0)
@@ -243,12 +259,12 @@ class SchwarzPreconditioner:
             self._allreduce_cb = L.ALLREDUCE_FN(_allreduce)
         if self.world > 1:
             torch.cuda.synchronize(dev)
-            rc = lib.bbfmm_schwarz_create_sharded(tree._h, pts.ctypes.data, n, d, n, ctypes.byref(st), ctypes.byref(prm),
-                                                  self.rank, self.world, self._xchg.data_ptr(), n,
-                                                  ctypes.cast(self._allreduce_cb, ctypes.c_void_p), None, ctypes.byref(h))
+            rc = lib.bbfmm_schwarz_create_sharded_ex(tree._h, pts.ctypes.data, n, d, n, mp_arg, n, ctypes.byref(st),
+                                                     ctypes.byref(prm), self.rank, self.world, self._xchg.data_ptr(), n,
+                                                     ctypes.cast(self._allreduce_cb, ctypes.c_void_p), None, ctypes.byref(h))
         else:
-            rc = lib.bbfmm_schwarz_create(tree._h, pts.ctypes.data, n, d, n, ctypes.byref(st), ctypes.byref(prm),
-                                          ctypes.byref(h))
+            rc = lib.bbfmm_schwarz_create_ex(tree._h, pts.ctypes.data, n, d, n, mp_arg, n, ctypes.byref(st), ctypes.byref(prm),
+                                             ctypes.byref(h))
         if self.world > 1:
             # every rank raises, or none does: a rank that failed alone (a local system that is not positive definite, out of
             # memory) would leave its peers waiting in the first level's all-reduce

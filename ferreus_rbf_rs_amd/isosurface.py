@@ -82,6 +82,16 @@ def _isovalues(isovalues):
     return v
 
 
+def _field_terms(drift):
+    """The rbf.FieldTerms given as `drift` (polynomial of degree -1 .. 2 and / or a global trend), else None."""
+    from .rbf import FieldTerms
+    if not isinstance(drift, FieldTerms):
+        return None
+    if drift.d != 3 or drift.k != 1:
+        raise ValueError("the field terms of an isosurface need d = 3 and one column")
+    return drift
+
+
 def _drift(drift):
     """None, [a, b0, b1, b2] or (a, [b0, b1, b2]): the affine drift a + b . x."""
     if drift is None:
@@ -355,7 +365,9 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
     lib = L.load()
     method, fin, isect = _cluster(cluster), _finish(finish), _self_intersections(self_intersections)
     fol, sd = _follow(follow), _seeds(seeds)
-    ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(drift)
+    terms = _field_terms(drift)
+    cterms = terms._c() if terms is not None else None
+    ext, iso, d = _ext(extents), _isovalues(isovalues), _drift(None if terms is not None else drift)
     field_t = None
     if return_field:
         import torch
@@ -364,8 +376,10 @@ def build_isosurfaces(tree, extents, resolution, isovalues, *, drift=None, retur
         field_t = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tree.device()}")
         torch.cuda.synchronize(field_t.device)
     res = ctypes.c_void_p()
-    if fin or isect or fol:
+    if fin or isect or fol or cterms is not None:
         opts = _options(method, fin, batch_bytes, isect, fol, sd if fol else None)
+        if cterms is not None:
+            opts.terms = ctypes.addressof(cterms)
         rc = lib.bbfmm_build_isosurfaces_opts(tree._h, ext.ctypes.data, float(resolution), iso.ctypes.data, len(iso),
                                               d.ctypes.data if d is not None else None,
                                               field_t.data_ptr() if field_t is not None else None, ctypes.addressof(opts),

@@ -328,6 +328,7 @@ int bbfmm_isosurface_curvature_stats(const bbfmm_isosurface_result *r, int32_t i
 /* Options of the *_opts entries.  size: sizeof(bbfmm_isosurface_options) as the caller was compiled; fields beyond it
  * take their defaults (CLUSTER_NONE, FINISH_RAW, batch_bytes 0, SELF_INTERSECTIONS_IGNORE, FOLLOW_DENSE, no seeds), as
  * does every field with options == NULL. */
+struct bbfmm_interpolant_terms; /* below: "The interpolant around the tree" */
 typedef struct bbfmm_isosurface_options {
     int64_t size;
     int32_t cluster_method; /* BBFMM_CLUSTER_* */
@@ -338,6 +339,18 @@ typedef struct bbfmm_isosurface_options {
     const double *seeds;    /* host, n_seeds x 3 column-major with leading dimension seeds_ld, or NULL */
     int64_t n_seeds;
     int64_t seeds_ld;
+    /* The field terms of an interpolant (read only where size covers the pointer; NULL: none), d = 3 and k = 1: the
+     * polynomial of any degree -1 .. 2 on (x - translation) / scale, evaluated at the WORLD point of every lattice node and
+     * seed, and a global trend's (B, b): the tree is asked at x B + b.  The clamp, the lattice and the whole extraction
+     * stay in world coordinates; the check that every node lies in the tree's cube tests the transformed corners of the
+     * lattice box (rbf.rs:599-613).  The seed projection's gradient is the tree's times B^T plus the polynomial's.  With
+     * a trend the seeds must be given (the tree's own points are the transformed ones).  Giving both these terms and the
+     * `drift` argument is BBFMM_BAD_ARGUMENT; the 4-value drift keeps its meaning.  On a BBFMM_FLAG_DETERMINISTIC handle
+     * the field with terms is evaluated with a fixed split of every leaf's targets (64 per pass in 8 source slices instead
+     * of the split sized to their number), so a node's value is the same double in the dense and the followed pass and
+     * follow = surface gives the dense mesh bit for bit; what the fixed split costs on a large lattice is not measured.
+     * A default handle keeps the tuned split (its f64 atomics rule the property out anyway). */
+    const struct bbfmm_interpolant_terms *terms;
 } bbfmm_isosurface_options;
 /* The counts of BBFMM_FOLLOW_SURFACE for mesh i, stats_out[8] (all 0 with BBFMM_FOLLOW_DENSE): seeds given, distinct seed
  * cells, Newton steps run, seed bricks, rounds, bricks visited, nodes evaluated for this isovalue, nodes of E. */
@@ -750,7 +763,8 @@ int bbfmm_ddm_domain(const bbfmm_ddm *t, int32_t level, int64_t domain, int64_t 
  * Domain::solve (domain.rs:153-475) for all leaf domains of a level batched on the device: Beatson's Q
  * formulation, Q^T A Q assembled from the points, blocked Cholesky and substitutions one workgroup
  * per domain.  The two partial matvecs per fine level go through `tree`
- * (IterativeSolver::precon, rbf.rs:140-155).  Global trend transforms are not supported.
+ * (IterativeSolver::precon, rbf.rs:140-155).  With a global trend the
+ * monomials are evaluated at the world points: bbfmm_schwarz_create_ex below.
  * A domain whose Cholesky factorisation fails is solved through a host-computed inverse instead (the
  * role of the reference's LBL^T fallback, domain.rs:60-68); the one large coarse domain (more than 2048
  * points) is then factorised by pivoted LU on the device (rocSOLVER, loaded on demand).  BBFMM_UNSUPPORTED
@@ -794,6 +808,19 @@ int bbfmm_schwarz_create_sharded(bbfmm_handle *tree, const double *points, int64
                                  const bbfmm_interpolant *settings, const bbfmm_ddm_params *params, int32_t rank,
                                  int32_t world, double *d_exchange, int64_t exchange_capacity,
                                  bbfmm_allreduce_fn allreduce, void *allreduce_user, bbfmm_schwarz **out);
+/* The same two with a global trend (GlobalTrend, global_trend.rs): `points` are the TRANSFORMED points -- the geometry of
+ * the decomposition, the kernel blocks and the cube scaling factors of every monomial basis come from them -- and the
+ * monomials are evaluated at monomial_points (n x d, ld_monomial), the WORLD points, as the reference does
+ * (domain.rs:161-175; rbf.rs:418-421, 476-491; domain_decomposition.rs:315, 338).  monomial_points NULL is the entry
+ * above, bit for bit (bbfmm_schwarz_create forwards with NULL). */
+int bbfmm_schwarz_create_ex(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
+                            const double *monomial_points, int64_t ld_monomial, const bbfmm_interpolant *settings,
+                            const bbfmm_ddm_params *params, bbfmm_schwarz **out);
+int bbfmm_schwarz_create_sharded_ex(bbfmm_handle *tree, const double *points, int64_t n, int32_t d, int64_t ld,
+                                    const double *monomial_points, int64_t ld_monomial, const bbfmm_interpolant *settings,
+                                    const bbfmm_ddm_params *params, int32_t rank, int32_t world, double *d_exchange,
+                                    int64_t exchange_capacity, bbfmm_allreduce_fn allreduce, void *allreduce_user,
+                                    bbfmm_schwarz **out);
 int64_t bbfmm_schwarz_factor_bytes(const bbfmm_schwarz *h); /* device bytes of the packed factors this handle holds */
 /* domains of `level` this handle factorised (returned), the first of them and the level's total in the decomposition */
 int64_t bbfmm_schwarz_domains_owned(const bbfmm_schwarz *h, int32_t level, int64_t *first, int64_t *total);
@@ -833,6 +860,11 @@ int bbfmm_ddm_debug_level_create(const double *points, int64_t n, int32_t d, int
                                  const int64_t *dom_ptr, const int64_t *dom_idx, const uint8_t *dom_internal,
                                  const bbfmm_interpolant *settings, int32_t basis_size, int32_t solve_for_poly,
                                  bbfmm_ddm_debug_level **out);
+/* ... with the monomials evaluated at monomial_points (NULL: at points), as bbfmm_schwarz_create_ex */
+int bbfmm_ddm_debug_level_create_ex(const double *points, int64_t n, int32_t d, int64_t ld, const double *monomial_points,
+                                    int64_t ld_monomial, int64_t n_dom, const int64_t *dom_ptr, const int64_t *dom_idx,
+                                    const uint8_t *dom_internal, const bbfmm_interpolant *settings, int32_t basis_size,
+                                    int32_t solve_for_poly, bbfmm_ddm_debug_level **out);
 void bbfmm_ddm_debug_level_destroy(bbfmm_ddm_debug_level *h);
 int bbfmm_ddm_debug_level_info(const bbfmm_ddm_debug_level *h, int64_t *info);
 int bbfmm_ddm_debug_level_layout(const bbfmm_ddm_debug_level *h, int32_t *k, int64_t *indices, uint8_t *internal, double *q,
@@ -842,6 +874,80 @@ int bbfmm_ddm_debug_level_factor(const bbfmm_ddm_debug_level *h, double *out);
 int bbfmm_ddm_debug_level_solve(bbfmm_ddm_debug_level *h, const double *values, double *out, int64_t n, int32_t all_points);
 /* a bbfmm_apply_fn: user = bbfmm_schwarz*, vectors of N + basis_size doubles */
 int bbfmm_schwarz_apply(void *user, const double *residual, double *correction, int64_t n);
+
+/* ---- The interpolant around the tree: what ferreus_rbf::RBFInterpolator (ferreus_rbf/src/rbf.rs:304-1298) adds to the
+ * kernel sum.  Arrays of points, values and gradients are column-major like every other entry's (column a at + a * ld);
+ * gradients are m x (k * d), columns [rhs0_dx, rhs0_dy, rhs0_dz, rhs1_dx, ...].  Nothing throws across the ABI. */
+
+/* GlobalTrendTransform::new (global_trend.rs:135-264) for GlobalTrend::One / Two / Three (d = 1, 2, 3).
+ * params: d = 1 {major_ratio}; d = 2 {rotation_angle, major_ratio, minor_ratio}; d = 3 {dip, dip_direction, pitch,
+ * major_ratio, semi_major_ratio, minor_ratio}; angles in degrees.  affine_out and inverse_out are (d + 1) x (d + 1)
+ * row-major for row-vector points, [x 1] * affine: its leading d x d block is B, the first d entries of its last row b
+ * (transform_points, global_trend.rs:266-272).  The matrices are multiplied in the reference's order (transform_back *
+ * scale * rotation * transform, then transposed); the inverse is taken by LU with partial pivoting on the host. */
+int bbfmm_global_trend_transform(int32_t d, const double *params, const double *center, double *affine_out, double *inverse_out);
+
+/* duplicate_cutoff_distance (rbf.rs:1391-1415): h_ref when |phi(h_ref) - phi(0)| is already within the target eps *
+ * |phi(h_ref) - phi(0)| (only when that rise is 0), else a root r in (0, h_ref) of |phi(r) - phi(0)| = target by
+ * bisection to 1e-13 relative, towards the smallest crossing.  The rise is evaluated without the subtraction's
+ * cancellation (r, |r^2 ln r|, r^3, slope * r), so the root is that of the kernel's formula where the reference's
+ * own residual is a step function of one ulp of phi(0) (the spheroidal family). */
+int bbfmm_duplicate_cutoff_distance(const bbfmm_interpolant *interpolant, double h_ref, double *out);
+
+/* remove_duplicates (rbf.rs:1430-1467) with tol given: point i is kept iff no KEPT j < i has |x_i - x_j|_inf <= tol
+ * (inclusive, kdtree.rs:187); keep_out (n entries allocated) receives the n_keep_out kept indices, ascending.
+ * where = 0: the host (a hash of a uniform grid; the checker and the path without a device).  where = 1: the device --
+ * points sorted by grid cell key (rocPRIM), each point probing the 3^d cells around it for earlier neighbours, resolved
+ * in rounds to the fixed point (no earlier neighbour, or all of them dropped: kept; an earlier kept neighbour: dropped;
+ * one status word read back per round, *rounds_out of them), which is the sequential set exactly.  The cell side is
+ * max(tol (1 + 2^-10), largest extent / 2^20 (2^30 below 3-D)), so the key always fits 64 bits: a tolerance far below
+ * the extent costs larger cells, never another path.  2^31 points or more, or a machine with no device at all, take
+ * the host path from where = 1 as well (the same set).  Cost, neither case measured: a point scans its 3^d cells linearly,
+ * so a cloud that a few far outliers squeeze into a handful of cells costs O(n^2) pair tests per round, and a chain of
+ * n points each within tol of the next costs n / 2 rounds of one launch and one read each.
+ * Non-finite coordinates or tol are BBFMM_BAD_ARGUMENT. */
+int bbfmm_remove_duplicates(const double *points, int64_t n, int32_t d, int64_t ld, double tol, int32_t where, int64_t *keep_out,
+                            int64_t *n_keep_out, int64_t *rounds_out);
+
+/* The terms of one interpolant besides its kernel sum.  size = sizeof(bbfmm_interpolant_terms). */
+typedef struct bbfmm_interpolant_terms {
+    int64_t size;
+    int32_t d;                  /* 1..3 */
+    int32_t polynomial_degree;  /* -1 none .. 2 quadratic */
+    int32_t k;                  /* value columns */
+    int32_t has_affine;         /* 0: no global trend (B, b ignored) */
+    const double *coefficients; /* basis_size x k polynomial coefficients, column c at + c * ld_coefficients, monomials in
+                                 * the order of polynomials.rs:30-74 (1 | s_a | s_a s_b, a <= b) */
+    int64_t ld_coefficients;
+    double translation[3], scale[3]; /* s = (x - translation) / scale, common.rs:330-336 */
+    double B[9], b[3];               /* x' = x B + b, B row-major d x d */
+} bbfmm_interpolant_terms;
+
+/* The three per-target operations on caller arrays, on the host (where = 0) or the device (where = 1, one kernel
+ * between an upload and a download), one __host__ __device__ definition of the arithmetic behind both
+ * (csrc/interpolant_terms.hpp; sums in a fixed order, never contracted to fused multiply-adds):
+ *   which = 0, affine_points: points_out = x B + b, summed a = 0 .. d-1 then + b (global_trend.rs:266-272);
+ *   which = 1, polynomial_terms: values[:, c] += sum_j m_j(s) coefficients[j, c], j ascending, and with grad
+ *              grad[:, c d + a] += d/dx_a of that sum (polynomials.rs:64-116); x are WORLD points;
+ *   which = 2, trend_gradients: grad <- grad B^T per target and column, in place (rbf.rs:1272-1298). */
+int bbfmm_debug_interpolant_terms(int32_t where, int32_t which, const bbfmm_interpolant_terms *terms, const double *x, int64_t m,
+                                  int64_t ldx, double *points_out, int64_t ldp, double *values, int64_t ldv, double *grad,
+                                  int64_t ldg);
+
+/* _evaluate (rbf.rs:1180-1270) in one call: the targets x (WORLD points) are mapped by the trend on the device, the
+ * existing Full (mode 0: bbfmm_evaluate[_with_gradients]) or Leaves (mode 1: bbfmm_evaluate_leaves[...]) pass runs at
+ * the mapped targets with the same w / rows / k / ldw, then one kernel applies trend_gradients, nugget * w (nugget != 0
+ * asks for it: the at-source case, m = N and w given) and polynomial_terms, in the reference's order.  terms NULL, or
+ * no trend with degree -1 and nugget 0, is the plain entry point bit for bit.  The mapped targets and the results
+ * make one extra trip through the host between the trend kernel, the tree's pass and the terms kernel (the tree's
+ * passes take host targets; each kernel sits between its own upload and download on the null stream).  A failure here
+ * sets the handle's bbfmm_last_error like the entries it forwards to.  On a device group (FERREUS_BBFMM_DEVICES) the terms run on the primary part's device. */
+#define BBFMM_EVALUATE_FULL 0
+#define BBFMM_EVALUATE_LEAVES 1
+int bbfmm_evaluate_interpolant(bbfmm_handle *h, int32_t mode, int32_t with_gradients, const double *w, int64_t rows, int32_t k,
+                               int64_t ldw, const double *x, int64_t m, int64_t ldx, const bbfmm_interpolant_terms *terms,
+                               double nugget, double *values_out, int64_t ldo, double *grad_out, int64_t ldg,
+                               int64_t *bad_point_index);
 
 #ifdef __cplusplus
 }
