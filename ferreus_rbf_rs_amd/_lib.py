@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FERREUS_BBFMM_HIP_LIB") or os.path.join(HERE, "libferreus_bbfmm_hip.so")
 
 # bbfmm_status
-OK, POINT_OUTSIDE_TREE, KERNEL_NO_GRADIENTS, BAD_ARGUMENT, DEVICE_ERROR, UNSUPPORTED = range(6)
+OK, POINT_OUTSIDE_TREE, KERNEL_NO_GRADIENTS, BAD_ARGUMENT, DEVICE_ERROR, UNSUPPORTED, CALLBACK_FAILED = range(7)
 FLAG_HOST_ONLY = 1
 FLAG_M2L_SHARED_BASIS = 2  # extension beyond the reference: M2L stages in one basis per level
 FLAG_DIRECT_SMALL_W_LEAVES = 4  # extension beyond the reference: small W-list leaves as near field
@@ -77,6 +77,10 @@ SIGNATURES = {
     "bbfmm_isosurface_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_build_isosurfaces_opts": (ctypes.c_int, [c_p, c_p, c_f64, c_p, c_i32, c_p, c_p, c_p, c_p]),
     "bbfmm_isosurfaces_from_values_opts": (ctypes.c_int, [c_p, c_p, c_p, c_f64, c_p, c_i32, c_p, c_p]),
+    "bbfmm_isosurfaces_from_fields_opts": (ctypes.c_int, [c_p, c_i32, c_p, c_i32, c_p, c_f64, c_p, c_i32, c_p, c_p, c_p]),
+    "bbfmm_isosurfaces_from_function_opts": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_f64, c_p, c_i32, c_p, c_p]),
+    "bbfmm_debug_evaluate_fields": (ctypes.c_int, [c_p, c_i32, c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64]),
+    "bbfmm_debug_field_program": (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_isosurface_follow_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
@@ -221,6 +225,19 @@ class InterpolantTerms(ctypes.Structure):
     _fields_ = [("size", c_i64), ("d", c_i32), ("polynomial_degree", c_i32), ("k", c_i32), ("has_affine", c_i32),
                 ("coefficients", ctypes.c_void_p), ("ld_coefficients", c_i64), ("translation", c_f64 * 3), ("scale", c_f64 * 3),
                 ("B", c_f64 * 9), ("b", c_f64 * 3)]
+
+
+class FieldOperand(ctypes.Structure):
+    """bbfmm_field_operand"""
+    _fields_ = [("size", c_i64), ("kind", c_i32), ("axis", c_i32), ("handle", ctypes.c_void_p), ("terms", ctypes.c_void_p),
+                ("scale", c_f64), ("offset", c_f64), ("affine", c_f64 * 4)]
+
+
+FIELD_MODEL, FIELD_HEIGHT, FIELD_AFFINE = 0, 1, 2
+FIELD_OP_MAX, FIELD_OP_MIN, FIELD_OP_NEG = -1, -2, -3
+# bbfmm_field_fn, bbfmm_gradient_fn
+FIELD_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(c_f64), c_i64, c_i64, ctypes.POINTER(c_f64), c_p)
+GRADIENT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(c_f64), c_i64, c_i64, ctypes.POINTER(c_f64), ctypes.POINTER(c_f64), c_i64, c_p)
 
 
 class DdmParams(ctypes.Structure):

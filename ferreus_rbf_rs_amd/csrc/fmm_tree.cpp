@@ -1332,10 +1332,10 @@ bool FmmTree::supports_gradients() const { return kernel_supports_gradients(kern
 int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
                                     int64_t *bad_point_index, double *d_grad, bool batch_independent) {
     if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
-    if (d_ != 3) return fail(BBFMM_BAD_ARGUMENT, "device-resident targets need d = 3");
     if (nrhs_ != 1 || !have_locals_) return fail(BBFMM_BAD_ARGUMENT, "set_local_coefficients (one column) must be called first");
     if (multipoles_partial_) return fail(BBFMM_BAD_ARGUMENT, kPartialMultipoles);
-    if (m < 0 || (m > 0 && (!d_x0 || !d_x1 || !d_x2))) return fail(BBFMM_BAD_ARGUMENT, "bad device target arrays");
+    // (the arrays past d are not read: points_to_leaves and the gather loop over d)
+    if (m < 0 || (m > 0 && (!d_x0 || (d_ > 1 && !d_x1) || (d_ > 2 && !d_x2)))) return fail(BBFMM_BAD_ARGUMENT, "bad device target arrays");
     if (m >= (int64_t(1) << 31)) return fail(BBFMM_BAD_ARGUMENT, "more than 2^31-1 target points");
     if (d_grad && !d_out) return fail(BBFMM_BAD_ARGUMENT, "gradients at device targets need their values too");
     if (d_grad && !kernel_supports_gradients(kernel_.id))

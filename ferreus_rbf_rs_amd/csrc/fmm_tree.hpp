@@ -167,7 +167,7 @@ class FmmTree {
                uint32_t flags);
     int set_weights(const double *w, int64_t rows, int k, int64_t ldw);                 // bbfmm.rs:383-401
     int set_local_coefficients(const double *w, int64_t rows, int k, int64_t ldw);      // bbfmm.rs:518-524
-    // Leaves mode (after set_local_coefficients, one column) at m targets that are already on the device (SoA, d == 3):
+    // Leaves mode (after set_local_coefficients, one column) at m targets that are already on the device (SoA; the arrays past d may be null):
     // the target set, grouping and leaf pass of evaluate(..., leaves_only = true) with no host copy; values to d_out in
     // row order, on the handle's stream (isosurface lattice nodes).  d_out == nullptr: only checks that every target
     // lies in the tree (BBFMM_POINT_OUTSIDE_TREE, *bad_point_index the first row that does not).  d_grad (with d_out): the
@@ -225,6 +225,7 @@ class FmmTree {
     hipStream_t stream() const { return stream_; }
     bool host_only() const { return host_only_; }
     bool deterministic() const { return deterministic_; }
+    bool leaves_ready() const { return nrhs_ == 1 && have_locals_; } // what evaluate_leaves_device asks for
     // The handle may be used from any host thread (a solver's worker threads start with device 0 current):
     // the C entry points call this first.
     void bind_device() const {

@@ -140,7 +140,7 @@ int terms_finish_device(const InterpolantTerms &t, const double *x, int64_t m, i
     return terms_pass(t, x, m, ldx, values, ldv, grad, ldg, t.has_affine, 1, nugget, w, ldw);
 }
 
-// ---- device-resident targets (3-D, one column)
+// ---- device-resident targets (one column; the coordinate arrays past t.d are not read and may be null)
 
 namespace {
 
@@ -148,12 +148,12 @@ __global__ __launch_bounds__(kThreads) void affine_soa_kernel(InterpolantTerms t
                                                               const double *__restrict__ x1, const double *__restrict__ x2, int64_t m,
                                                               double *__restrict__ y0, double *__restrict__ y1, double *__restrict__ y2) {
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kThreads) {
-        const double p[3] = {x0[i], x1[i], x2[i]};
+        const double p[3] = {x0[i], t.d > 1 ? x1[i] : 0.0, t.d > 2 ? x2[i] : 0.0};
         double q[3];
         affine_point(t, p, q);
         y0[i] = q[0];
-        y1[i] = q[1];
-        y2[i] = q[2];
+        if (t.d > 1) y1[i] = q[1];
+        if (t.d > 2) y2[i] = q[2];
     }
 }
 
@@ -161,10 +161,10 @@ __global__ __launch_bounds__(kThreads) void field_soa_kernel(InterpolantTerms t,
                                                              const double *__restrict__ x1, const double *__restrict__ x2, int64_t m,
                                                              double *__restrict__ vals, double *__restrict__ grad) {
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kThreads) {
-        const double p[3] = {x0[i], x1[i], x2[i]};
+        const double p[3] = {x0[i], t.d > 1 ? x1[i] : 0.0, t.d > 2 ? x2[i] : 0.0};
         double v = vals[i], g[3] = {0, 0, 0};
         if (grad) {
-            for (int a = 0; a < 3; ++a) g[a] = grad[a * m + i];
+            for (int a = 0; a < t.d; ++a) g[a] = grad[a * m + i];
             if (t.has_affine) trend_gradient_column(t, g);
         }
         double mono[kMaxMonomials], dm[kMaxMonomials][3];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void field_soa_kernel(InterpolantTerms t,
         if (nb > 0) polynomial_column(t, nb, mono, dm, 0, &v, grad ? g : nullptr);
         vals[i] = v;
         if (grad)
-            for (int a = 0; a < 3; ++a) grad[a * m + i] = g[a];
+            for (int a = 0; a < t.d; ++a) grad[a * m + i] = g[a];
     }
 }
 
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void field_soa_kernel(InterpolantTerms t,
 int terms_affine_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *y0,
                             double *y1, double *y2, hipStream_t stream) {
     if (m <= 0) return 0;
-    if (t.d != 3) return 1;
+    if (t.d < 1 || t.d > 3 || !x0 || !y0 || (t.d > 1 && (!x1 || !y1)) || (t.d > 2 && (!x2 || !y2))) return 1;
     hipLaunchKernelGGL(affine_soa_kernel, dim3(grid_for(m)), dim3(kThreads), 0, stream, t, x0, x1, x2, m, y0, y1, y2);
     TERMS_HIP(hipGetLastError());
     return 0;
@@ -190,7 +190,7 @@ int terms_affine_soa_device(const InterpolantTerms &t, const double *x0, const d
 int terms_field_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *vals,
                            double *grad, hipStream_t stream) {
     if (m <= 0) return 0;
-    if (t.d != 3 || t.k != 1 || !vals) return 1;
+    if (t.d < 1 || t.d > 3 || t.k != 1 || !vals || !x0 || (t.d > 1 && !x1) || (t.d > 2 && !x2)) return 1;
     hipLaunchKernelGGL(field_soa_kernel, dim3(grid_for(m)), dim3(kThreads), 0, stream, t, x0, x1, x2, m, vals, grad);
     TERMS_HIP(hipGetLastError());
     return 0;

@@ -212,7 +212,9 @@ int terms_finish_device(const InterpolantTerms &t, const double *x, int64_t m, i
                         double *grad, int64_t ldg, double nugget, const double *w, int64_t ldw);
 // The same on device-resident targets, one pointer per axis, on `stream` (the lattice field of the isosurfacer, k = 1;
 // t.lambda is a DEVICE pointer here): y = x B + b; and vals[i] += polynomial, grad[a * m + i] <- (grad B^T)[a] + its
-// gradient (grad may be null, the trend applies when t.has_affine).  Nothing is synchronised.
+// gradient (grad may be null, the trend applies when t.has_affine).  Nothing is synchronised.  t.d = 1 or 2 (a height
+// operand of a composite field): the arrays past t.d are not read and may be null, grad holds t.d columns of m, and the
+// arithmetic per point is that of the AoS entries above.
 int terms_affine_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *y0,
                             double *y1, double *y2, hipStream_t stream);
 int terms_field_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *vals,

@@ -112,6 +112,10 @@ class FmmError(ValueError):
     """FmmError (bbfmm.rs:20-45); the PyO3 binding raises ValueError with these messages."""
 
 
+class CallbackFailed(FmmError):
+    """BBFMM_CALLBACK_FAILED: a caller's field callback returned nonzero (bbfmm_isosurfaces_from_function_opts)"""
+
+
 class PointOutsideTree(FmmError):
     def __init__(self, point_index: int, leaf: bool = False):
         what = "FMM leaf evaluation failed" if leaf else "FMM evaluation failed"

@@ -347,7 +347,9 @@ def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0, met
 
 
 def _raise(rc, msg, leaf=True):
-    from .fmm_tree import FmmError, PointOutsideTree
+    from .fmm_tree import CallbackFailed, FmmError, PointOutsideTree
+    if rc == L.CALLBACK_FAILED:
+        raise CallbackFailed(msg)
     if rc == L.POINT_OUTSIDE_TREE:
         e = PointOutsideTree(-1, leaf)
         e.args = (msg,)

@@ -26,7 +26,7 @@ from .fmm_tree import FmmTree, KernelParams, KernelType, M2LCompressionType, Sph
 
 __all__ = ["RBFInterpolator", "GlobalTrend", "InterpolantSettings", "RBFKernelType", "SpheroidalOrder", "Drift", "FittingAccuracy",
            "FittingAccuracyType", "Params", "FmmParams", "DDMParams", "Solvers", "FmmCompressionType", "Coefficients", "Mesh",
-           "BoundaryClosure", "Progress", "DuplicatesRemoved", "SolverIteration", "SurfacingProgress", "Message", "FieldTerms",
+           "BoundaryClosure", "ClusterMethod", "Progress", "DuplicatesRemoved", "SolverIteration", "SurfacingProgress", "Message", "FieldTerms",
            "global_trend_transform", "duplicate_cutoff_distance", "remove_duplicates", "affine_points", "polynomial_terms",
            "trend_gradients", "evaluate_interpolant", "default_drift", "default_fmm_interpolation_order"]
 
@@ -227,6 +227,13 @@ class BoundaryClosure(enum.Enum):
     None_ = 0
     ClosePositive = 1
     CloseNegative = 2
+
+
+class ClusterMethod(enum.Enum):
+    """ferreus_rmt's ClusterMethod; the string options "none", "average" and "curvature" keep working everywhere"""
+    None_ = 0
+    Average = 1
+    CurvatureWeighted = 2
 
 
 class Mesh:

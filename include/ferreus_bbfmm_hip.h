@@ -34,7 +34,8 @@ typedef enum {
     BBFMM_KERNEL_NO_GRADIENTS = 2,        /* FmmError::KernelDoesNotSupportGradients */
     BBFMM_BAD_ARGUMENT = 3,               /* the reference panics (e.g. bbfmm.rs:293-298) */
     BBFMM_DEVICE_ERROR = 4,               /* HIP failure or no device */
-    BBFMM_UNSUPPORTED = 5                 /* valid in the reference, not built here yet */
+    BBFMM_UNSUPPORTED = 5,                /* valid in the reference, not built here yet */
+    BBFMM_CALLBACK_FAILED = 6             /* a caller's field callback returned nonzero (bbfmm_isosurfaces_from_function_opts) */
 } bbfmm_status;
 
 /* KernelType, in registry order (ferreus_rbf_utils/src/utils.rs:558-571).
@@ -366,6 +367,77 @@ int bbfmm_build_isosurfaces_opts(bbfmm_handle *h, const double *extents, double 
 int bbfmm_isosurfaces_from_values_opts(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                        const double *isovalues, int32_t n_isovalues,
                                        const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out);
+
+/* ---- Isosurfaces of any field (ferreus_rmt::build_isosurface with its surface_fn; DESIGN.md "Composite fields").
+ * A composite field is evaluated on the device from up to 8 operands and one postfix program of at most 64 int32 codes
+ * on a stack at most 8 deep.  An operand gives a value v and a gradient at a world point x:
+ *   BBFMM_FIELD_MODEL:  the interpolant of a d = 3 handle (after bbfmm_set_local_coefficients, one column) with its
+ *                       optional terms (d = 3, k = 1): exactly the field bbfmm_build_isosurfaces_opts evaluates for that
+ *                       handle and those terms (trend map, leaf pass, terms kernel; the fixed split of every leaf's
+ *                       targets with terms on a BBFMM_FLAG_DETERMINISTIC handle);
+ *   BBFMM_FIELD_HEIGHT: x[axis] - g(u, v), (u, v) the other two coordinates in ascending axis order and g the
+ *                       interpolant of a d = 2 handle with its optional terms (d = 2, k = 1); the gradient is e_axis
+ *                       minus grad g on the other two axes;
+ *   BBFMM_FIELD_AFFINE: affine[0] + affine[1] x0 + affine[2] x1 + affine[3] x2, summed left to right; no handle.
+ * What an operand pushes is scale * v + offset (one multiply, then one add, never fused) with the gradient scale * grad v.
+ * Program codes: >= 0 pushes that operand; BBFMM_FIELD_OP_MAX and _MIN pop b, then a, and push a >= b ? a : b and
+ * a <= b ? a : b (not fmax / fmin: a tie keeps a with its sign of zero, a NaN gives b), the gradient travelling with
+ * the value chosen; BBFMM_FIELD_OP_NEG negates both.  A valid program leaves exactly one entry.  Everything is checked
+ * on the host before any device work (BBFMM_BAD_ARGUMENT, the message names the operand or the program position):
+ * stack underflow or depth, unknown codes, operand ids, the entries left, non-finite scale / offset / affine, a handle
+ * of the wrong dimension, without local coefficients for one column, host-only, a device group, or on another device
+ * than the first, more than 8 operands or 64 codes. */
+#define BBFMM_FIELD_MODEL 0
+#define BBFMM_FIELD_HEIGHT 1
+#define BBFMM_FIELD_AFFINE 2
+#define BBFMM_FIELD_OP_MAX (-1)
+#define BBFMM_FIELD_OP_MIN (-2)
+#define BBFMM_FIELD_OP_NEG (-3)
+typedef struct bbfmm_field_operand {
+    int64_t size;          /* sizeof(bbfmm_field_operand) as the caller was compiled */
+    int32_t kind;          /* BBFMM_FIELD_* */
+    int32_t axis;          /* BBFMM_FIELD_HEIGHT: 0 .. 2 */
+    bbfmm_handle *handle;  /* MODEL: d = 3, HEIGHT: d = 2, AFFINE: NULL */
+    const struct bbfmm_interpolant_terms *terms; /* of that handle's interpolant, or NULL */
+    double scale, offset;
+    double affine[4];      /* BBFMM_FIELD_AFFINE */
+} bbfmm_field_operand;
+/* Meshes of the composite field, with every option of bbfmm_isosurface_options except terms (NULL here: terms belong to
+ * operands) and the accessors above.  BBFMM_FOLLOW_SURFACE needs the seeds.  Before any evaluation the lattice box is
+ * tested against every MODEL operand's cube (through its trend's transformed corners) and on its two axes against every
+ * HEIGHT operand's square: BBFMM_POINT_OUTSIDE_TREE naming the operand.  The extraction runs on the stream of the first
+ * operand with a handle (one of the call's own without any); every tree evaluates on its own stream and returns
+ * synchronised, the affine, height and program kernels run on the extraction's stream.  The seed projection takes the
+ * composite gradient when every tree operand's kernel has gradients and BBFMM_ISO_SEED_GRADIENTS is not `differences`,
+ * else central differences of the composite value.  d_field_out as for bbfmm_build_isosurfaces.  *out is set whenever out
+ * is not NULL and holds the message of a failure (bbfmm_isosurface_error). */
+int bbfmm_isosurfaces_from_fields_opts(const bbfmm_field_operand *operands, int32_t n_operands, const int32_t *program,
+                                       int32_t n_program, const double *extents, double resolution, const double *isovalues,
+                                       int32_t n_isovalues, double *d_field_out, const bbfmm_isosurface_options *options,
+                                       bbfmm_isosurface_result **out);
+/* Meshes of a caller's function.  x: m points, coordinate a of point t at x[a * ldx + t]; values: m doubles; gradients:
+ * component a of point t at gradients[a * ldg + t].  All host arrays; nonzero is failure and ends the extraction with
+ * BBFMM_CALLBACK_FAILED.  Every batch of lattice nodes is downloaded, handed over and its values uploaded, on the current
+ * device and a stream of the call's own.  gradient NULL: the seed projection of BBFMM_FOLLOW_SURFACE (seeds required)
+ * takes central differences of `field`.  *out is set whenever out is not NULL and holds the message of a failure. */
+typedef int (*bbfmm_field_fn)(const double *x, int64_t m, int64_t ldx, double *values, void *user);
+typedef int (*bbfmm_gradient_fn)(const double *x, int64_t m, int64_t ldx, double *values, double *gradients, int64_t ldg, void *user);
+int bbfmm_isosurfaces_from_function_opts(bbfmm_field_fn field, bbfmm_gradient_fn gradient, void *user, const double *extents,
+                                         double resolution, const double *isovalues, int32_t n_isovalues,
+                                         const bbfmm_isosurface_options *options, bbfmm_isosurface_result **out);
+/* The composite field at m host points (coordinate a of point t at x[a * ldx + t]) through the path of the extraction's
+ * FieldFn / GradFn: upload, every tree operand's check of the points (BBFMM_POINT_OUTSIDE_TREE), one column per operand,
+ * the program kernel, download.  values: m doubles; gradients: NULL, or component a of point t at gradients[a * ldg + t]
+ * (BBFMM_KERNEL_NO_GRADIENTS where a tree operand's kernel has none).  The message of a failure is bbfmm_last_error of
+ * the first operand that has a handle. */
+int bbfmm_debug_evaluate_fields(const bbfmm_field_operand *operands, int32_t n_operands, const int32_t *program, int32_t n_program,
+                                const double *x, int64_t m, int64_t ldx, double *values, double *gradients, int64_t ldg);
+/* The program alone on caller columns, on the host (where = 0) or the device (where = 1), one __host__ __device__
+ * definition behind both (csrc/field_program.hpp).  V: m x n_operands, G: NULL or m x 3 n_operands (operand o, axis a at
+ * column 3 o + a), packed column-major; out_v: m; out_g (with G): m x 3.  scale, offset: n_operands each. */
+int bbfmm_debug_field_program(int32_t where, int32_t n_operands, const double *scale, const double *offset, const int32_t *program,
+                              int32_t n_program, const double *V, const double *G, int64_t m, double *out_v, double *out_g);
+
 /* BBFMM_FINISH_CLIPPED of a caller's own mesh (host arrays: n_vertices x 3 doubles, n_facets x 3 int64 ids) on the
  * current device, or the handle's when h is not NULL: *out holds one mesh.  Messages as for
  * bbfmm_isosurfaces_from_values. */
