@@ -11,11 +11,11 @@ from .fmm_tree import (FmmError, FmmKernelType, FmmParams, FmmTree, KernelDoesNo
 from . import solvers  # noqa: E402  (FGMRES / Schwarz drivers, iterative_solvers.rs)
 from . import rbf  # noqa: E402  (RBFInterpolator: fit, evaluate and mesh in one object, rbf.rs)
 from . import rmt  # noqa: E402  (isosurfaces of any field: composite interpolants and callables, py_ferreus_rmt)
-from .isosurface import (clip_mesh, isosurface_from_values, isosurfaces_from_values,  # noqa: E402
+from .isosurface import (clip_mesh, close_mesh, isosurface_from_values, isosurfaces_from_values,  # noqa: E402
                          mesh_self_intersections, triangle_pair)
 
 __all__ = ["solvers", "rbf", "rmt", "FmmTree", "FmmParams", "KernelParams", "KernelType", "FmmKernelType",
            "SpheroidalOrder", "M2LCompressionType", "FmmError", "PointOutsideTree",
            "KernelDoesNotSupportGradients", "mfma_f64_selftest", "fp64_valu_selftest", "debug_kernel_values", "debug_math",
-           "isosurface_from_values", "isosurfaces_from_values", "clip_mesh", "mesh_self_intersections",
+           "isosurface_from_values", "isosurfaces_from_values", "clip_mesh", "close_mesh", "mesh_self_intersections",
            "triangle_pair"]

@@ -83,6 +83,11 @@ SIGNATURES = {
     "bbfmm_debug_field_program": (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "bbfmm_isosurface_finish_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_isosurface_close_mesh": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, ctypes.c_double, c_i32, c_p]),
+    "bbfmm_isosurface_closure_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
+    "bbfmm_debug_closure_triangulate": (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, ctypes.c_double,
+                                                       ctypes.c_double, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64]),
+    "bbfmm_debug_orient2d": (ctypes.c_int, [c_p, c_i64, c_p]),
     "bbfmm_isosurface_follow_stats": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_isosurface_follow_times": (ctypes.c_int, [c_p, c_i32, c_p]),
     "bbfmm_isosurface_follow_bricks": (ctypes.c_int, [c_p, c_i32, c_p, c_p]),

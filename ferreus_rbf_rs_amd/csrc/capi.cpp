@@ -16,7 +16,9 @@
 #include "fmm_tree.hpp"
 #include "interpolant_terms.hpp"
 #include "field_program.hpp"
+#include "closure_triangulate.hpp"
 #include "isosurface.hpp"
+#include "isosurface_closure.hpp"
 #include "isosurface_curvature.hpp"
 #include "isosurface_intersect.hpp"
 #include "morton.hpp"
@@ -460,7 +462,7 @@ static bool iso_methods_ok(int32_t cluster, int32_t finish, int32_t self_interse
         *err = "isosurface: unknown cluster method " + std::to_string(cluster);
         return false;
     }
-    if (finish != BBFMM_FINISH_RAW && finish != BBFMM_FINISH_CLIPPED) {
+    if (finish < BBFMM_FINISH_RAW || finish > BBFMM_FINISH_CLOSE_NEGATIVE) {
         *err = "isosurface: unknown finish " + std::to_string(finish);
         return false;
     }
@@ -696,7 +698,7 @@ static int build_isosurfaces_impl(bbfmm_handle *h, const double *extents, double
 
 // A host mesh (mesh_op: clip and clean, or the self-intersection detector) or a host field through extract(), on the
 // handle's stream or one of the call's own.
-enum IsoMeshOp : int { kIsoField = 0, kIsoFinishMesh = 1, kIsoDetectMesh = 2 };
+enum IsoMeshOp : int { kIsoField = 0, kIsoFinishMesh = 1, kIsoDetectMesh = 2, kIsoCloseMesh = 3 };
 static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const double *extents, double resolution,
                                  const double *isovalues, int32_t n_isovalues, int64_t batch_bytes, int32_t cluster_method,
                                  int32_t finish, int32_t self_intersections, const double *vertices, int64_t n_vertices,
@@ -781,6 +783,9 @@ static int isosurfaces_from_host(bbfmm_handle *h, const double *values, const do
                     for (int64_t t = 0; rc == BBFMM_OK && t < n_facets; ++t)
                         if (flag[t]) m.isect_ids.push_back(t);
                 }
+            } else if (mesh_op == kIsoCloseMesh) { // the closure alone (finish: the mode)
+                rc = bbfmm::iso::closure_device(d_v, n_vertices, d_f, n_facets, box, resolution, finish, st, &r->meshes[0], &err);
+                if (rc == BBFMM_OK && n_facets == 0 && n_vertices > 0) r->meshes[0].vertices.assign(vertices, vertices + 3 * n_vertices);
             } else {
                 rc = bbfmm::iso::finish_device(d_v, n_vertices, d_f, n_facets, box, st, &r->meshes[0], &err);
             }
@@ -1368,6 +1373,63 @@ int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_
                                  int64_t n_facets, const double *extents, bbfmm_isosurface_result **out) {
     return isosurfaces_from_host(h, nullptr, extents, 0.0, nullptr, 0, 0, BBFMM_CLUSTER_NONE, BBFMM_FINISH_CLIPPED,
                                  BBFMM_SELF_INTERSECTIONS_IGNORE, vertices, n_vertices, facets, n_facets, kIsoFinishMesh, out);
+}
+
+int bbfmm_isosurface_close_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                int64_t n_facets, const double *extents, double resolution, int32_t mode,
+                                bbfmm_isosurface_result **out) {
+    return isosurfaces_from_host(h, nullptr, extents, resolution, nullptr, 0, 0, BBFMM_CLUSTER_NONE, mode,
+                                 BBFMM_SELF_INTERSECTIONS_IGNORE, vertices, n_vertices, facets, n_facets, kIsoCloseMesh, out);
+}
+
+int bbfmm_isosurface_closure_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out) {
+    if (!r || !stats_out || i < 0 || i >= static_cast<int32_t>(r->meshes.size())) return BBFMM_BAD_ARGUMENT;
+    static_assert(sizeof(r->meshes[i].closure_stats) == BBFMM_CLOSURE_STATS * sizeof(int64_t), "closure stats");
+    std::memcpy(stats_out, r->meshes[i].closure_stats, sizeof(r->meshes[i].closure_stats));
+    return BBFMM_OK;
+}
+
+int bbfmm_debug_orient2d(const double *abc, int64_t n, int32_t *sign_out) {
+    if (n < 0 || (n > 0 && (!abc || !sign_out))) return BBFMM_BAD_ARGUMENT;
+    for (int64_t i = 0; i < n; ++i) sign_out[i] = bbfmm::iso::closure::orient2d_sign(abc + 6 * i, abc + 6 * i + 2, abc + 6 * i + 4);
+    return BBFMM_OK;
+}
+
+int bbfmm_debug_closure_triangulate(int32_t nu, int32_t nv, const double *gu, const double *gv, const double *points,
+                                    int64_t n_points, const int64_t *edges, int64_t n_edges, const int32_t *cut,
+                                    int64_t n_cut, double tol, double key_cell, int64_t cap_points, double *pts_out,
+                                    int64_t *ids_out, int64_t cap_tris, int64_t *tris_out, int64_t *counts_out,
+                                    char *err_out, int64_t err_cap) {
+    auto fail = [&](const std::string &msg) {
+        if (err_out && err_cap > 0) {
+            const size_t n = std::min(msg.size(), static_cast<size_t>(err_cap - 1));
+            std::memcpy(err_out, msg.data(), n);
+            err_out[n] = 0;
+        }
+        return BBFMM_BAD_ARGUMENT;
+    };
+    try {
+        if (nu < 1 || nv < 1 || !gu || !gv || n_points < 0 || n_edges < 0 || n_cut < 0 || (n_points > 0 && !points) ||
+            (n_edges > 0 && !edges) || (n_cut > 0 && !cut) || !counts_out || cap_points < 0 || cap_tris < 0 || !(key_cell > 0.0) ||
+            n_points > 2000000000 || n_cut > 400000000)
+            return fail("closure: bad arguments");
+        bbfmm::iso::closure::Band B;
+        B.nu = nu, B.nv = nv, B.gu = gu, B.gv = gv, B.points = points, B.n_points = n_points, B.edges = edges, B.n_edges = n_edges;
+        B.cut = cut, B.n_cut = n_cut, B.tol = tol, B.key_cell = key_cell;
+        std::string err;
+        if (!bbfmm::iso::closure::triangulate_band(&B, &err)) return fail(err);
+        const int64_t np = static_cast<int64_t>(B.id.size()), nt = static_cast<int64_t>(B.tri.size() / 3);
+        if (np > cap_points || nt > cap_tris || (np > 0 && (!pts_out || !ids_out)) || (nt > 0 && !tris_out))
+            return fail("closure: " + std::to_string(np) + " band points and " + std::to_string(nt) + " triangles do not fit the capacities given");
+        if (np) std::memcpy(pts_out, B.xy.data(), B.xy.size() * sizeof(double));
+        if (np) std::memcpy(ids_out, B.id.data(), B.id.size() * sizeof(int64_t));
+        if (nt) std::memcpy(tris_out, B.tri.data(), B.tri.size() * sizeof(int64_t));
+        for (int q = 0; q < 8; ++q) counts_out[q] = 0;
+        counts_out[0] = np, counts_out[1] = nt, counts_out[2] = B.dropped, counts_out[3] = B.constraint_flips, counts_out[4] = B.lawson_flips;
+        return BBFMM_OK;
+    } catch (const std::exception &e) {
+        return fail(std::string("exception: ") + e.what());
+    }
 }
 
 int bbfmm_isosurface_self_intersections(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,

@@ -699,7 +699,8 @@ constexpr int kStatCurv = 18, kStatCount = kStatCurv + kCurvStats;
 // The clustered mesh of one isovalue of the resident field (DESIGN.md "Isosurfaces on the RMT lattice", clustering).
 // inside: the extents of the self-intersection rollback, nullptr without it.
 int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const ClusterState &c, double iso, const ClipBox *clip,
-                    const ClipBox *inside, Pool &pool, hipStream_t st, Mesh *mesh, std::string *err) {
+                    const ClipBox *inside, Pool &pool, hipStream_t st, Mesh *mesh, std::string *err, int finish = kFinishClipped,
+                    double resolution = 0.0) {
     const int g = grid_for(s.nodes);
     const size_t nodes = static_cast<size_t>(s.nodes);
     ISO_HIP(hipMemsetAsync(c.d_stats, 0, kStatCount * sizeof(unsigned long long), st));
@@ -862,7 +863,7 @@ int cluster_extract(const Slab &s, int64_t nk, const TetTables &tt, const Cluste
         pool.put(weights);
         pool.put(vinfo);
         pool.put(vflag);
-        rc = finish_device(verts, nv, facets, nf, *clip, st, mesh, err);
+        rc = finish_device(verts, nv, facets, nf, *clip, st, mesh, err, finish, resolution);
         pool.put(verts);
         pool.put(facets);
         return rc;
@@ -1025,7 +1026,8 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
         return BBFMM_BAD_ARGUMENT;
     }
-    const bool clipped = req.finish == kFinishClipped;
+    const bool clipped = req.finish == kFinishClipped || req.finish == kFinishClosePositive || req.finish == kFinishCloseNegative;
+    const double resolution = lat.spacing[0] * 2.0; // (make_lattice halves it: exact both ways)
     if (req.finish != kFinishRaw && !clipped) {
         *err = "isosurface: unknown finish " + std::to_string(req.finish);
         return BBFMM_BAD_ARGUMENT;
@@ -1241,14 +1243,15 @@ int extract(const Lattice &lat, const FieldFn &field, const Request &req, hipStr
         const Slab box = slab_for(0, nk);
         for (int q = 0; q < n_iso; ++q) {
             const int rc = cluster_extract(box, nk, tt, cs, req.isovalues[q], clipped ? &clip_box : nullptr, rollback ? &clip_box : nullptr,
-                                           pool, st, &(*meshes)[q], err);
+                                           pool, st, &(*meshes)[q], err, req.finish, resolution);
             if (rc != BBFMM_OK) return rc;
         }
         return BBFMM_OK;
     }
     if (clipped) { // clipped and cleaned while still on the device
         for (int q = 0; q < n_iso; ++q) {
-            const int rc = finish_device(states[q].v.p, states[q].vtotal, states[q].fc.p, states[q].ftotal, clip_box, st, &(*meshes)[q], err);
+            const int rc = finish_device(states[q].v.p, states[q].vtotal, states[q].fc.p, states[q].ftotal, clip_box, st, &(*meshes)[q], err, req.finish,
+                                          resolution);
             if (rc != BBFMM_OK) return rc;
         }
         return BBFMM_OK;

@@ -3,7 +3,8 @@
 // ClusterMethod::Average or ClusterMethod::CurvatureWeighted (the intersections near a sample point merged where the topology tests allow it, with the
 // predicted-edge and non-manifold rollbacks and, where asked for, the self-intersection rollback), taken from every sample
 // point of the extraction domain in device passes instead of a CPU wavefront; with kFinishClipped followed by its clip_mesh_to_aabb and clean_mesh on the device (the
-// finished mesh of BoundaryClosure::None; boundary closure is not run).  With kFollowSurface the field is evaluated only in the
+// finished mesh of BoundaryClosure::None) and with kFinishClosePositive / kFinishCloseNegative then closed on the six faces
+// of the extents (isosurface_closure.hpp).  With kFollowSurface the field is evaluated only in the
 // bricks of lattice nodes that a wavefront reaches from projected seed points (isosurface_follow.hip), as the reference
 // follows the surface, and the same passes run on that field.  Contract: DESIGN.md "Isosurfaces on the RMT
 // lattice"; numpy restatements: tests/isosurface_restatement.py, tests/isosurface_cluster_restatement.py,
@@ -301,6 +302,8 @@ struct Mesh {
     int32_t follow_dims[4] = {0, 0, 0, 0};                               // B and the bricks per axis (x, y, z)
     std::vector<uint8_t> follow_bricks;                                  // 1 per brick visited for this isovalue, x fastest
     std::vector<int64_t> isect_ids;                                      // the detector on a caller's mesh: the triangles found
+    int64_t closure_stats[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // ClosureStat (isosurface_closure.hpp), all 0 without a closure
 };
 
 // Mesh::stats: [0, 6) sample points per TopologyCase; mesh edges with more than 2 faces before pass A and the clusters
@@ -309,7 +312,7 @@ struct Mesh {
 constexpr int kStatOverA = 6, kStatSplitA = 7, kStatRolledB = 8, kStatOverB = 12, kRoundsB = 4;
 
 enum ClusterMethod : int { kClusterNone = 0, kClusterAverage = 1, kClusterCurvature = 2 };
-enum Finish : int { kFinishRaw = 0, kFinishClipped = 1 };
+enum Finish : int { kFinishRaw = 0, kFinishClipped = 1, kFinishClosePositive = 2, kFinishCloseNegative = 3 };
 enum SelfIntersections : int { kSelfIntersectionsIgnore = 0, kSelfIntersectionsRollback = 1 };
 
 // ---- self-intersections (ferreus_rmt/src/mesh_intersections.rs; DESIGN.md "Self-intersection rollback")
@@ -374,9 +377,11 @@ constexpr int64_t kFinishMaxFacets = int64_t(1) << 26, kFinishMaxVertices = (int
 bool finish_fits(int64_t n_vertices, int64_t n_facets, std::string *err);
 
 // clean_mesh(clip_mesh_to_aabb(mesh)) of a mesh on the device (facet ids in [0, n_vertices)), on `stream`; the finished
-// mesh and its finish_stats go to *mesh on the host.  Returns a bbfmm_status.
+// mesh and its finish_stats go to *mesh on the host.  close_mode kFinishClosePositive / kFinishCloseNegative: the finished
+// mesh stays on the device and goes through closure_device (isosurface_closure.hpp) with close_resolution before that one
+// download.  Returns a bbfmm_status.
 int finish_device(const double *d_vertices, int64_t n_vertices, const int64_t *d_facets, int64_t n_facets, const ClipBox &box,
-                  hipStream_t stream, Mesh *mesh, std::string *err);
+                  hipStream_t stream, Mesh *mesh, std::string *err, int close_mode = kFinishClipped, double close_resolution = 0.0);
 
 // The true self-intersections of a mesh on the device (get_intersecting_triangles, mesh_intersections.rs:163-208, with a
 // uniform grid in place of the R-tree): d_tri_flag[t] (n_facets bytes, zeroed here) becomes 1 for every facet on a true

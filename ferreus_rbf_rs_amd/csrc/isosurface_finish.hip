@@ -3,6 +3,7 @@
 // grid-stride; placement by rocPRIM exclusive scans and stable radix sorts.  The integer atomics (minimum over indices,
 // use counts, stats) are order-independent, so the mesh does not depend on thread order.
 #include "isosurface.hpp"
+#include "isosurface_closure.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -425,7 +426,7 @@ bool finish_fits(int64_t n_vertices, int64_t n_facets, std::string *err) {
 }
 
 int finish_device(const double *d_vertices, int64_t nv, const int64_t *d_facets, int64_t nf, const ClipBox &box, hipStream_t st,
-                  Mesh *mesh, std::string *err) {
+                  Mesh *mesh, std::string *err, int close_mode, double close_resolution) {
 #define FIN_HIP(x)                                                                               \
     do {                                                                                         \
         hipError_t e_ = (x);                                                                     \
@@ -633,6 +634,12 @@ int finish_device(const double *d_vertices, int64_t nv, const int64_t *d_facets,
     FIN_HIP(hipGetLastError());
     out_facets_kernel<<<gf, kThreads, 0, st>>>(nef, kept, fidx, ef, wid, first_use, pidx, of);
     FIN_HIP(hipGetLastError());
+    if (close_mode == kFinishClosePositive || close_mode == kFinishCloseNegative) { // closed while still on the device
+        if ((rc = download_stats()) != BBFMM_OK) return rc;
+        for (int32_t *p : {keep, use, first_use, kept, fidx, pos, pidx, wid, ef}) pool.put(p);
+        pool.put(wv);
+        return closure_device(ov, nv_out, of, nf_out, box, close_resolution, close_mode, st, mesh, err);
+    }
     mesh->vertices.resize(3 * static_cast<size_t>(nv_out));
     mesh->facets.resize(3 * static_cast<size_t>(nf_out));
     if (nv_out) FIN_HIP(hipMemcpyAsync(mesh->vertices.data(), ov, mesh->vertices.size() * sizeof(double), hipMemcpyDeviceToHost, st));

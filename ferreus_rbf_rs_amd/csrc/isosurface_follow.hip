@@ -343,7 +343,7 @@ int extract_follow(const Lattice &lat, const FieldFn &field, const Request &req,
         *err = "isosurface: unknown cluster method " + std::to_string(req.cluster);
         return BBFMM_BAD_ARGUMENT;
     }
-    if (req.finish != kFinishRaw && req.finish != kFinishClipped) {
+    if (req.finish < kFinishRaw || req.finish > kFinishCloseNegative) {
         *err = "isosurface: unknown finish " + std::to_string(req.finish);
         return BBFMM_BAD_ARGUMENT;
     }

@@ -284,7 +284,8 @@ class FmmTree:
         (isosurface.rs:489-) over every sample point of the extraction domain.  finish: "raw" (the default) is that mesh
         before clipping and cleaning, two lattice cells past the extents on every side; "clipped" runs the reference's
         clip_mesh_to_aabb and clean_mesh on the device before the download (isosurface.rs:1009-1021), its finished mesh
-        for BoundaryClosure::None; boundary closure is not implemented.  cluster: "none" (the default) is ClusterMethod::None, one vertex per crossed lattice edge; "average"
+        for BoundaryClosure::None; "close_positive" / "close_negative" then close that mesh on the six faces of the
+        extents (BoundaryClosure::ClosePositive / CloseNegative; see isosurface.py; stats under "closure").  cluster: "none" (the default) is ClusterMethod::None, one vertex per crossed lattice edge; "average"
         is ClusterMethod::Average, the intersections near a sample point merged into their mean where the topology
         tests allow it, with the predicted-edge and non-manifold rollbacks (isosurface.rs:715-930); its
         self-intersection rollback (isosurface.rs:932-1007) runs with self_intersections="rollback" ("ignore", the

@@ -4,8 +4,10 @@ The mesh is ferreus_rmt's marching-tetrahedra output (`build_isosurface`, ferreu
 over every sample point of the extraction domain instead of the sample points a seeded wavefront reaches (DESIGN.md
 "Isosurfaces on the RMT lattice").  `finish="raw"` (the default) is that mesh as it is, before `clip_mesh_to_aabb` and
 `clean_mesh`: it reaches two lattice cells past the extents.  `finish="clipped"` runs both on the device before the
-download (isosurface.rs:1009-1021): the reference's finished mesh for `BoundaryClosure::None`.  Boundary closure
-(`ClosePositive` / `CloseNegative`) and vertex gradients are not implemented.  `cluster="none"` (the
+download (isosurface.rs:1009-1021): the reference's finished mesh for `BoundaryClosure::None`;
+`finish="close_positive"` / `"close_negative"` then close that mesh on the six faces of the extents (its
+`BoundaryClosure::ClosePositive` / `CloseNegative`, boundary_closure.rs; see below).  Vertex gradients are not
+implemented.  `cluster="none"` (the
 default) is its `ClusterMethod::None`, one vertex per crossed lattice edge; `cluster="average"` its
 `ClusterMethod::Average`: the intersections near a sample point are merged into their mean where the topology tests
 allow it (topology.rs:232-314), and clusters that give a mesh edge more than 2 faces are split again
@@ -41,7 +43,15 @@ facets, every cluster placed at the mean of its intersections weighted by the cu
 * finish="clipped" (aabb_clipping.rs:55-105, mesh_cleanup.rs:32-96), with eps = 1e-10 * max(|hi - lo|, 1): every facet
   clipped against the six planes of the extents in turn and fanned; vertices within eps welded, the lowest-index
   vertex of a group its representative; collapsed, zero-area (|ab x ac|^2 <= eps^4), repeated and lone facets dropped;
-  vertices renumbered in order of first use.  `return_stats=True` then also holds the counts of `FINISH_STATS`.
+  vertices renumbered in order of first use.  `return_stats=True` then also holds the counts of `FINISH_STATS`;
+* finish="close_positive" / "close_negative" (DESIGN.md "Boundary closure"): the clipped mesh first (reversed for
+  "close_negative"), then per face of the extents (XMin, XMax, YMin, YMax, ZMin, ZMax) the cap facets, wound outward: the
+  kept whole cells of a grid of `resolution` (two triangles each, made on the device) and the triangles of the band of
+  cut cells along the open edges (triangulated on the host with exact orientation tests).  "close_positive" keeps the
+  part of the faces where the field outside the extents counts as above the isovalue, "close_negative" the rest.  New
+  vertices follow the mesh's in order of first use.  A mesh without open edges is returned as it is; an open edge off
+  the faces is refused.  `return_stats=True` then holds the counts of `CLOSURE_STATS` under "closure".  `close_mesh`
+  runs the closure alone on a caller's clipped mesh.
 
 `follow="dense"` (the default) evaluates the field at every node of E.  `follow="surface"` follows the surface from seed
 points as the reference does (seed_projection.rs:29-130, isosurface.rs:551-697; DESIGN.md "Following the surface"): the
@@ -152,6 +162,13 @@ STATS = ("closed", "multi_hole", "flat_hole", "multi_surface", "simple", "incomp
 
 
 FINISH = {"raw": 0, "clipped": 1}
+# the boundary closure behind the clip and clean: further values of `finish`, and the modes of close_mesh
+FINISH_CLOSE = {"close_positive": 2, "close_negative": 3}
+# return_stats with finish="close_positive" / "close_negative", and close_mesh (bbfmm_isosurface_closure_stats); the
+# per-face entries are lists of 6 (XMin, XMax, YMin, YMax, ZMin, ZMax)
+CLOSURE_STATS = ("open_edges", "open_edges_off_box", "cut_cells", "whole_cells_kept", "regions", "band_points",
+                 "band_triangles", "dropped", "constraint_flips", "lawson_flips", "vertices_added", "conflicts",
+                 "band_host_us")
 # return_stats with finish="clipped" (bbfmm_isosurface_finish_stats)
 FINISH_STATS = ("facets_in", "straddling", "outside", "vertices_emitted", "welded", "weld_loose", "collapsed", "tiny",
                 "duplicate", "lone")
@@ -172,8 +189,10 @@ def _self_intersections(mode):
 
 
 def _finish(finish):
+    if finish in FINISH_CLOSE:
+        return FINISH_CLOSE[finish]
     if finish not in FINISH:
-        raise ValueError(f"finish must be one of {sorted(FINISH)}, got {finish!r}")
+        raise ValueError(f"finish must be one of {sorted(FINISH) + sorted(FINISH_CLOSE)}, got {finish!r}")
     return FINISH[finish]
 
 
@@ -295,6 +314,15 @@ def _finish_stats(lib, res, i):
     return {name: int(s[q]) for q, name in enumerate(FINISH_STATS)}
 
 
+def _closure_stats(lib, res, i):
+    s = np.zeros(32, dtype=np.int64)
+    lib.bbfmm_isosurface_closure_stats(res, i, s.ctypes.data)
+    out = dict(open_edges=s[0:6].tolist(), open_edges_off_box=int(s[6]), cut_cells=s[7:13].tolist(),
+               whole_cells_kept=s[13:19].tolist())
+    out.update({name: int(s[19 + q]) for q, name in enumerate(CLOSURE_STATS[4:])})
+    return out
+
+
 def _follow_stats(lib, res, i):
     s, ms = np.zeros(len(FOLLOW_STATS), dtype=np.int64), np.zeros(3)
     lib.bbfmm_isosurface_follow_stats(res, i, s.ctypes.data)
@@ -334,6 +362,8 @@ def _meshes(lib, res, stats=False, finish=0, self_intersections=0, follow=0, met
             st = _stats(lib, res, i)
             if finish:
                 st["finish"] = _finish_stats(lib, res, i)
+            if finish >= FINISH_CLOSE["close_positive"]:
+                st["closure"] = _closure_stats(lib, res, i)
             if self_intersections:
                 st["self_intersections"] = _intersection_stats(lib, res, i)
             if follow:
@@ -407,7 +437,8 @@ def isosurfaces_from_values(lattice_values, extents, resolution, isovalues, *, b
                             cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
                             seeds=None):
     """Meshes of a caller's lattice field (shape lattice_info(extents, resolution)["shape"]) at each isovalue, on the
-    current device (or the tree's).  cluster: "none", "average" or "curvature", finish: "raw" or "clipped", self_intersections:
+    current device (or the tree's).  cluster: "none", "average" or "curvature", finish: "raw", "clipped", "close_positive" or
+    "close_negative" (then under "closure" the counts of CLOSURE_STATS), self_intersections:
     "ignore" or "rollback" (see the module); return_stats: (vertices, facets, stats) per mesh, stats the clustering
     counts (all 0 with "none"), with cluster="curvature" under "curvature" the counts of CURVATURE_STATS, with
     finish="clipped" under "finish" the counts of FINISH_STATS and with
@@ -471,6 +502,68 @@ def clip_mesh(vertices, facets, extents, return_stats=False, *, tree=None):
     finally:
         if res:
             lib.bbfmm_isosurface_destroy(res)
+
+
+def close_mesh(vertices, facets, extents, resolution, mode, return_stats=False, *, tree=None):
+    """The boundary closure alone of a caller's own clipped and cleaned mesh (clip_mesh gives one) on the current device
+    (or the tree's): (vertices, facets) closed on the faces of the extents with a cap grid of `resolution`; mode:
+    "close_positive" or "close_negative" (see the module); and the counts of CLOSURE_STATS when return_stats.  A mesh
+    without facets or without open edges is returned as it is; one with an open edge off the faces is refused."""
+    lib = L.load()
+    if mode not in FINISH_CLOSE:
+        raise ValueError(f"mode must be one of {sorted(FINISH_CLOSE)}, got {mode!r}")
+    ext = _ext(extents)
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(facets, dtype=np.int64).reshape(-1, 3))
+    res = ctypes.c_void_p()
+    h = tree._h if tree is not None else None
+    rc = lib.bbfmm_isosurface_close_mesh(h, v.ctypes.data, len(v), f.ctypes.data, len(f), ext.ctypes.data,
+                                         float(resolution), FINISH_CLOSE[mode], ctypes.byref(res))
+    try:
+        if rc != L.OK:
+            _raise(rc, lib.bbfmm_isosurface_error(res).decode() if res else "isosurface closure failed")
+        vo, fo = _meshes(lib, res)[0]
+        return (vo, fo, _closure_stats(lib, res, 0)) if return_stats else (vo, fo)
+    finally:
+        if res:
+            lib.bbfmm_isosurface_destroy(res)
+
+
+def orient2d(a, b, c):
+    """The exact signs (-1, 0, 1; 1: counter-clockwise) of the orientation determinants of the triples a, b, c ((n, 2)
+    each) by the predicate the closure's triangulator runs (host only)."""
+    lib = L.load()
+    abc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 2) for x in (a, b, c)], axis=1))
+    out = np.zeros(len(abc), dtype=np.int32)
+    rc = lib.bbfmm_debug_orient2d(abc.ctypes.data, len(abc), out.ctypes.data)
+    if rc != L.OK:
+        raise ValueError("orient2d: bad arguments")
+    return out
+
+
+def triangulate_band(gu, gv, points, edges, cut, resolution, eps):
+    """The closure's band triangulator on one face (host only): gu, gv the grid coordinates, points (n, 2) the mesh
+    vertices on the face, edges (m, 2) the open edges as point indices, cut the ascending ids v * nu + u of the cut
+    cells.  Returns (band points (p, 2), ids (p,): the index of a mesh point or -1 - (v index * (nu + 1) + u index) of a
+    grid point, triangles (t, 3) counter-clockwise, counts); raises FmmError where the constraints cannot be met."""
+    lib = L.load()
+    gu, gv = (np.ascontiguousarray(np.asarray(g, dtype=np.float64).reshape(-1)) for g in (gu, gv))
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 2))
+    ed = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 2))
+    ct = np.ascontiguousarray(np.asarray(cut, dtype=np.int32).reshape(-1))
+    cap_p = len(pts) + 4 * len(ct) + 4
+    cap_t = 2 * cap_p + 4
+    po, ido, to = np.zeros((cap_p, 2)), np.zeros(cap_p, np.int64), np.zeros((cap_t, 3), np.int64)
+    counts, err = np.zeros(8, np.int64), ctypes.create_string_buffer(512)
+    rc = lib.bbfmm_debug_closure_triangulate(len(gu) - 1, len(gv) - 1, gu.ctypes.data, gv.ctypes.data, pts.ctypes.data, len(pts),
+                                             ed.ctypes.data, len(ed), ct.ctypes.data, len(ct), 1e-9 * float(resolution),
+                                             max(float(eps), 1e-12), cap_p, po.ctypes.data, ido.ctypes.data, cap_t,
+                                             to.ctypes.data, counts.ctypes.data, err, len(err))
+    if rc != L.OK:
+        _raise(rc, err.value.decode())
+    n, t = int(counts[0]), int(counts[1])
+    return po[:n].copy(), ido[:n].copy(), to[:t].copy(), dict(points=n, triangles=t, dropped=int(counts[2]),
+                                                               constraint_flips=int(counts[3]), lawson_flips=int(counts[4]))
 
 
 def clip_triangle(triangle, extents):

@@ -709,10 +709,12 @@ class RBFInterpolator:
                           cluster="curvature", follow="surface", seeds=None, finish="clipped", self_intersections="rollback",
                           return_stats=False, return_field=False, batch_bytes: int = 0):
         """build_isosurfaces (rbf.rs:980-1069) on the device extractor; the keywords override its options
-        (FmmTree.build_isosurfaces).  The first value column is meshed."""
+        (FmmTree.build_isosurfaces); finish="close_positive" / "close_negative" close the mesh on the faces of the extents.
+        The first value column is meshed."""
         closure = BoundaryClosure.None_ if boundary_closure is None else BoundaryClosure(boundary_closure)
         if closure is not BoundaryClosure.None_:
-            raise NotImplementedError(f"BoundaryClosure.{closure.name} is not implemented (only BoundaryClosure.None_)")
+            raise NotImplementedError(f"boundary_closure=BoundaryClosure.{closure.name} is not mapped onto the closure yet: pass "
+                                      f"finish={'close_positive' if closure is BoundaryClosure.ClosePositive else 'close_negative'!r} instead")
         if self.dimensions != 3:
             raise ValueError("Only supported for 3D isosurfacing")
         ext = np.asarray(extents, dtype=np.float64).reshape(-1)

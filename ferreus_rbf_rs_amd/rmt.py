@@ -361,11 +361,13 @@ def build_isosurfaces(seed_points, extents, resolution: float, isovalues, isosur
                       batch_bytes: int = 0):
     """One rbf.Mesh per isovalue of `isosurface_fn`, a FieldExpr or a callable (see the module), followed from
     `seed_points` ((n, 3) world points).  The keywords past progress_callback are those of
-    RBFInterpolator.build_isosurfaces with its defaults; return_field needs a FieldExpr.  `gradient_fn` is used by the seed
+    RBFInterpolator.build_isosurfaces with its defaults (finish="close_positive" / "close_negative": the mesh closed on the
+    faces of the extents); return_field needs a FieldExpr.  `gradient_fn` is used by the seed
     projection of a callable and ignored for a FieldExpr, which has its own gradient."""
     closure = BoundaryClosure.None_ if boundary_closure is None else BoundaryClosure(boundary_closure)
     if closure is not BoundaryClosure.None_:
-        raise NotImplementedError(f"BoundaryClosure.{closure.name} is not implemented (only BoundaryClosure.None_; see rmt.box)")
+        raise NotImplementedError(f"boundary_closure=BoundaryClosure.{closure.name} is not mapped onto the closure yet: pass "
+                                  f"finish={'close_positive' if closure is BoundaryClosure.ClosePositive else 'close_negative'!r} instead")
     method = ClusterMethod.CurvatureWeighted if cluster_method is None else ClusterMethod(cluster_method)
     lib = L.load()
     cm, fin, isect = _iso._cluster(_CLUSTER[method]), _iso._finish(finish), _iso._self_intersections(self_intersections)

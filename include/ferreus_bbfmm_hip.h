@@ -295,9 +295,16 @@ int bbfmm_isosurface_curvature_stats(const bbfmm_isosurface_result *r, int32_t i
  * eps = 1e-10 * max(|hi - lo|, 1): every facet clipped against the six planes of the extents and fanned, then vertices
  * within eps welded (the representative of a group is its lowest-index vertex), collapsed, zero-area, repeated and
  * lone facets dropped, and vertices renumbered in order of first use.  A mesh of more than 2^26 facets is refused
- * before any work (ids are packed in 32 bits). */
+ * before any work (ids are packed in 32 bits).  BBFMM_FINISH_CLOSE_POSITIVE / BBFMM_FINISH_CLOSE_NEGATIVE: the clipped
+ * mesh closed on the six faces of the extents (the reference's BoundaryClosure::ClosePositive / CloseNegative,
+ * boundary_closure.rs; contract: DESIGN.md "Boundary closure"): its facets first (reversed for NEGATIVE), then per face
+ * the cap facets wound outward, on a grid of the call's resolution; the new vertices follow the mesh's in order of first
+ * use.  POSITIVE keeps the part of the faces where the field outside the extents counts as above the isovalue, NEGATIVE
+ * the rest.  A mesh without open edges is returned as it is; one with an open edge off the faces is refused. */
 #define BBFMM_FINISH_RAW 0
 #define BBFMM_FINISH_CLIPPED 1
+#define BBFMM_FINISH_CLOSE_POSITIVE 2
+#define BBFMM_FINISH_CLOSE_NEGATIVE 3
 /* Self-intersections.  BBFMM_SELF_INTERSECTIONS_IGNORE: the clustered mesh as the two passes above leave it (averaging can
  * pull two sheets of a complex surface through each other).  BBFMM_SELF_INTERSECTIONS_ROLLBACK, with
  * BBFMM_CLUSTER_AVERAGE or BBFMM_CLUSTER_CURVATURE (nothing is done with BBFMM_CLUSTER_NONE: the mesh and the counts are those without it): after
@@ -448,6 +455,45 @@ int bbfmm_isosurface_finish_mesh(bbfmm_handle *h, const double *vertices, int64_
  * another, [5] vertices further than eps from their representative (weld_loose; 0 where the weld is the reference's
  * greedy one); facets dropped as [6] collapsed, [7] zero-area, [8] repeated, [9] lone. */
 int bbfmm_isosurface_finish_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* The boundary closure alone of a caller's own clipped and cleaned mesh (host arrays as for
+ * bbfmm_isosurface_finish_mesh) on the current device, or the handle's when h is not NULL: *out holds one mesh.  mode:
+ * BBFMM_FINISH_CLOSE_POSITIVE or BBFMM_FINISH_CLOSE_NEGATIVE; resolution: the spacing of the cap grid. */
+int bbfmm_isosurface_close_mesh(bbfmm_handle *h, const double *vertices, int64_t n_vertices, const int64_t *facets,
+                                int64_t n_facets, const double *extents, double resolution, int32_t mode,
+                                bbfmm_isosurface_result **out);
+/* The closure counts of mesh i, stats_out[BBFMM_CLOSURE_STATS] (all 0 where no closure ran).  Faces in the order XMin,
+ * XMax, YMin, YMax, ZMin, ZMax. */
+#define BBFMM_CLOSURE_OPEN_EDGES 0      /* [0, 6) open edges per face (one on a box edge counts on both faces) */
+#define BBFMM_CLOSURE_OPEN_OFF_BOX 6    /* open edges with an end on no common face (the call is then refused) */
+#define BBFMM_CLOSURE_CUT_CELLS 7       /* [7, 13) cut cells per face */
+#define BBFMM_CLOSURE_WHOLE_KEPT 13     /* [13, 19) whole cells kept per face */
+#define BBFMM_CLOSURE_REGIONS 19        /* connected components of whole cells */
+#define BBFMM_CLOSURE_BAND_POINTS 20    /* points the host triangulated, summed over the faces */
+#define BBFMM_CLOSURE_BAND_KEPT 21      /* band triangles in the output */
+#define BBFMM_CLOSURE_BAND_DROPPED 22   /* band triangles of non-positive area (0 for a valid triangulation) */
+#define BBFMM_CLOSURE_CONSTRAINT_FLIPS 23
+#define BBFMM_CLOSURE_LAWSON_FLIPS 24
+#define BBFMM_CLOSURE_VERTICES_ADDED 25
+#define BBFMM_CLOSURE_CONFLICTS 26      /* seeded components that also border the unseeded side of an open edge */
+#define BBFMM_CLOSURE_BAND_HOST_US 27   /* host time of the band triangulation and the selection, microseconds */
+#define BBFMM_CLOSURE_STATS 32
+int bbfmm_isosurface_closure_stats(const bbfmm_isosurface_result *r, int32_t i, int64_t *stats_out);
+/* Host only: the band triangulator of the closure on one face (csrc/closure_triangulate.hpp).  gu, gv: the nu + 1 and
+ * nv + 1 grid coordinates; points: n_points x 2 (the mesh vertices on the face); edges: n_edges x 2 point indices (the
+ * open edges); cut: n_cut cut cells (v * nu + u, ascending); tol: 1e-9 * resolution; key_cell: max(eps, 1e-12).
+ * Receives the band points (pts_out: 2 per point, ids_out: the index of a mesh point, or -1 - (gv_index * (nu + 1) +
+ * gu_index) for a grid point; at most cap_points) and the triangles, counter-clockwise (tris_out: 3 band point
+ * indices each; at most cap_tris).  counts_out[8]: [0] band points, [1] triangles, [2] triangles dropped as
+ * non-positive, [3] constraint flips, [4] Lawson flips.  BBFMM_BAD_ARGUMENT with a message in err_out (err_cap bytes)
+ * for constraints that cannot be met (two open edges that cross) or too small capacities. */
+int bbfmm_debug_closure_triangulate(int32_t nu, int32_t nv, const double *gu, const double *gv, const double *points,
+                                    int64_t n_points, const int64_t *edges, int64_t n_edges, const int32_t *cut,
+                                    int64_t n_cut, double tol, double key_cell, int64_t cap_points, double *pts_out,
+                                    int64_t *ids_out, int64_t cap_tris, int64_t *tris_out, int64_t *counts_out,
+                                    char *err_out, int64_t err_cap);
+/* Host only: the exact sign of the orientation determinant of n triples of points in the plane (abc: 6 doubles per
+ * triple: a, b, c), the predicate of that triangulator: sign_out[i] in {-1, 0, 1}, 1 for counter-clockwise. */
+int bbfmm_debug_orient2d(const double *abc, int64_t n, int32_t *sign_out);
 /* The counts of the self-intersection detector for mesh i, stats_out[8] (all 0 where it did not run): [0] facets with
  * every corner inside the extents, [1] pairs of those with overlapping bounding boxes, [2] of those, pairs the Moeller
  * test accepts, [3] of those, true self-intersections, [4] triangles on a true pair, [5] their vertices that are clusters
