@@ -2051,6 +2051,16 @@ int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t ca
     return BBFMM_OK;
 }
 
+// The stage-2 operators with their x pairs, y pairs, singles and slot offsets (FmmTree::debug_m2l_pairs_axes_stage2).
+int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out) {
+    if (!h || !n_out) return BBFMM_BAD_ARGUMENT;
+    std::vector<int32_t> v;
+    h->tree.debug_m2l_pairs_axes_stage2(&v);
+    *n_out = static_cast<int64_t>(v.size());
+    if (out) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap, *n_out), out);
+    return BBFMM_OK;
+}
+
 // Debug only: parts into which the handle's most recent parity-basis stage-2 launch split the contraction (0: no launch yet).
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit) {
     if (!h || !ksplit) return BBFMM_BAD_ARGUMENT;

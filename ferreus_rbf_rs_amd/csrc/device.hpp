@@ -57,10 +57,13 @@ struct M2lClass {
     int32_t n_t;             // number of transfer vectors of this class (189 in 3-D)
     // stage 2 (target side): L_B[i] = sum_k UAllT[k][i] * ccat_B[k]
     const double *u_all;     // k_pad x n_pad; in the parity basis of stage 2 (k_pad - kp) x n_par, [U_e | pad | U_o | pad]
+                             // (two axes: [U_ee | U_eo | U_oe | U_oo] in the columns M2lS2PairsPlan::col())
     int32_t k_pad;           // slot length of a target of this class (multiple of 16)
     int32_t kp;              // parity-basis stage 2: the slot is [A | B | S] with the pairs' leaders in A and their partners
                              // in B (kp values each, a multiple of 16), the singles in S; operator row r < kp contracts
                              // slot[r] +- slot[kp + r], row r >= kp contracts slot[kp + r].  0: the plain layout
+    int32_t kpy;             // two axes of stage 2: the pairs of the rows [kpy, kp) are (t, R_y t), those below (t, R_x t);
+                             // a multiple of 16, kp when the class has no y pairs
     // cells of this class at this level
     const int32_t *cells;    // cell indices
     int32_t n_cells;
@@ -136,12 +139,25 @@ void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const 
 // Stage 2 in the parity basis of the x reflection: the operators are [U_e | pad | U_o | pad] (M2lClass::kp), Lp gets n_par =
 // 16 (ce ga + co gb) values per cell and right-hand side: ce chunks of ga column groups for the even part, then co chunks
 // of gb groups for the odd part (m2l_s2_pairs_plan chooses them for ne16 / 16 and no16 / 16 groups of real columns).
+// Two axes (ya > 0): the basis is [ee | eo | oe | oo]; a chunk of the x-even half holds ya groups of ee, then ga - ya groups
+// of eo, a chunk of the x-odd half yb groups of oe, then gb - yb of oo, so the boundary between the y-even and the y-odd
+// columns sits at the same place in every chunk of a half.  col(): the Lp / operator column of representative j of a part.
 struct M2lS2PairsPlan {
     int ga, gb, ce, co;
+    int ya = 0, yb = 0;
     int ne16() const { return 16 * ga * ce; }
-    int n_par() const { return 16 * (ga * ce + gb * co); }
+    __host__ __device__ int n_par() const { return 16 * (ga * ce + gb * co); }
+    __host__ __device__ int col(int part, int j) const { // part = 2 (odd along x) + (odd along y)
+        const int g = part < 2 ? ga : gb, y = part < 2 ? ya : yb, w = 16 * ((part & 1) ? g - y : y);
+        // group gl of the chunk, as the kernel's accumulators see it: groups 2 k and 2 k + 1 interleave over 32 columns
+        const int jj = j % w, gl = ((part & 1) ? y : 0) + jj / 16, pp = jj % 16, paired = g / 2 * 2;
+        const int local = gl < paired ? 32 * (gl / 2) + 2 * pp + (gl & 1) : 16 * paired + pp;
+        return (part < 2 ? 0 : 16 * ga * ce) + (j / w) * 16 * g + local;
+    }
 };
 M2lS2PairsPlan m2l_s2_pairs_plan(int groups_even, int groups_odd);
+// The plan of two axes for the 16-column groups of the parts ee, eo, oe, oo (all at least 1).
+M2lS2PairsPlan m2l_s2_pairs_plan2(const int groups[4]);
 // Returns false (and launches nothing) when the plan's widths have no kernel instance.  *ksplit_out (may be NULL): the parts
 // into which the launch split the contraction.
 bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
@@ -151,6 +167,10 @@ bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, 
 // writes all n_pad values of every row (the padding as zeros).
 void launch_m2l_unparity(const double *Lp, int n_par, int ne16, double *L, int n, int n_pad, int n_e, int n_o, int p, int64_t rows,
                          hipStream_t s);
+// The same from the basis of two axes, the inverse of launch_m2l_parity2: Lp[row] holds [ee | eo | oe | oo] in the columns
+// plan.col(); p2 = nodes per value of the second digit (n / p^2).
+void launch_m2l_unparity2(const double *Lp, const M2lS2PairsPlan &plan, double *L, int n, int n_pad, int p, int p2, int64_t rows,
+                          hipStream_t s);
 // Zeroes the slot segments of absent V pairs of a batch: segs = (slot / 2, length / 2) pairs, K buffers of cbuf_len.
 void launch_m2l_zero_segments(const int32_t *segs, int64_t n_segs, int K, double *cbuf, int64_t cbuf_len, hipStream_t s);
 // shared-basis extension: per-cell change of basis (OUT[cell] = IN[cell] * OP_level), setup-time dense product
@@ -176,6 +196,7 @@ struct M2lAssembleClass {
     int32_t u_npar, u_ne16, u_rows, u_ne, u_no;
     int32_t s1_axes;         // 2: stage 1 in the parity basis of axes 0 and 1, its four parts at the rows s1_off of vt_all
     M2lParityOffsets s1_off;
+    M2lS2PairsPlan u_plan;   // ya > 0: stage 2 in the parity basis of axes 0 and 1, the columns of u_all by u_plan.col()
 };
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s);

@@ -616,7 +616,11 @@ void launch_m2l_stage2(const M2lClass *classes, const M2lTileDesc *tiles, const 
 // every lane forms x + y (even half) or x - y (odd half) from LDS before the MFMAs.  A singles step multiplies the one
 // tile as m2l_gemm_k4 does.  The operator image, the IN tile layout, the MFMA loop and the epilogue are those of
 // m2l_gemm_k4's stage 2 (its comments apply); OUT is Lp with n_par values per cell.
-template <int NG16>
+// Two axes (Y < NG16): the chunk is [Y groups that are even along y | NG16 - Y groups that are odd along y] and the pair
+// steps from kpy / 16 on hold y pairs (t, R_y t): every lane forms x + y AND x - y and feeds the first Y groups from the
+// one set, the others from the other set, in either x half.  The boundary Y is fixed per instance, the kind of a step is
+// wave-uniform; x-pair steps and singles steps use one set for all groups as before.
+template <int NG16, int Y = NG16>
 __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2lTileDesc &tile, int n_par, int g16, bool odd,
                                                   int zk, int ksplit, int64_t C, const double *__restrict__ in, int64_t in_len,
                                                   double *__restrict__ out, const uint16_t *__restrict__ qlist,
@@ -628,6 +632,7 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
     const int nq = tile.q_count * (zk + 1) / ksplit - q_lo;
     const uint16_t *ql = qlist + tile.q_first + q_lo;
     const int kp = cls.kp, kp16 = kp >> 4;
+    const int kpy16 = Y < NG16 ? cls.kpy >> 4 : kp16; // first step of the y pairs
     const double *opbase = cls.u_all + 16 * g16;
 
     constexpr int OP_CHUNKS = 2 * NG16;
@@ -660,7 +665,7 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
     }
     const unsigned lds0 = lds_offset(lds);
     const int64_t qstride = (int64_t)16 * ld;
-    auto stage = [&](int qi, int buf) { // returns whether the step is a pair step (wave-uniform)
+    auto stage = [&](int qi, int buf) { // returns the kind of the step (wave-uniform): 0 singles, 1 x pairs, 2 y pairs
         const int q = (int)uniform_u32(ql[qi]);
 #pragma unroll
         for (int i = 0; i < NCH; ++i)
@@ -674,8 +679,10 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
             for (int h = 0; h < 2; ++h)
                 dma16(cptr[h] + 16 * q, lds0 + (unsigned)(buf * BUF + OP_DOUBLES + (2 * wave + h) * 128) * 8u);
         }
-        return q < kp16;
+        if constexpr (Y < NG16) return q < kpy16 ? 1 : q < kp16 ? 2 : 0;
+        else return q < kp16; // (one axis: whether the step is a pair step)
     };
+    using StepKind = std::conditional_t<(Y < NG16), int, bool>;
 
     double acc[4][NG16];
 #pragma unroll
@@ -687,17 +694,18 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
     const bool wave_live = wave * 16 < tile.count;
     const int di = lane >> 4, db = (lane >> 2) & 3, dj = lane & 3;
     const double sgn = odd ? -1.0 : 1.0;
-    bool pair_cur = false;
+    StepKind pair_cur{};
     if (nq > 0) pair_cur = stage(0, 0);
     wait_dma_and_barrier();
+    auto grp = [](auto &bs, auto &bd, int g) -> auto & { return g < Y ? bs : bd; }; // (g is a constant after unrolling)
     for (int sidx = 0; sidx < nq; ++sidx) {
         const double *op = lds + (sidx & 1) * BUF + lane;
         const double2 *op2 = reinterpret_cast<const double2 *>(lds + (sidx & 1) * BUF) + lane;
         const double *cx = lds + (sidx & 1) * BUF + OP_DOUBLES + wave * 256 + (bk * 4 + bj) * 2;
-        bool pair_next = false;
+        StepKind pair_next{};
         if (sidx + 1 < nq) pair_next = stage(sidx + 1, (sidx + 1) & 1); // streams in under the MFMAs below
         if (wave_live) {
-            double bq[4][4];
+            double bq[4][4], bd[4][4]; // bd: the set of the y-odd groups (two axes only)
 #pragma unroll
             for (int tg = 0; tg < 4; ++tg)
 #pragma unroll
@@ -706,7 +714,7 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
                     bq[tg][2 * eh] = y.x;
                     bq[tg][2 * eh + 1] = y.y;
                 }
-            if (pair_cur) { // x + y for the even half, x - y for the odd half (sgn * y is exact)
+            if (pair_cur == StepKind(1)) { // x + y for the even half, x - y for the odd half (sgn * y is exact)
 #pragma unroll
                 for (int tg = 0; tg < 4; ++tg)
 #pragma unroll
@@ -716,6 +724,26 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
                         bq[tg][2 * eh + 1] = x.y + sgn * bq[tg][2 * eh + 1];
                     }
             }
+            if constexpr (Y < NG16) {
+                if (pair_cur == 2) { // a y pair: x + y for the y-even groups, x - y for the y-odd groups, in both x halves
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                        for (int eh = 0; eh < 2; ++eh) {
+                            const double2 x = *reinterpret_cast<const double2 *>(cx + ((tg * 2 + eh) * 16) * 2);
+                            const double y0 = bq[tg][2 * eh], y1 = bq[tg][2 * eh + 1];
+                            bq[tg][2 * eh] = x.x + y0;
+                            bq[tg][2 * eh + 1] = x.y + y1;
+                            bd[tg][2 * eh] = x.x - y0;
+                            bd[tg][2 * eh + 1] = x.y - y1;
+                        }
+                } else {
+#pragma unroll
+                    for (int tg = 0; tg < 4; ++tg)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) bd[tg][e] = bq[tg][e];
+                }
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
 #pragma unroll
@@ -723,15 +751,15 @@ __device__ __forceinline__ void m2l_s2_pairs_body(const M2lClass &cls, const M2l
                     const double2 a = op2[(e * NP + pr) * 64];
 #pragma unroll
                     for (int tg = 0; tg < 4; ++tg) {
-                        acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, bq[tg][e], acc[tg][2 * pr], 0, 0, 0);
-                        acc[tg][2 * pr + 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, bq[tg][e], acc[tg][2 * pr + 1], 0, 0, 0);
+                        acc[tg][2 * pr] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, grp(bq, bd, 2 * pr)[tg][e], acc[tg][2 * pr], 0, 0, 0);
+                        acc[tg][2 * pr + 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, grp(bq, bd, 2 * pr + 1)[tg][e], acc[tg][2 * pr + 1], 0, 0, 0);
                     }
                 }
                 if (NS) {
                     const double a = op[4 * NP * 128 + e * 64];
 #pragma unroll
                     for (int tg = 0; tg < 4; ++tg)
-                        acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, bq[tg][e], acc[tg][NG16 - 1], 0, 0, 0);
+                        acc[tg][NG16 - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, grp(bq, bd, NG16 - 1)[tg][e], acc[tg][NG16 - 1], 0, 0, 0);
                 }
             }
         }
@@ -779,6 +807,21 @@ __global__ __launch_bounds__(512, 1) void m2l_s2_pairs_kernel(const M2lClass *__
     else m2l_s2_pairs_body<GB>(cls, tile, n_par, ce * GA + (zc - ce) * GB, true, zk, ksplit, C, in, in_len, out, qlist, tile_idx, lds);
 }
 
+// Two axes: a chunk of the x-even half is [YA groups of ee | GA - YA of eo], one of the x-odd half [YB of oe | GB - YB of oo].
+template <int GA, int YA, int GB, int YB>
+__global__ __launch_bounds__(512, 1) void m2l_s2_pairs2_kernel(const M2lClass *__restrict__ classes, const M2lTileDesc *__restrict__ tiles,
+                                                               int n_par, int ce, int co, int ksplit, int64_t C,
+                                                               const double *__restrict__ in, int64_t in_len, double *__restrict__ out,
+                                                               const uint16_t *__restrict__ qlist, const int32_t *__restrict__ tile_idx) {
+    extern __shared__ double lds[];
+    const M2lTileDesc tile = tiles[blockIdx.x];
+    const M2lClass cls = classes[tile.level_class];
+    const int zcols = ce + co;
+    const int zk = (int)blockIdx.z / zcols, zc = (int)blockIdx.z - zk * zcols;
+    if (zc < ce) m2l_s2_pairs_body<GA, YA>(cls, tile, n_par, zc * GA, false, zk, ksplit, C, in, in_len, out, qlist, tile_idx, lds);
+    else m2l_s2_pairs_body<GB, YB>(cls, tile, n_par, ce * GA + (zc - ce) * GB, true, zk, ksplit, C, in, in_len, out, qlist, tile_idx, lds);
+}
+
 // The chunk widths the kernel is instantiated for, (even, odd): 3-D order 7 has 13 + 10 groups, order 9 26 + 21, order 5
 // 5 + 4; the equal widths serve the other orders.  A half is padded to a whole number of chunks (zero operator columns).
 // The planner's table and the launcher's dispatch are both generated from this list.
@@ -802,6 +845,41 @@ M2lS2PairsPlan m2l_s2_pairs_plan(int groups_even, int groups_odd) {
     return best;
 }
 
+// Two axes, (GA, YA, GB, YB): 3-D order 7 has 7 + 6 and 6 + 4 groups, order 9 15 + 12 and 12 + 9 (two chunks of 8 + 6 and of
+// 6 + 5), order 5 3 + 2 and 2 + 2; (2, 1, 2, 1) serves any order with one chunk per group of the longer part.  Planner and
+// dispatch are generated from this list, as above.
+#define M2L_S2_PAIR2_WIDTHS(X) X(13, 7, 10, 6) X(14, 8, 11, 6) X(8, 4, 8, 4) X(5, 3, 4, 2) X(4, 2, 4, 2) X(2, 1, 2, 1)
+#define M2L_S2_WIDTH2_ENTRY(A, YA, B, YB) {A, YA, B, YB},
+static constexpr int kM2lS2Pair2Widths[][4] = {M2L_S2_PAIR2_WIDTHS(M2L_S2_WIDTH2_ENTRY)};
+#undef M2L_S2_WIDTH2_ENTRY
+
+M2lS2PairsPlan m2l_s2_pairs_plan2(const int groups[4]) {
+    M2lS2PairsPlan best{2, 2, 1, 1, 1, 1};
+    int best_cost = 1 << 30;
+    auto chunks = [](int n, int w) { return std::max(1, (n + w - 1) / w); };
+    for (const auto &w : kM2lS2Pair2Widths) {
+        const int ce = std::max(chunks(groups[0], w[1]), chunks(groups[1], w[0] - w[1]));
+        const int co = std::max(chunks(groups[2], w[3]), chunks(groups[3], w[2] - w[3]));
+        const int cost = ce * (w[0] + 2) + co * (w[2] + 2);
+        if (cost < best_cost) {
+            best_cost = cost;
+            best = M2lS2PairsPlan{w[0], w[2], ce, co, w[1], w[3]};
+        }
+    }
+    return best;
+}
+
+template <int GA, int YA, int GB, int YB>
+static void m2l_s2_pairs2_launch(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
+                                 const M2lS2PairsPlan &plan, int ksplit, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
+                                 const uint16_t *qlist, double *Lp, hipStream_t s) {
+    const size_t lds = 2 * sizeof(double) * (size_t)(2 * (GA > GB ? GA : GB) * 128 + 4096);
+    static std::atomic<uint64_t> attr_set[4] = {{0}, {0}, {0}, {0}};
+    (void)allow_large_dynamic_lds(reinterpret_cast<const void *>(&m2l_s2_pairs2_kernel<GA, YA, GB, YB>), lds, attr_set);
+    hipLaunchKernelGGL((m2l_s2_pairs2_kernel<GA, YA, GB, YB>), dim3(n_tiles, K, (plan.ce + plan.co) * ksplit), dim3(512), lds, s, classes,
+                       tiles, plan.n_par(), plan.ce, plan.co, ksplit, C, cbuf, cbuf_len, Lp, qlist, tile_idx);
+}
+
 template <int GA, int GB>
 static void m2l_s2_pairs_launch(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                                 const M2lS2PairsPlan &plan, int ksplit, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
@@ -820,7 +898,18 @@ bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, 
     // the contraction split of launch_m2l_stage2, on this launch's workgroups per tile (the parts add to the zeroed Lp)
     const int ksplit = m2l_s2_ksplit(static_cast<int64_t>(n_tiles) * (plan.ce + plan.co) * K, allow_ksplit);
     if (ksplit_out) *ksplit_out = ksplit;
-#define M2L_S2_DISPATCH(A, B)                                                                                            \
+    if (plan.ya > 0) { // two axes
+#define M2L_S2_DISPATCH2(A, YA, B, YB)                                                                                   \
+    if (plan.ga == A && plan.ya == YA && plan.gb == B && plan.yb == YB) {                                                \
+        m2l_s2_pairs2_launch<A, YA, B, YB>(classes, tiles, tile_idx, n_tiles, plan, ksplit, K, C, cbuf, cbuf_len, qlist, \
+                                           Lp, s);                                                                       \
+        return true;                                                                                                     \
+    }
+        M2L_S2_PAIR2_WIDTHS(M2L_S2_DISPATCH2)
+#undef M2L_S2_DISPATCH2
+        return false;
+    }
+#define M2L_S2_DISPATCH(A, B)                                                                                           \
     if (plan.ga == A && plan.gb == B) {                                                                                  \
         m2l_s2_pairs_launch<A, B>(classes, tiles, tile_idx, n_tiles, plan, ksplit, K, C, cbuf, cbuf_len, qlist, Lp, s);  \
         return true;                                                                                                     \
@@ -858,6 +947,44 @@ void launch_m2l_unparity(const double *Lp, int n_par, int ne16, double *L, int n
     const int p1 = n_e / ((p + 1) / 2);
     hipLaunchKernelGGL(m2l_unparity_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, Lp, n_par, ne16, L, n, n_pad, n_e,
                        n_o, p, p1, rows);
+}
+
+// Lp in the basis of two axes back to the node order, the inverse of m2l_parity2_kernel in one pass: a representative (i0, i1
+// < ceil(p/2), r < p2) reads ee, eo, oe, oo at the columns plan.col() and writes a = ee + eo, b = ee - eo, c = oe + oo, d =
+// oe - oo as L[m] = a + c, L[rho_x m] = a - c, L[rho_y m] = b + d, L[rho_x rho_y m] = b - d; on a centre plane the part that is
+// odd along that axis does not exist and the reflected node is the node itself.  The padding of the row is written as zeros.
+__global__ __launch_bounds__(256) void m2l_unparity2_kernel(const double *__restrict__ Lp, M2lS2PairsPlan plan, double *__restrict__ L,
+                                                            int n, int n_pad, int p, int p2, int64_t rows) {
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int n_par = plan.n_par();
+    const double *src = Lp + row * n_par;
+    double *dst = L + row * n_pad;
+    const int h = (p + 1) / 2, f = p / 2;
+    for (int e = threadIdx.x & 63; e < h * h * p2; e += 64) {
+        const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
+        const int m = (i0 * p + i1) * p2 + r;
+        const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2; // 0 on the centre planes
+        const bool cx = i0 >= f, cy = i1 >= f;
+        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
+        const double ee = src[plan.col(0, je)];
+        const double eo = cy ? 0.0 : src[plan.col(1, jo)];
+        const double oe = cx ? 0.0 : src[plan.col(2, je)];
+        const double oo = cx || cy ? 0.0 : src[plan.col(3, jo)];
+        const double a = cy ? ee : ee + eo, b = ee - eo, c = cy ? oe : oe + oo, d = oe - oo;
+        dst[m] = cx ? a : a + c;
+        if (!cx) dst[m + dx] = a - c;
+        if (!cy) dst[m + dy] = cx ? b : b + d;
+        if (!cx && !cy) dst[m + dx + dy] = b - d;
+    }
+    for (int j = n + (threadIdx.x & 63); j < n_pad; j += 64) dst[j] = 0.0;
+}
+
+void launch_m2l_unparity2(const double *Lp, const M2lS2PairsPlan &plan, double *L, int n, int n_pad, int p, int p2, int64_t rows,
+                          hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(m2l_unparity2_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, Lp, plan, L, n, n_pad, p, p2,
+                       rows);
 }
 
 // The multipoles in the parity basis of the x reflection: row = (right-hand side, cell), Mp[row] = [M_e | pad | M_o | pad]
@@ -1115,6 +1242,32 @@ __global__ __launch_bounds__(256) void assemble_u_parity_kernel(M2lAssembleClass
     }
 }
 
+// The same in the parity basis of axes 0 and 1 (assemble_vt_parity2_kernel's enumeration and factors): one thread per (rank
+// index kk, representative of ee) writes the entries of U_ee, U_eo, U_oe, U_oo of row + kk at the columns u_plan.col().
+__global__ __launch_bounds__(256) void assemble_u_parity2_kernel(M2lAssembleClass c, int n, const double *__restrict__ ops,
+                                                                 const int32_t *__restrict__ invperm, double *__restrict__ u_all) {
+    const int p = c.p, p2 = n / (p * p), h = (p + 1) / 2, f = p / 2, n_ee = h * h * p2;
+    const M2lAssembleTv tv = c.tgt[blockIdx.y];
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= static_cast<int64_t>(tv.rank) * n_ee) return;
+    const int kk = static_cast<int>(t / n_ee), e = static_cast<int>(t % n_ee);
+    const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
+    const int m = (i0 * p + i1) * p2 + r;
+    const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2;
+    const bool cx = i0 >= f, cy = i1 >= f;
+    const int32_t *inv = invperm + static_cast<int64_t>(tv.perm) * n;
+    const double *ucol = ops + tv.u_off + static_cast<int64_t>(kk) * n;
+    double *dst = u_all + static_cast<int64_t>(tv.row + kk) * c.u_npar;
+    const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
+    const double v = ucol[inv[m]], vx = ucol[inv[m + dx]], vy = ucol[inv[m + dy]], vxy = ucol[inv[m + dx + dy]];
+    const double w = (cx ? 1.0 : 0.5) * (cy ? 1.0 : 0.5);
+    const double e0 = cx ? v : v + vx, e1 = cx ? vy : vy + vxy, o0 = v - vx, o1 = vy - vxy;
+    dst[c.u_plan.col(0, je)] = w * (cy ? e0 : e0 + e1);
+    if (!cy) dst[c.u_plan.col(1, jo)] = w * (e0 - e1);
+    if (!cx) dst[c.u_plan.col(2, je)] = w * (cy ? o0 : o0 + o1);
+    if (!cx && !cy) dst[c.u_plan.col(3, jo)] = w * (o0 - o1);
+}
+
 void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compressed, const double *ops,
                          const int32_t *invperm, double *vt_all, double *u_all, hipStream_t s) {
     (void)hipMemsetAsync(vt_all, 0, static_cast<size_t>(c.n_e > 0 ? c.n_par : n_pad) * c.r_pad16 * sizeof(double), s);
@@ -1130,7 +1283,11 @@ void launch_m2l_assemble(const M2lAssembleClass &c, int n, int n_pad, bool compr
         // (one thread per entry, no grid-stride loop: the exact block count, not grid_for's capped one)
         hipLaunchKernelGGL(assemble_vt_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.n_src) * n + 255) / 256)), dim3(256), 0, s, c, n, n_pad,
                            compressed ? 1 : 0, ops, invperm, vt_all);
-    if (c.n_tgt > 0 && c.max_rank > 0 && c.u_npar > 0)
+    if (c.n_tgt > 0 && c.max_rank > 0 && c.u_npar > 0 && c.u_plan.ya > 0) {
+        const int h = (c.p + 1) / 2, n_ee = h * h * (n / (c.p * c.p));
+        hipLaunchKernelGGL(assemble_u_parity2_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.max_rank) * n_ee + 255) / 256), c.n_tgt),
+                           dim3(256), 0, s, c, n, ops, invperm, u_all);
+    } else if (c.n_tgt > 0 && c.max_rank > 0 && c.u_npar > 0)
         hipLaunchKernelGGL(assemble_u_parity_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(c.max_rank) * c.u_ne + 255) / 256), c.n_tgt),
                            dim3(256), 0, s, c, n, ops, invperm, u_all);
     else if (c.n_tgt > 0 && c.max_rank > 0)

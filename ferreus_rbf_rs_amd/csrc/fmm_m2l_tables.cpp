@@ -109,6 +109,21 @@ void FmmTree::fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, d
             for (int kk = 0; kk < op.rank; ++kk) {
                 double *dst = u_all + static_cast<size_t>(row0 + kk) * n_par;
                 const double *ucol = &op.u[static_cast<size_t>(kk) * n];
+                // two axes: column k holds (1 / orbit) sum over the orbit of +- U_t[kk][.] (m2l_s2_node_ / m2l_s2_sign_)
+                for (int k = 0; m2l_s2_axes_ == 2 && k < n_par; ++k) {
+                    const int32_t *nd = &m2l_s2_node_[static_cast<size_t>(4 * k)];
+                    const int8_t *sg = &m2l_s2_sign_[static_cast<size_t>(4 * k)];
+                    if (nd[0] < 0) continue; // padding
+                    int cnt = 0;
+                    double half[2] = {0.0, 0.0}; // (m, rho_x m) and (rho_y m, rho_x rho_y m), summed as the device's butterfly does
+                    for (int g = 0; g < 4; ++g)
+                        if (nd[g] >= 0) {
+                            half[g >> 1] += sg[g] * ucol[inv[nd[g]]];
+                            ++cnt;
+                        }
+                    dst[k] = (half[0] + half[1]) / cnt;
+                }
+                if (m2l_s2_axes_ == 2) continue;
                 for (int i = 0; i < m2l_ne_; ++i) {
                     const double a = ucol[inv[i]], b = ucol[inv[m2l_rho(i)]];
                     if (i >= m2l_no_) {
@@ -203,8 +218,10 @@ int FmmTree::build_m2l_tables() {
         }
         // The same along axis 1 for stage 1: t and R_y t (component 1 negated) share the reference operator and
         // invperm_{R_y t}[m] = invperm_t[rho_y m].  Only vectors that no x pair of the list at hand holds pair this way.
+        // The one check serves both stages: stage 2 pairs the target-side vectors on UAll_{R_y t}[kk][i] = U_ref[kk][
+        // invperm_{R_y t}[i]] = U_ref[kk][invperm_t[rho_y i]] = UAll_t[kk][rho_y i], the same reference entries, bit for bit.
         m2l_partner_y_.assign(static_cast<size_t>(nvec), -1);
-        for (int tv = 0; tv < nvec && m2l_pairs_; ++tv) {
+        for (int tv = 0; tv < nvec && (m2l_pairs_ || m2l_pairs2_); ++tv) {
             if (comp(tv, 1) == 0) continue;
             int rt = -1;
             for (int u = 0; u < nvec && rt < 0; ++u) {
@@ -425,13 +442,16 @@ int FmmTree::build_m2l_tables() {
     }
     // per target position: the partner's position (leader of a pair), -1 (single), -2 (partner)
     std::vector<std::vector<int32_t>> tgt_pair(ncls);
+    std::vector<std::vector<int8_t>> tgt_kind(ncls); // 0 single, 1 member of an x pair, 2 member of a y pair
     for (int o = 0; o < ncls; ++o) {
         const std::vector<int> &tl = tgt_list[o];
         tgt_pair[o].assign(tl.size(), -1);
+        tgt_kind[o].assign(tl.size(), 0);
         for (size_t pos = 0; m2l_pairs2_ && pos + 1 < tl.size(); ++pos)
             if (m2l_partner_[static_cast<size_t>(tl[pos])] == tl[pos + 1] && m2l_partner_[static_cast<size_t>(tl[pos + 1])] == tl[pos]) {
                 tgt_pair[o][pos] = static_cast<int32_t>(pos + 1);
                 tgt_pair[o][pos + 1] = -2;
+                tgt_kind[o][pos] = tgt_kind[o][pos + 1] = 1;
                 ++pos;
             }
     }
@@ -450,20 +470,37 @@ int FmmTree::build_m2l_tables() {
     // With the pairs of stage 2 the slot is [A | B | S]: the leaders' segments, padded to kp (a multiple of 16); their
     // partners' at the same offsets behind them; the singles.  Step q of the pair region contracts the 16 values at 16 q
     // and the 16 at kp + 16 q; a vector's rows stay contiguous, so stage 1 stores as before.
-    auto slot_layout = [&](int level, std::vector<std::vector<int>> *off_tgt, std::vector<int> *k_pad, std::vector<int> *kp_out = nullptr) {
+    // Two axes: the list is [x pairs | y pairs | singles]; the first y leader starts at kpy = the x leaders' length rounded up
+    // to 16, so that a contraction step holds pairs of one kind (kpy = kp when there are no y pairs).
+    auto slot_layout = [&](int level, std::vector<std::vector<int>> *off_tgt, std::vector<int> *k_pad, std::vector<int> *kp_out = nullptr,
+                           std::vector<int> *kpy_out = nullptr, std::vector<int> *pad_out = nullptr) {
         const auto &lops = ops_.m2l[level];
         off_tgt->assign(ncls, {});
         k_pad->assign(ncls, 0);
         if (kp_out) kp_out->assign(ncls, 0);
+        if (kpy_out) kpy_out->assign(ncls, 0);
+        if (pad_out) pad_out->assign(ncls, 0);
         for (int o = 0; o < ncls; ++o) {
-            int lead = 0;
+            int lead = 0, lead_y = 0;
+            bool has_y = false;
             for (size_t pos = 0; pos < tgt_list[o].size(); ++pos)
-                if (tgt_pair[o][pos] >= 0) lead += round_up(lops[ops_.ref_lookup[tgt_list[o][pos]]].rank, 2);
-            const int kp = round_up(lead, 16);
+                if (tgt_pair[o][pos] >= 0) {
+                    (tgt_kind[o][pos] == 2 ? lead_y : lead) += round_up(lops[ops_.ref_lookup[tgt_list[o][pos]]].rank, 2);
+                    has_y = has_y || tgt_kind[o][pos] == 2;
+                }
+            const int kp = has_y ? round_up(round_up(lead, 16) + lead_y, 16) : round_up(lead, 16);
+            const int kpy = has_y ? round_up(lead, 16) : kp;
+            if (kpy_out) (*kpy_out)[o] = kpy;
+            if (pad_out) (*pad_out)[o] = has_y ? kpy - lead : 0;
             int off = 0, off_s = 2 * kp;
+            bool in_y = false;
             for (size_t pos = 0; pos < tgt_list[o].size(); ++pos) {
                 const int seg = round_up(lops[ops_.ref_lookup[tgt_list[o][pos]]].rank, 2); // 16-byte aligned segments
                 if (tgt_pair[o][pos] >= 0) {
+                    if (tgt_kind[o][pos] == 2 && !in_y) { // the first y leader
+                        off = kpy;
+                        in_y = true;
+                    }
                     (*off_tgt)[o].push_back(off);
                 } else if (tgt_pair[o][pos] == -2) {
                     (*off_tgt)[o].push_back(kp + off);
@@ -477,6 +514,112 @@ int FmmTree::build_m2l_tables() {
             if (kp_out) (*kp_out)[o] = kp;
         }
     };
+    // BBFMM_M2L_S2_AXES (read per handle): 1 the x pairs alone, 2 also the y pairs of the vectors that x leaves alone; unset: by
+    // executed work, the sum over the level classes of contraction steps x column groups (padding included) -- two axes only
+    // where that is strictly smaller.
+    m2l_s2_axes_ = 1;
+    m2l_s2_work_[0] = m2l_s2_work_[1] = 0;
+    m2l_s2_node_.clear();
+    m2l_s2_sign_.clear();
+    m2l_s2_part_.clear();
+    if (m2l_pairs2_) {
+        const int p = ops_.p, p2 = n / (p * p), h = (p + 1) / 2, f = p / 2;
+        const int len[4] = {h * h * p2, h * f * p2, f * h * p2, f * f * p2};
+        int grp[4];
+        for (int i = 0; i < 4; ++i) grp[i] = std::max(1, round_up(len[i], 16) / 16);
+        const M2lS2PairsPlan plan2 = m2l_s2_pairs_plan2(grp);
+        // the candidate lists of two axes: [x pairs | y pairs | singles], R_y t directly behind t (t1 > 0 first)
+        std::vector<std::vector<int>> list2(ncls);
+        std::vector<std::vector<int32_t>> pair2(ncls);
+        std::vector<std::vector<int8_t>> kind2(ncls);
+        for (int o = 0; o < ncls; ++o) {
+            const std::vector<int> &tl = tgt_list[o];
+            std::vector<int> where(static_cast<size_t>(nvec), -1), xs, ys, ss;
+            for (size_t i = 0; i < tl.size(); ++i) where[static_cast<size_t>(tl[i])] = static_cast<int>(i);
+            std::vector<uint8_t> used(tl.size(), 0);
+            for (size_t i = 0; i < tl.size(); ++i)
+                if (tgt_pair[o][i] != -1) {
+                    xs.push_back(tl[i]); // (leader and partner are adjacent in the list)
+                    used[i] = 1;
+                }
+            for (size_t i = 0; i < tl.size(); ++i) {
+                if (used[i]) continue;
+                const int tv = tl[i], rt = m2l_partner_y_[static_cast<size_t>(tv)];
+                const int j = rt >= 0 ? where[static_cast<size_t>(rt)] : -1;
+                if (j < 0 || j == static_cast<int>(i) || used[static_cast<size_t>(j)] || m2l_partner_y_[static_cast<size_t>(rt)] != tv) continue;
+                const bool lead = comp(tv, 1) > 0;
+                ys.push_back(lead ? tv : rt);
+                ys.push_back(lead ? rt : tv);
+                used[i] = used[static_cast<size_t>(j)] = 1;
+            }
+            for (size_t i = 0; i < tl.size(); ++i)
+                if (!used[i]) ss.push_back(tl[i]);
+            for (int part = 0; part < 3; ++part) {
+                const std::vector<int> &src = part == 0 ? xs : part == 1 ? ys : ss;
+                for (size_t i = 0; i < src.size(); ++i) {
+                    const int32_t pos = static_cast<int32_t>(list2[o].size());
+                    list2[o].push_back(src[i]);
+                    pair2[o].push_back(part == 2 ? -1 : (i & 1) ? -2 : pos + 1);
+                    kind2[o].push_back(static_cast<int8_t>(part == 2 ? 0 : part + 1));
+                }
+            }
+        }
+        auto work_of = [&](int groups) {
+            int64_t w = 0;
+            for (int level = 2; level <= t.depth; ++level) {
+                std::vector<uint8_t> has(static_cast<size_t>(ncls), 0);
+                for (int64_t c = t.level_ptr[level]; c < t.level_ptr[level + 1]; ++c) has[t.octant[c]] = 1;
+                std::vector<std::vector<int>> off_tgt;
+                std::vector<int> k_pad, kp_cls;
+                slot_layout(level, &off_tgt, &k_pad, &kp_cls);
+                for (int o = 0; o < ncls; ++o)
+                    if (has[static_cast<size_t>(o)]) w += static_cast<int64_t>((k_pad[o] - kp_cls[o]) / 16) * groups;
+            }
+            return w;
+        };
+        m2l_s2_work_[0] = work_of(m2l_s2_plan_.n_par() / 16);
+        tgt_list.swap(list2);
+        tgt_pair.swap(pair2);
+        tgt_kind.swap(kind2);
+        m2l_s2_work_[1] = work_of(plan2.n_par() / 16);
+        const char *e = std::getenv("BBFMM_M2L_S2_AXES");
+        const int want = e ? std::atoi(e) : 0;
+        if (want == 2 || (want != 1 && m2l_s2_work_[1] < m2l_s2_work_[0])) {
+            m2l_s2_axes_ = 2;
+            m2l_s2_plan_ = plan2;
+            for (int o = 0; o < ncls; ++o)
+                for (size_t i = 0; i < tgt_list[o].size(); ++i) tpos_tgt[o][tgt_list[o][i]] = static_cast<int>(i);
+            // column of Lp / the operators -> the nodes of its orbit under {rho_x, rho_y}, their signs, its part
+            const int n_par = plan2.n_par();
+            m2l_s2_node_.assign(static_cast<size_t>(n_par) * 4, -1);
+            m2l_s2_sign_.assign(static_cast<size_t>(n_par) * 4, 0);
+            m2l_s2_part_.assign(static_cast<size_t>(n_par), -1);
+            for (int i0 = 0; i0 < h; ++i0)
+                for (int i1 = 0; i1 < h; ++i1)
+                    for (int r = 0; r < p2; ++r) {
+                        const int m = (i0 * p + i1) * p2 + r;
+                        const bool cx = i0 >= f, cy = i1 >= f;
+                        const int nodes[4] = {m, m2l_rho(m), m2l_rho_y(m), m2l_rho_y(m2l_rho(m))};
+                        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
+                        for (int part = 0; part < 4; ++part) {
+                            const bool ox = part >= 2, oy = part & 1; // odd along x / y
+                            if ((ox && cx) || (oy && cy)) continue;
+                            const size_t k = static_cast<size_t>(plan2.col(part, oy ? jo : je));
+                            m2l_s2_part_[k] = static_cast<int8_t>(part);
+                            for (int g = 0; g < 4; ++g) {
+                                const bool gx = g & 1, gy = g & 2; // the node reflected along x / y
+                                if ((gx && cx) || (gy && cy)) continue;
+                                m2l_s2_node_[4 * k + g] = nodes[g];
+                                m2l_s2_sign_[4 * k + g] = static_cast<int8_t>(((gx && ox) != (gy && oy)) ? -1 : 1);
+                            }
+                        }
+                    }
+        } else { // the x pairs alone: the lists as they were
+            tgt_list.swap(list2);
+            tgt_pair.swap(pair2);
+            tgt_kind.swap(kind2);
+        }
+    }
     // ---- batches.  The slots of all targets (one per cell, sum_t r_t doubles: 37 KB at order 7) are what the two
     // stages exchange -- 10.9 GB per right-hand side at 10M points, 76 GB for the finest level of an 80M-point tree.
     // They go through one buffer of at most m2l_budget_bytes_: consecutive levels share a batch while they fit; a
@@ -544,8 +687,8 @@ int FmmTree::build_m2l_tables() {
         const auto &lops = ops_.m2l[level];
         auto rank_of = [&](int tv) { return lops[ops_.ref_lookup[tv]].rank; };
         std::vector<std::vector<int>> off_tgt;
-        std::vector<int> k_pad, kp_cls;
-        slot_layout(level, &off_tgt, &k_pad, &kp_cls);
+        std::vector<int> k_pad, kp_cls, kpy_cls, pad_cls;
+        slot_layout(level, &off_tgt, &k_pad, &kp_cls, &kpy_cls, &pad_cls);
         const size_t first_class = m2l_host_.size();
         // Stage-1 row tables of a class-o operator stacked over the transfer vectors `tvs` (the whole admissible
         // list for the class itself, the present ones for a boundary variant): every transfer vector's rows
@@ -663,6 +806,9 @@ int FmmTree::build_m2l_tables() {
             hc.k_pad = k_pad[o];
             hc.kp = kp_cls[o];
             hc.tgt_pair = tgt_pair[o];
+            hc.tgt_kind = tgt_kind[o];
+            hc.kpy = kpy_cls[o];
+            hc.tgt_pad = pad_cls[o];
             // stage 1 tall operator rows
             if (!stage1_rows(o, src_list[o], &hc)) return fail(BBFMM_BAD_ARGUMENT, "M2L slot too long for the packed row table");
             if (hc.cells.empty()) continue;
@@ -1344,11 +1490,28 @@ int FmmTree::debug_apply_m2l_tables_host(const double *M, double *L) const {
                         sm[static_cast<size_t>(r)] = r < hc.kp ? cc[r] + cc[hc.kp + r] : cc[hc.kp + r];
                         df[static_cast<size_t>(r)] = r < hc.kp ? cc[r] - cc[hc.kp + r] : cc[hc.kp + r];
                     }
+                    if (m2l_s2_axes_ == 2) { // rows below kpy: x pairs, the sum to [ee | eo], the difference to [oe | oo]; rows
+                        // [kpy, kp): y pairs, the sum to [ee | oe], the difference to [eo | oo]; then the signed orbit sums back
+                        for (int k = 0; k < n_par; ++k) {
+                            const int part = m2l_s2_part_[static_cast<size_t>(k)];
+                            if (part < 0) continue;
+                            double acc = 0.0;
+                            for (int r = 0; r < rows; ++r) {
+                                const bool odd = r < hc.kpy ? part >= 2 : (part & 1);
+                                acc += hc.u_all[static_cast<size_t>(r) * n_par + k] * (odd ? df : sm)[static_cast<size_t>(r)];
+                            }
+                            for (int g = 0; g < 4; ++g)
+                                if (m2l_s2_node_[static_cast<size_t>(4 * k + g)] >= 0)
+                                    Lb[m2l_s2_node_[static_cast<size_t>(4 * k + g)]] += m2l_s2_sign_[static_cast<size_t>(4 * k + g)] * acc;
+                        }
+                        continue;
+                    }
                     for (int i = 0; i < m2l_ne_; ++i) {
                         double le = 0.0, lo = 0.0;
                         for (int r = 0; r < rows; ++r) {
                             le += hc.u_all[static_cast<size_t>(r) * n_par + i] * sm[static_cast<size_t>(r)];
-                            lo += hc.u_all[static_cast<size_t>(r) * n_par + ne16 + i] * df[static_cast<size_t>(r)];
+                            // (the centre plane has no odd part: ne16 + i would lie past the row's end at order 5)
+                            if (i < m2l_no_) lo += hc.u_all[static_cast<size_t>(r) * n_par + ne16 + i] * df[static_cast<size_t>(r)];
                         }
                         if (i >= m2l_no_) {
                             Lb[i] += le;
@@ -1447,9 +1610,41 @@ void FmmTree::debug_m2l_pairs_stage2(std::vector<int32_t> *out) const {
         const size_t n_at = out->size();
         out->push_back(0);
         int32_t n_entries = 0;
+        for (size_t pos = 0; pos < h.tgt_tv.size(); ++pos) { // (the members of a y pair are listed as two singles)
+            const bool x_member = h.tgt_kind[pos] == 1;
+            if (h.tgt_pair[pos] == -2 && x_member) continue;
+            out->push_back(h.tgt_pair[pos] >= 0 && x_member ? 1 : 0);
+            for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.tgt_tv[pos]) * d + a]);
+            ++n_entries;
+        }
+        (*out)[n_at] = n_entries;
+    }
+}
+
+void FmmTree::debug_m2l_pairs_axes_stage2(std::vector<int32_t> *out) const {
+    out->clear();
+    const int d = d_;
+    out->push_back(m2l_pairs2_ ? m2l_s2_axes_ : 0);
+    out->push_back(static_cast<int32_t>(m2l_s2_work_[0]));
+    out->push_back(static_cast<int32_t>(m2l_s2_work_[1]));
+    for (const HostM2lClass &h : m2l_host_) {
+        if (h.cells.empty()) continue;
+        const auto &lops = ops_.m2l[h.level];
+        out->push_back(h.level);
+        out->push_back(h.octant);
+        out->push_back(h.kp);
+        out->push_back(h.kpy);
+        out->push_back(h.k_pad);
+        out->push_back(h.tgt_pad);
+        const size_t n_at = out->size();
+        out->push_back(0);
+        int32_t n_entries = 0;
         for (size_t pos = 0; pos < h.tgt_tv.size(); ++pos) {
             if (h.tgt_pair[pos] == -2) continue;
-            out->push_back(h.tgt_pair[pos] >= 0 ? 1 : 0);
+            out->push_back(h.tgt_pair[pos] >= 0 ? h.tgt_kind[pos] : 0);
+            out->push_back(h.tgt_off[pos]);
+            out->push_back(h.tgt_pair[pos] >= 0 ? h.tgt_off[static_cast<size_t>(h.tgt_pair[pos])] : -1);
+            out->push_back(lops[ops_.ref_lookup[h.tgt_tv[pos]]].rank);
             for (int a = 0; a < d; ++a) out->push_back(ops_.all_vecs[static_cast<size_t>(h.tgt_tv[pos]) * d + a]);
             ++n_entries;
         }

@@ -499,6 +499,7 @@ int FmmTree::upload() {
         c.n_t = h.n_t;
         c.k_pad = h.k_pad;
         c.kp = h.kp;
+        c.kpy = h.kpy;
         c.yb0 = h.yb0;
         c.n_cells = static_cast<int32_t>(h.cells.size());
         if (h.cells.empty()) continue;
@@ -535,7 +536,7 @@ int FmmTree::upload() {
                                       h.r_pad16, h.k_pad, max_rank,
                                       m2l_pairs_ ? m2l_ne_ : 0, m2l_no_, m2l_ne16_, m2l_npar_, ops_.p,
                                       m2l_pairs2_ ? m2l_s2_plan_.n_par() : 0, m2l_s2_plan_.ne16(), h.k_pad - h.kp, m2l_ne_, m2l_no_,
-                                      m2l_axes_, m2l_s1_off_};
+                                      m2l_axes_, m2l_s1_off_, m2l_pairs2_ && m2l_s2_axes_ == 2 ? m2l_s2_plan_ : M2lS2PairsPlan{1, 1, 1, 1}};
             static const bool host_fill = std::getenv("BBFMM_M2L_ASSEMBLE_HOST") != nullptr; // checker: the host fill of round 1
             if (host_fill) {
                 std::vector<double> hv, hu;
@@ -989,8 +990,12 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
         }
         if (s2_pairs) { // this pass's right-hand sides back to the node order (part of stage 2's time)
             phase_begin();
-            launch_m2l_unparity(d_Lp_.p, lp_len, m2l_s2_plan_.ne16(), d_L_.p + static_cast<size_t>(k0) * C * cheb_.n_pad, ops_.n, cheb_.n_pad,
-                                m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(kb) * C, stream_);
+            if (m2l_s2_axes_ == 2)
+                launch_m2l_unparity2(d_Lp_.p, m2l_s2_plan_, d_L_.p + static_cast<size_t>(k0) * C * cheb_.n_pad, ops_.n, cheb_.n_pad, ops_.p,
+                                     ops_.n / (ops_.p * ops_.p), static_cast<int64_t>(kb) * C, stream_);
+            else
+                launch_m2l_unparity(d_Lp_.p, lp_len, m2l_s2_plan_.ne16(), d_L_.p + static_cast<size_t>(k0) * C * cheb_.n_pad, ops_.n, cheb_.n_pad,
+                                    m2l_ne_, m2l_no_, ops_.p, static_cast<int64_t>(kb) * C, stream_);
             phase_end(kPhM2L2);
         }
     }

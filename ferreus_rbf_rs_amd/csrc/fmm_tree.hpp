@@ -54,6 +54,11 @@ struct HostM2lClass {
     // at the same offsets kp further on, the singles from 2 kp; the operator has k_pad - kp rows (M2lClass::kp)
     int kp = 0;
     std::vector<int32_t> tgt_pair; // per target position: partner's position (leader), -1 (single), -2 (partner)
+    // two axes of stage 2 (FmmTree::m2l_s2_axes_ == 2): the list is [x pairs | y pairs | singles]; A holds the x leaders, padded
+    // to kpy (a multiple of 16), then the y leaders; kpy == kp when the class has no y pairs (M2lClass::kpy)
+    std::vector<int8_t> tgt_kind;  // per target position: 0 single, 1 member of an x pair, 2 member of a y pair
+    int kpy = 0;
+    int tgt_pad = 0;               // slot entries left empty in A so that the y pairs begin at a step of their own
     std::vector<int64_t> cbase;
 };
 
@@ -272,6 +277,12 @@ class FmmTree {
     // The same for the stage-2 operators (the target lists of the classes; kind is always 0).
     void debug_m2l_pairs_stage2(std::vector<int32_t> *out) const;
     bool m2l_pairs_stage2() const { return m2l_pairs2_; }
+    // Test hook: the stage-2 operators with both kinds of pairs.  Header: axes in force (0: no pairs), executed work
+    // (contraction steps x column groups over the level classes) of the one-axis and of the two-axis layout.  Per class with
+    // cells: level, octant, kp, kpy, k_pad, padding entries of A before kpy, number of entries; per entry: 0 (single), 1 (x
+    // pair, listed by its leader) or 2 (y pair), its slot offset, its partner's slot offset (-1: a single), its rank, then
+    // the d components of t.
+    void debug_m2l_pairs_axes_stage2(std::vector<int32_t> *out) const;
     // Test hook: parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet).
     int debug_m2l_s2_last_ksplit() const { return m2l_s2_last_ksplit_; }
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
@@ -398,6 +409,13 @@ class FmmTree {
     M2lS2PairsPlan m2l_s2_plan_{1, 1, 1, 1}; // column chunks of the two halves; n_par() values per cell in Lp
     DevBuf<double> d_Lp_;                // m2l_rhs_chunk_ x C x m2l_s2_plan_.n_par(): one pass of right-hand sides at a time
     int m2l_s2_last_ksplit_ = 0;         // debug_m2l_s2_last_ksplit
+    // Two axes of stage 2 (BBFMM_M2L_S2_AXES): the target-side vectors without an x partner pair by R_y,
+    // Lp and the operators are [ee | eo | oe | oo] in the columns m2l_s2_plan_.col().
+    int m2l_s2_axes_ = 1;                // reflection axes of stage 2's pairs: 1 (x) or 2
+    int64_t m2l_s2_work_[2] = {0, 0};    // contraction steps x column groups over the level classes, one axis / two axes
+    std::vector<int32_t> m2l_s2_node_;   // two axes: per column of Lp the up to four nodes of its orbit (-1: none) ...
+    std::vector<int8_t> m2l_s2_sign_;    // ... their signs ...
+    std::vector<int8_t> m2l_s2_part_;    // ... and its part (2 (odd along x) + (odd along y)); -1: padding
     // partition
     int part_rank_ = 0, part_world_ = 1;
     std::vector<int64_t> part_rows_, part_bounds_;

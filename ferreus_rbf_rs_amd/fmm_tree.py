@@ -599,12 +599,33 @@ class FmmTree:
             i += 4 + ne * (d + 1)
         return bool(on.value), ops
 
-    def debug_m2l_pairs_axes(self):
+    def debug_m2l_pairs_axes(self, stage=1):
         """(info, operators) of stage 1 with both kinds of pairs.  info: axes in force (0: no pairs) and the executed work
         (column blocks x contraction steps over the level classes) of the one-axis and the two-axis layout.  Per operator:
         level, octant, kind, pad_cols (columns left empty to keep the kinds apart), yb0, block_kinds (per column block 0:
         x order, 1: y order), and x_pairs (listed by the member with t0 > 0), y_pairs (t1 > 0), singles as dicts
-        vector -> (first, last) column block of its columns ((-1, -1): rank 0)."""
+        vector -> (first, last) column block of its columns ((-1, -1): rank 0).
+        stage=2: the target lists of the classes.  info as above with the work as contraction steps x column groups.  Per
+        class: level, octant, kp (length of A), kpy (the y boundary: offset in A of the first y leader, kp without y
+        pairs), k_pad, pad (entries of A left empty before kpy), and x_pairs, y_pairs (listed by their leaders), singles
+        as dicts vector -> (slot offset, partner's slot offset or -1, rank)."""
+        if stage == 2:
+            fn = self._lib.bbfmm_debug_m2l_pairs_axes_stage2
+            n = ctypes.c_int64()
+            self._raise(fn(self._h, None, 0, ctypes.byref(n)))
+            buf = np.zeros(max(n.value, 1), dtype=np.int32)
+            self._raise(fn(self._h, buf.ctypes.data, n.value, ctypes.byref(n)))
+            info = {"axes": int(buf[0]), "work_x": int(buf[1]), "work_xy": int(buf[2])}
+            d, ops, i = self.dim, [], 3
+            while i < n.value:
+                level, octant, kp, kpy, k_pad, pad, ne = (int(v) for v in buf[i:i + 7])
+                ent = buf[i + 7:i + 7 + ne * (d + 4)].reshape(ne, d + 4)
+                by_kind = [{tuple(int(x) for x in e[4:]): (int(e[1]), int(e[2]), int(e[3])) for e in ent if e[0] == k}
+                           for k in range(3)]
+                ops.append({"level": level, "octant": octant, "kp": kp, "kpy": kpy, "k_pad": k_pad, "pad": pad,
+                            "singles": by_kind[0], "x_pairs": by_kind[1], "y_pairs": by_kind[2]})
+                i += 7 + ne * (d + 4)
+            return info, ops
         fn = self._lib.bbfmm_debug_m2l_pairs_axes
         n = ctypes.c_int64()
         self._raise(fn(self._h, None, 0, ctypes.byref(n)))

@@ -772,6 +772,7 @@ int bbfmm_debug_m2l_variants(const bbfmm_handle *h, int64_t *n_variants, int64_t
 int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
 int bbfmm_debug_m2l_pairs_axes(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
 int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
+int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit); /* debug only */
 
 /* The Morton primitives of csrc/morton.hpp as the host tree build uses them (morton.rs:58-263; the
