@@ -2068,6 +2068,14 @@ int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit) {
     return BBFMM_OK;
 }
 
+// Debug only: values per row of the multipoles in stage 1's parity basis (what debug_get_coefficients('P') returns per cell);
+// 0 when the handle has none.
+int bbfmm_debug_m2l_parity_len(const bbfmm_handle *h, int32_t *len) {
+    if (!h || !len) return BBFMM_BAD_ARGUMENT;
+    *len = h->tree.debug_m2l_parity_len();
+    return BBFMM_OK;
+}
+
 int bbfmm_debug_get_coefficients(bbfmm_handle *h, char which, int32_t k, double *out) {
     GUARD(h) return h->tree.debug_get_coefficients(which, k, out);
     END_GUARD(h)

@@ -107,12 +107,24 @@ void launch_p2m(const ChebRef &ch, const double *const *src_xyz, const double *w
                 const int32_t *pt_end, const double *centers, const double *lengths, double *M,
                 hipStream_t s);
 // (both return 0 or the hipError_t of a refused function attribute: dynamic LDS above 64 KB at 3-D orders 14-16)
+struct M2lParityRowArgs;
+struct M2lUnparityRowArgs;
+// par / Mp (both or neither): the 3-D register kernel also writes every child's row of Mp, the multipoles in stage 1's
+// parity basis (m2m_writes_parity() says whether this order and dimension have that kernel; otherwise par must be NULL).
 int launch_m2m(const ChebRef &ch, int K, int64_t C, const int32_t *parents, int n_parents,
                const int64_t *child_ptr, const int32_t *child_idx, const int32_t *octant, double *M,
-               hipStream_t s);
+               hipStream_t s, const M2lParityRowArgs *par = nullptr, double *Mp = nullptr);
+bool m2m_writes_parity(const ChebRef &ch);
+// unp / Lp / has_m2l / has_x (all or none): the 3-D register kernel takes the M2L part of a child from Lp, stage 2's output in
+// the parity basis, instead of from L: L[c] = (unparity(Lp[c]) or 0 without has_m2l[c]) + (L[c] if has_x[c], else 0) +
+// transfer (l2l_reads_parity() says whether this order and dimension have that kernel; otherwise unp must be NULL).
 int launch_l2l(const ChebRef &ch, int K, int64_t C, const int32_t *cells, int n_cells,
                const int32_t *parent, const int32_t *octant, const uint8_t *active, double *L,
-               hipStream_t s);
+               hipStream_t s, const M2lUnparityRowArgs *unp = nullptr, const double *Lp = nullptr,
+               const uint8_t *has_m2l = nullptr, const uint8_t *has_x = nullptr);
+bool l2l_reads_parity(const ChebRef &ch);
+// Zeroes the rows (n_pad values, every right-hand side) of the listed cells.
+void launch_zero_rows(const int32_t *cells, int n_cells, int n_pad, int K, int64_t C, double *L, hipStream_t s);
 
 // tile_idx: NULL, or for tiles with pad != 0 the class positions of the tile's cells
 // (tile.first indexes tile_idx; a partition's compact source tiles)
@@ -158,6 +170,32 @@ struct M2lS2PairsPlan {
 M2lS2PairsPlan m2l_s2_pairs_plan(int groups_even, int groups_odd);
 // The plan of two axes for the 16-column groups of the parts ee, eo, oe, oo (all at least 1).
 M2lS2PairsPlan m2l_s2_pairs_plan2(const int groups[4]);
+// What a kernel needs to write a row of Mp (stage 1's basis): axes = 1: [M_e | pad | M_o | pad] (ne16, n_e, n_o, p1);
+// axes = 2: [M_ee | M_eo | M_oe | M_oo] at off (p2); axes = 0: none.
+struct M2lParityRowArgs {
+    int axes = 0;
+    int n_par = 0;
+    int p = 0;
+    int ne16 = 0, n_e = 0, n_o = 0, p1 = 0; // one axis
+    M2lParityOffsets off{{0, 0, 0, 0}};     // two axes
+    int p2 = 0;
+};
+
+// What a kernel needs to read a row of Lp (stage 2's basis): axes = 1: [L_e | pad | L_o | pad]; axes = 2: the columns
+// plan.col() of [ee | eo | oe | oo]; axes = 0: none.
+struct M2lUnparityRowArgs {
+    int axes = 0;
+    int n_par = 0;
+    int p = 0;
+    int ne16 = 0, n_e = 0, n_o = 0, p1 = 0; // one axis
+    M2lS2PairsPlan plan{1, 1, 1, 1};        // two axes
+    int p2 = 0;
+};
+// Mp rows of the listed cells only (every right-hand side): the standalone change of basis for the cells no fused M2M writes.
+void launch_m2l_parity_cells(const double *M, int n_pad, double *Mp, const M2lParityRowArgs &par, const int32_t *cells, int n_cells,
+                             int K, int64_t C, hipStream_t s);
+// The parts into which launch_m2l_stage2_pairs splits the contraction of a launch of n_tiles tiles and K right-hand sides.
+int m2l_s2_pairs_ksplit(int n_tiles, const M2lS2PairsPlan &plan, int K, bool allow_ksplit);
 // Returns false (and launches nothing) when the plan's widths have no kernel instance.  *ksplit_out (may be NULL): the parts
 // into which the launch split the contraction.
 bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
@@ -267,7 +305,10 @@ void launch_p2l(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32
 void launch_l2p(const ChebRef &ch, int n_jobs, const int32_t *leaf_cells, const int32_t *tgt_begin,
                 const int32_t *tgt_end, const double *centers, const double *lengths,
                 const double *const *tgt_xyz, int64_t n_tgt, int K, int64_t C, const double *L,
-                double *out_sorted, double *grad_sorted, hipStream_t s);
+                double *out_sorted, double *grad_sorted, hipStream_t s, const int32_t *perm = nullptr,
+                double *user_out = nullptr, int64_t ldo = 0);
+// (perm / user_out / ldo, all or none: the potentials go to user_out[k ldo + perm[t]] = out_sorted[k n_tgt + t] + y, the
+// caller's order, and out_sorted keeps the near field alone; every target must lie in one job)
 
 // Orders the device Chebyshev kernels are instantiated for (3-D: p <= 12).
 bool l2p_order_supported(int p, int d);

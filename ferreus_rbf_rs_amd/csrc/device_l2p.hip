@@ -19,7 +19,9 @@ __global__ __launch_bounds__((64 * l2p_waves<P, D>())) void l2p_kernel(const Dev
                                                              const double *__restrict__ lengths, Xyz tgt,
                                                              int64_t n_tgt, int K, int64_t C,
                                                              const double *__restrict__ L,
-                                                             double *__restrict__ out, double *__restrict__ grad) {
+                                                             double *__restrict__ out, double *__restrict__ grad,
+                                                             const int32_t *__restrict__ perm, double *__restrict__ user_out,
+                                                             int64_t ldo) {
     constexpr int P1 = D > 1 ? P : 1, P2 = D > 2 ? P : 1, N = P * P1 * P2;
     constexpr int WAVES = l2p_waves<P, D>();
     __shared__ double s_L[WAVES][N];
@@ -105,7 +107,10 @@ __global__ __launch_bounds__((64 * l2p_waves<P, D>())) void l2p_kernel(const Dev
                 }
             }
             if (valid) {
-                out[(int64_t)k * n_tgt + t] += y;
+                // (perm: the sum goes to the caller's row of user_out instead of back to the sorted array -- the same one add.
+                // Values only: the gradient kernels are out of registers as they are and take no perm.)
+                if (!GRAD && perm) user_out[(int64_t)k * ldo + perm[t]] = out[(int64_t)k * n_tgt + t] + y;
+                else out[(int64_t)k * n_tgt + t] += y;
                 if (GRAD) {
                     grad[((int64_t)k * D + 0) * n_tgt + t] += gx * gs;
                     if (D > 1) grad[((int64_t)k * D + 1) * n_tgt + t] += gy * gs;
@@ -120,29 +125,30 @@ template <int P, int D>
 static void l2p_launch_pd(const ChebRef &ch, int n_jobs, const int32_t *leaf_cells, const int32_t *tgt_begin,
                           const int32_t *tgt_end, const double *centers, const double *lengths, Xyz tgt,
                           int64_t n_tgt, int K, int64_t C, const double *L, double *out_sorted, double *grad_sorted,
-                          hipStream_t s) {
+                          hipStream_t s, const int32_t *perm, double *user_out, int64_t ldo) {
     constexpr int WAVES = l2p_waves<P, D>();
     const int blocks = (n_jobs + WAVES - 1) / WAVES;
     if (grad_sorted)
         hipLaunchKernelGGL((l2p_kernel<P, D, true>), dim3(blocks), dim3(64 * WAVES), 0, s, ch.dev, n_jobs,
                            leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted,
-                           grad_sorted);
+                           grad_sorted, perm, user_out, ldo);
     else
         hipLaunchKernelGGL((l2p_kernel<P, D, false>), dim3(blocks), dim3(64 * WAVES), 0, s, ch.dev, n_jobs,
                            leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted,
-                           grad_sorted);
+                           grad_sorted, perm, user_out, ldo);
 }
 
 template <int P>
 static void l2p_launch_p(const ChebRef &ch, int n_jobs, const int32_t *leaf_cells, const int32_t *tgt_begin,
                          const int32_t *tgt_end, const double *centers, const double *lengths, Xyz tgt, int64_t n_tgt,
-                         int K, int64_t C, const double *L, double *out_sorted, double *grad_sorted, hipStream_t s) {
+                         int K, int64_t C, const double *L, double *out_sorted, double *grad_sorted, hipStream_t s,
+                         const int32_t *perm, double *user_out, int64_t ldo) {
     if (ch.d == 3) {
-        l2p_launch_pd<P, 3>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s);
+        l2p_launch_pd<P, 3>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s, perm, user_out, ldo);
     } else if (ch.d == 2) {
-        l2p_launch_pd<P, 2>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s);
+        l2p_launch_pd<P, 2>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s, perm, user_out, ldo);
     } else {
-        l2p_launch_pd<P, 1>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s);
+        l2p_launch_pd<P, 1>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L, out_sorted, grad_sorted, s, perm, user_out, ldo);
     }
 }
 
@@ -151,12 +157,13 @@ bool l2p_order_supported(int p, int d) { return p >= 2 && p <= kMaxOrder && d >=
 void launch_l2p(const ChebRef &ch, int n_jobs, const int32_t *leaf_cells, const int32_t *tgt_begin,
                 const int32_t *tgt_end, const double *centers, const double *lengths, const double *const *tgt_xyz,
                 int64_t n_tgt, int K, int64_t C, const double *L, double *out_sorted, double *grad_sorted,
-                hipStream_t s) {
+                hipStream_t s, const int32_t *perm, double *user_out, int64_t ldo) {
     if (n_jobs == 0) return;
+    if (perm && grad_sorted) return; // (no caller asks for both; the gradient kernels ignore perm)
     const Xyz tgt = make_xyz(tgt_xyz);
     dispatch_order<2, 16>(ch.p, [&](auto pc) {
         l2p_launch_p<decltype(pc)::value>(ch, n_jobs, leaf_cells, tgt_begin, tgt_end, centers, lengths, tgt, n_tgt, K, C, L,
-                                          out_sorted, grad_sorted, s);
+                                          out_sorted, grad_sorted, s, perm, user_out, ldo);
     });
 }
 

@@ -1,5 +1,6 @@
 // M2L: the streamed-operator GEMM kernel of both stages, its chunk and split plans, and the operators' assembly in HBM.
 #include "device_common.hpp"
+#include "m2l_basis_rows.hpp"
 
 #include <cmath>
 
@@ -891,12 +892,16 @@ static void m2l_s2_pairs_launch(const M2lClass *classes, const M2lTileDesc *tile
                        plan.n_par(), plan.ce, plan.co, ksplit, C, cbuf, cbuf_len, Lp, qlist, tile_idx);
 }
 
+int m2l_s2_pairs_ksplit(int n_tiles, const M2lS2PairsPlan &plan, int K, bool allow_ksplit) {
+    return m2l_s2_ksplit(static_cast<int64_t>(n_tiles) * (plan.ce + plan.co) * K, allow_ksplit);
+}
+
 bool launch_m2l_stage2_pairs(const M2lClass *classes, const M2lTileDesc *tiles, const int32_t *tile_idx, int n_tiles,
                              const M2lS2PairsPlan &plan, int K, int64_t C, const double *cbuf, int64_t cbuf_len,
                              const uint16_t *qlist, double *Lp, hipStream_t s, bool allow_ksplit, int *ksplit_out) {
     if (n_tiles == 0) return true;
     // the contraction split of launch_m2l_stage2, on this launch's workgroups per tile (the parts add to the zeroed Lp)
-    const int ksplit = m2l_s2_ksplit(static_cast<int64_t>(n_tiles) * (plan.ce + plan.co) * K, allow_ksplit);
+    const int ksplit = m2l_s2_pairs_ksplit(n_tiles, plan, K, allow_ksplit);
     if (ksplit_out) *ksplit_out = ksplit;
     if (plan.ya > 0) { // two axes
 #define M2L_S2_DISPATCH2(A, YA, B, YB)                                                                                   \
@@ -928,16 +933,7 @@ __global__ __launch_bounds__(256) void m2l_unparity_kernel(const double *__restr
     if (row >= rows) return;
     const double *src = Lp + row * n_par;
     double *dst = L + row * n_pad;
-    for (int j = threadIdx.x & 63; j < n_e; j += 64) {
-        const double e = src[j];
-        if (j < n_o) {
-            const double o = src[ne16 + j];
-            dst[j] = e + o;
-            dst[j + (p - 1 - 2 * (j / p1)) * p1] = e - o;
-        } else {
-            dst[j] = e;
-        }
-    }
+    m2l_unparity_row(src, ne16, n_e, n_o, p, p1, threadIdx.x & 63, [&](int m, double v) { dst[m] = v; });
     for (int j = n + (threadIdx.x & 63); j < n_pad; j += 64) dst[j] = 0.0;
 }
 
@@ -960,23 +956,7 @@ __global__ __launch_bounds__(256) void m2l_unparity2_kernel(const double *__rest
     const int n_par = plan.n_par();
     const double *src = Lp + row * n_par;
     double *dst = L + row * n_pad;
-    const int h = (p + 1) / 2, f = p / 2;
-    for (int e = threadIdx.x & 63; e < h * h * p2; e += 64) {
-        const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
-        const int m = (i0 * p + i1) * p2 + r;
-        const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2; // 0 on the centre planes
-        const bool cx = i0 >= f, cy = i1 >= f;
-        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r;
-        const double ee = src[plan.col(0, je)];
-        const double eo = cy ? 0.0 : src[plan.col(1, jo)];
-        const double oe = cx ? 0.0 : src[plan.col(2, je)];
-        const double oo = cx || cy ? 0.0 : src[plan.col(3, jo)];
-        const double a = cy ? ee : ee + eo, b = ee - eo, c = cy ? oe : oe + oo, d = oe - oo;
-        dst[m] = cx ? a : a + c;
-        if (!cx) dst[m + dx] = a - c;
-        if (!cy) dst[m + dy] = cx ? b : b + d;
-        if (!cx && !cy) dst[m + dx + dy] = b - d;
-    }
+    m2l_unparity2_row(src, plan, p, p2, threadIdx.x & 63, [&](int m, double v) { dst[m] = v; });
     for (int j = n + (threadIdx.x & 63); j < n_pad; j += 64) dst[j] = 0.0;
 }
 
@@ -996,16 +976,7 @@ __global__ __launch_bounds__(256) void m2l_parity_kernel(const double *__restric
     if (row >= rows) return;
     const double *src = M + row * n_pad;
     double *dst = Mp + row * n_par;
-    for (int j = threadIdx.x & 63; j < n_e; j += 64) {
-        const double v = src[j];
-        if (j < n_o) {
-            const double w = src[j + (p - 1 - 2 * (j / p1)) * p1];
-            dst[j] = v + w;
-            dst[ne16 + j] = v - w;
-        } else {
-            dst[j] = v;
-        }
-    }
+    m2l_parity_row(src, dst, ne16, n_e, n_o, p, p1, threadIdx.x & 63);
 }
 
 void launch_m2l_parity(const double *M, int n_pad, double *Mp, int n_par, int ne16, int n_e, int n_o, int p, int64_t rows,
@@ -1027,20 +998,7 @@ __global__ __launch_bounds__(256) void m2l_parity2_kernel(const double *__restri
     if (row >= rows) return;
     const double *src = M + row * n_pad;
     double *dst = Mp + row * n_par;
-    const int h = (p + 1) / 2, f = p / 2;
-    for (int e = threadIdx.x & 63; e < h * h * p2; e += 64) {
-        const int i0 = e / (h * p2), i1 = (e - i0 * h * p2) / p2, r = e - (i0 * h + i1) * p2;
-        const int m = (i0 * p + i1) * p2 + r;
-        const int dx = (p - 1 - 2 * i0) * p * p2, dy = (p - 1 - 2 * i1) * p2; // 0 on the centre planes
-        const bool cx = i0 >= f, cy = i1 >= f;
-        const double v = src[m], vx = src[m + dx], vy = src[m + dy], vxy = src[m + dx + dy];
-        const double e0 = cx ? v : v + vx, e1 = cx ? vy : vy + vxy, o0 = v - vx, o1 = vy - vxy;
-        const int je = (i0 * h + i1) * p2 + r, jo = (i0 * f + i1) * p2 + r; // position among the y-even / y-odd representatives
-        dst[off.v[0] + je] = cy ? e0 : e0 + e1;
-        if (!cy) dst[off.v[1] + jo] = e0 - e1;
-        if (!cx) dst[off.v[2] + je] = cy ? o0 : o0 + o1;
-        if (!cx && !cy) dst[off.v[3] + jo] = o0 - o1;
-    }
+    m2l_parity2_row(src, dst, off, p, p2, threadIdx.x & 63);
 }
 
 void launch_m2l_parity2(const double *M, int n_pad, double *Mp, int n_par, M2lParityOffsets off, int p, int p2, int64_t rows,
@@ -1048,6 +1006,23 @@ void launch_m2l_parity2(const double *M, int n_pad, double *Mp, int n_par, M2lPa
     if (rows <= 0) return;
     hipLaunchKernelGGL(m2l_parity2_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, M, n_pad, Mp, n_par, off, p, p2,
                        rows);
+}
+
+// The same change of basis (either layout) for the rows of a list of cells: one wave per (right-hand side, listed cell).
+__global__ __launch_bounds__(256) void m2l_parity_cells_kernel(const double *__restrict__ M, int n_pad, double *__restrict__ Mp,
+                                                               M2lParityRowArgs par, const int32_t *__restrict__ cells, int n_cells,
+                                                               int K, int64_t C) {
+    const int64_t job = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (job >= static_cast<int64_t>(K) * n_cells) return;
+    const int64_t row = (job / n_cells) * C + cells[job % n_cells];
+    m2l_parity_row_any(par, M + row * n_pad, Mp + row * par.n_par, threadIdx.x & 63);
+}
+
+void launch_m2l_parity_cells(const double *M, int n_pad, double *Mp, const M2lParityRowArgs &par, const int32_t *cells, int n_cells,
+                             int K, int64_t C, hipStream_t s) {
+    if (n_cells <= 0 || K <= 0) return;
+    hipLaunchKernelGGL(m2l_parity_cells_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(K) * n_cells + 3) / 4)), dim3(256), 0, s, M,
+                       n_pad, Mp, par, cells, n_cells, K, C);
 }
 
 // Slot segments of absent pairs: 16 lanes per segment, 16 bytes per lane and round.

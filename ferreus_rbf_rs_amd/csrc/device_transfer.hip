@@ -1,5 +1,6 @@
 // M2M / L2L: the transfers between a cell and its children, general and 3-D register kernels with their launchers.
 #include "device_common.hpp"
+#include "m2l_basis_rows.hpp"
 
 namespace bbfmm {
 
@@ -123,8 +124,10 @@ __device__ inline void pencil_apply(double (&v)[P], const double *__restrict__ x
 
 // in: global vector of the source cell; buf: wave-private LDS (P^3 doubles); on return buf holds
 // the transferred vector.  oct: octant of the child (bit a <-> axis a, chebyshev.rs:183-192).
+// (always inline: each kernel instance has its own copy with the P x P blocks in scalar registers -- with two kernel
+// instances per order calling it the compiler otherwise leaves it out of line from order 8 up, at twice the time)
 template <int P, bool FORWARD>
-__device__ inline void transfer3_wave(const double *__restrict__ in, double *buf, const double *__restrict__ xfer,
+__device__ __forceinline__ void transfer3_wave(const double *__restrict__ in, double *buf, const double *__restrict__ xfer,
                                       int oct, int lane) {
     constexpr int PP = P * P, NPEN = (PP + 63) / 64;
     const double *x0 = xfer + ((oct >> 0) & 1) * PP, *x1 = xfer + ((oct >> 1) & 1) * PP,
@@ -177,13 +180,20 @@ __device__ inline void transfer3_wave(const double *__restrict__ in, double *buf
 constexpr int XFER_WAVES = 4;
 
 // local_to_local, one wave per child cell: L_child += T_child^T L_parent (bbfmm.rs:1051-1086)
-template <int P>
+// UNP = 1 or 2 (the reflection axes of stage 2's basis; 0: the plain kernel): the M2L part of the child comes from Lp, stage 2's output in the parity basis, through the row function of the
+// standalone pass back to the node order: L_child = (unparity(Lp_child) + (has_x ? L_child : 0)) + T_child^T L_parent, the
+// association of that pass, P2L and the plain kernel one after the other.  Cells in no stage-2 tile (has_m2l = 0) take 0 and
+// do not read Lp; only cells with an X list hold anything in L before (P2L, onto rows zeroed by launch_zero_rows).
+template <int P, int UNP>
 __global__ __launch_bounds__(64 * XFER_WAVES) void l2l3_kernel(const DevCheb *__restrict__ chp, int K, int64_t C,
                                                                const int32_t *__restrict__ cells, int n_cells,
                                                                const int32_t *__restrict__ parent,
                                                                const int32_t *__restrict__ octant,
                                                                const uint8_t *__restrict__ active,
-                                                               double *__restrict__ L) {
+                                                               double *__restrict__ L, M2lUnparityRowArgs unp,
+                                                               const double *__restrict__ Lp,
+                                                               const uint8_t *__restrict__ has_m2l,
+                                                               const uint8_t *__restrict__ has_x) {
     constexpr int N = P * P * P;
     __shared__ double s_buf[XFER_WAVES][N];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -195,22 +205,60 @@ __global__ __launch_bounds__(64 * XFER_WAVES) void l2l3_kernel(const DevCheb *__
     if (Pc < 0) return;
     const int oct = __builtin_amdgcn_readfirstlane(octant[c]);
     const int n_pad = chp->n_pad;
+    bool hm = false, hx = false;
+    if constexpr (UNP != 0) {
+        hm = __builtin_amdgcn_readfirstlane((int)has_m2l[c]) != 0;
+        hx = __builtin_amdgcn_readfirstlane((int)has_x[c]) != 0;
+    }
     for (int k = 0; k < K; ++k) {
         transfer3_wave<P, false>(L + ((int64_t)k * C + Pc) * n_pad, s_buf[wave], chp->xfer, oct, lane);
         double *Lc = L + ((int64_t)k * C + c) * n_pad;
-        for (int I = lane; I < N; I += 64) Lc[I] += s_buf[wave][I];
+        if constexpr (UNP != 0) {
+            const double *tr = s_buf[wave];
+            // (The row of Lp is read here, behind the transfer, one representative after the other.  Loading all of it before the
+            // transfer, to hide its latency, was measured slower at order 7: 101 registers halve the waves per SIMD, L2L 0.65
+            // against 0.61 ms at 10M points.  The order and p1 = p2 = P as constants: no integer division by a kernel argument.)
+            const double *src = Lp + ((int64_t)k * C + c) * unp.n_par;
+            const auto add = [&](int m, double v) { Lc[m] = (v + (hx ? Lc[m] : 0.0)) + tr[m]; };
+            if (hm && UNP == 2) m2l_unparity2_row(src, unp.plan, P, P, lane, add);
+            else if (hm) m2l_unparity_row(src, unp.ne16, unp.n_e, unp.n_o, P, P * P, lane, add);
+            else
+                for (int I = lane; I < N; I += 64) Lc[I] = (0.0 + (hx ? Lc[I] : 0.0)) + tr[I];
+        } else {
+            for (int I = lane; I < N; I += 64) Lc[I] += s_buf[wave][I];
+        }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
+// Rows of L that P2L is about to add to: one wave per (right-hand side, listed cell), all n_pad values.
+__global__ __launch_bounds__(256) void zero_rows_kernel(const int32_t *__restrict__ cells, int n_cells, int n_pad, int K, int64_t C,
+                                                        double *__restrict__ L) {
+    const int64_t job = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (job >= static_cast<int64_t>(K) * n_cells) return;
+    double *row = L + ((job / n_cells) * C + cells[job % n_cells]) * n_pad;
+    for (int j = threadIdx.x & 63; j < n_pad; j += 64) row[j] = 0.0;
+}
+
+void launch_zero_rows(const int32_t *cells, int n_cells, int n_pad, int K, int64_t C, double *L, hipStream_t s) {
+    if (n_cells <= 0 || K <= 0) return;
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(K) * n_cells + 3) / 4)), dim3(256), 0, s, cells,
+                       n_cells, n_pad, K, C, L);
+}
+
 // multipole_to_multipole, one workgroup per parent, one wave per child:
 // M_parent += sum_children T_child M_child (bbfmm.rs:742-772)
-template <int P>
+// PAR: the wave also writes its child's row of Mp, the multipoles in stage 1's parity basis, through the row function of
+// the standalone change of basis.  It reads the child's M from global memory as the transfer does: the two sets of loads
+// are in flight together and meet in the cache, where a copy through the wave's LDS slice would put the change of basis
+// between the loads and the transfer.  The children of all parents are the cells of level >= 2, the ones stage 1 reads.
+template <int P, bool PAR>
 __global__ __launch_bounds__(512) void m2m3_kernel(const DevCheb *__restrict__ chp, int K, int64_t C,
                                                    const int32_t *__restrict__ parents,
                                                    const int64_t *__restrict__ child_ptr,
                                                    const int32_t *__restrict__ child_idx,
-                                                   const int32_t *__restrict__ octant, double *__restrict__ M) {
+                                                   const int32_t *__restrict__ octant, double *__restrict__ M,
+                                                   M2lParityRowArgs par, double *__restrict__ Mpar) {
     constexpr int N = P * P * P;
     __shared__ double s_buf[8][N];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -222,7 +270,13 @@ __global__ __launch_bounds__(512) void m2m3_kernel(const DevCheb *__restrict__ c
         if (wave < n_ch) {
             const int ch = __builtin_amdgcn_readfirstlane(child_idx[c0 + wave]);
             const int oct = __builtin_amdgcn_readfirstlane(octant[ch]);
-            transfer3_wave<P, true>(M + ((int64_t)k * C + ch) * n_pad, s_buf[wave], chp->xfer, oct, lane);
+            const double *Mc = M + ((int64_t)k * C + ch) * n_pad;
+            if constexpr (PAR) { // (the order and p1 = p2 = P as constants: no integer division by a kernel argument)
+                double *dst = Mpar + ((int64_t)k * C + ch) * par.n_par;
+                if (par.axes == 2) m2l_parity2_row(Mc, dst, par.off, P, P, lane);
+                else m2l_parity_row(Mc, dst, par.ne16, par.n_e, par.n_o, P, P * P, lane);
+            }
+            transfer3_wave<P, true>(Mc, s_buf[wave], chp->xfer, oct, lane);
         }
         __syncthreads();
         double *Mp = M + ((int64_t)k * C + Pc) * n_pad;
@@ -235,13 +289,21 @@ __global__ __launch_bounds__(512) void m2m3_kernel(const DevCheb *__restrict__ c
     }
 }
 
+bool m2m_writes_parity(const ChebRef &ch) { return ch.d == 3 && ch.p >= 2 && ch.p <= 10; }
+bool l2l_reads_parity(const ChebRef &ch) { return ch.d == 3 && ch.p >= 2 && ch.p <= 12; }
+
 int launch_m2m(const ChebRef &ch, int K, int64_t C, const int32_t *parents, int n_parents, const int64_t *child_ptr,
-               const int32_t *child_idx, const int32_t *octant, double *M, hipStream_t s) {
+               const int32_t *child_idx, const int32_t *octant, double *M, hipStream_t s, const M2lParityRowArgs *par, double *Mp) {
     if (n_parents == 0) return 0;
+    if (par && (!Mp || !m2m_writes_parity(ch))) return static_cast<int>(hipErrorInvalidValue); // (no kernel writes Mp here)
     // wave-per-child register kernels (8 x P^3 doubles of LDS)
     if (ch.d == 3 && dispatch_order<2, 10>(ch.p, [&](auto pc) {
-            hipLaunchKernelGGL((m2m3_kernel<decltype(pc)::value>), dim3(n_parents), dim3(512), 0, s, ch.dev, K, C, parents, child_ptr,
-                               child_idx, octant, M);
+            if (par)
+                hipLaunchKernelGGL((m2m3_kernel<decltype(pc)::value, true>), dim3(n_parents), dim3(512), 0, s, ch.dev, K, C, parents,
+                                   child_ptr, child_idx, octant, M, *par, Mp);
+            else
+                hipLaunchKernelGGL((m2m3_kernel<decltype(pc)::value, false>), dim3(n_parents), dim3(512), 0, s, ch.dev, K, C, parents,
+                                   child_ptr, child_idx, octant, M, M2lParityRowArgs{}, nullptr);
         }))
         return 0;
     const size_t lds = sizeof(double) * (3 * (size_t)ch.n + 2 * ch.p * ch.p);
@@ -253,11 +315,21 @@ int launch_m2m(const ChebRef &ch, int K, int64_t C, const int32_t *parents, int 
 }
 
 int launch_l2l(const ChebRef &ch, int K, int64_t C, const int32_t *cells, int n_cells, const int32_t *parent,
-               const int32_t *octant, const uint8_t *active, double *L, hipStream_t s) {
+               const int32_t *octant, const uint8_t *active, double *L, hipStream_t s, const M2lUnparityRowArgs *unp, const double *Lp,
+               const uint8_t *has_m2l, const uint8_t *has_x) {
     if (n_cells == 0) return 0;
+    if (unp && (!Lp || !has_m2l || !has_x || !l2l_reads_parity(ch))) return static_cast<int>(hipErrorInvalidValue); // (no kernel reads Lp here)
     if (ch.d == 3 && dispatch_order<2, 12>(ch.p, [&](auto pc) {
-            hipLaunchKernelGGL((l2l3_kernel<decltype(pc)::value>), dim3((n_cells + XFER_WAVES - 1) / XFER_WAVES), dim3(64 * XFER_WAVES),
-                               0, s, ch.dev, K, C, cells, n_cells, parent, octant, active, L);
+            const dim3 grid((n_cells + XFER_WAVES - 1) / XFER_WAVES), block(64 * XFER_WAVES);
+            if (unp && unp->axes == 2)
+                hipLaunchKernelGGL((l2l3_kernel<decltype(pc)::value, 2>), grid, block, 0, s, ch.dev, K, C, cells, n_cells, parent, octant,
+                                   active, L, *unp, Lp, has_m2l, has_x);
+            else if (unp)
+                hipLaunchKernelGGL((l2l3_kernel<decltype(pc)::value, 1>), grid, block, 0, s, ch.dev, K, C, cells, n_cells, parent, octant,
+                                   active, L, *unp, Lp, has_m2l, has_x);
+            else
+                hipLaunchKernelGGL((l2l3_kernel<decltype(pc)::value, 0>), grid, block, 0, s, ch.dev, K, C, cells, n_cells, parent, octant,
+                                   active, L, M2lUnparityRowArgs{}, nullptr, nullptr, nullptr);
         }))
         return 0;
     const size_t lds = sizeof(double) * (2 * (size_t)ch.n + 2 * ch.p * ch.p);

@@ -595,7 +595,68 @@ int FmmTree::upload() {
     CHK(dupload(&d_m2l_qlist_, m2l_qlist_h_));
     std::vector<uint8_t> act(static_cast<size_t>(C), 1);
     CHK(dupload(&d_active_, act));
+    { // the fused changes of basis (see fused_mask_): what the whole-tree plan writes where
+        const char *e = std::getenv("BBFMM_FUSED_PASSES"); // read per handle
+        fused_mask_ = e ? static_cast<unsigned>(std::atoi(e)) & 15u : 15u;
+        if (!(fused_mask_ & 2u)) fused_mask_ &= ~4u;
+        std::vector<uint8_t> has_m2l(static_cast<size_t>(C), 0), has_x(static_cast<size_t>(C), 0);
+        fused_flags_ok_ = true;
+        for (const M2lTileDesc &td : m2l_tiles2_h_) {
+            const size_t lc = static_cast<size_t>(td.level_class);
+            const HostM2lClass &h = lc < m2l_host_.size() ? m2l_host_[lc] : m2l_variants_[lc - m2l_host_.size()];
+            if (td.pad != 0 || td.first < 0 || static_cast<size_t>(td.first) + td.count > h.cells.size()) {
+                fused_flags_ok_ = false; // (not a plain range of the class list: no whole-tree stage-2 tile is)
+                break;
+            }
+            for (int32_t q = 0; q < td.count; ++q) has_m2l[static_cast<size_t>(h.cells[static_cast<size_t>(td.first + q)])] = 1;
+        }
+        for (int32_t c : x_cells_) has_x[static_cast<size_t>(c)] = 1;
+        CHK(dupload(&d_has_m2l_, has_m2l));
+        CHK(dupload(&d_has_x_, has_x));
+        std::vector<int32_t> top;
+        for (size_t l = 0; l < level_cells_.size() && l < 2; ++l) top.insert(top.end(), level_cells_[l].begin(), level_cells_[l].end());
+        n_top_cells_ = static_cast<int>(top.size());
+        CHK(dupload(&d_top_cells_, top));
+    }
     return BBFMM_OK;
+}
+
+M2lParityRowArgs FmmTree::mp_row_args() const {
+    M2lParityRowArgs a;
+    a.axes = m2l_axes_;
+    a.n_par = m2l_npar_;
+    a.p = ops_.p;
+    a.ne16 = m2l_ne16_;
+    a.n_e = m2l_ne_;
+    a.n_o = m2l_no_;
+    a.p1 = m2l_ne_ / ((ops_.p + 1) / 2);
+    a.off = m2l_s1_off_;
+    a.p2 = ops_.n / (ops_.p * ops_.p);
+    return a;
+}
+
+M2lUnparityRowArgs FmmTree::lp_row_args() const {
+    M2lUnparityRowArgs a;
+    a.axes = m2l_s2_axes_;
+    a.n_par = m2l_s2_plan_.n_par();
+    a.p = ops_.p;
+    a.ne16 = m2l_s2_plan_.ne16();
+    a.n_e = m2l_ne_;
+    a.n_o = m2l_no_;
+    a.p1 = m2l_ne_ / ((ops_.p + 1) / 2);
+    a.plan = m2l_s2_plan_;
+    a.p2 = ops_.n / (ops_.p * ops_.p);
+    return a;
+}
+
+bool FmmTree::m2m_fusable() const {
+    return (fused_mask_ & 1u) && m2l_pairs_ && !m2l_batches_.empty() && !shared_basis_ && ops_.d == 3 && ops_.p == cheb_.p &&
+           m2m_writes_parity(cheb_);
+}
+
+bool FmmTree::l2l_fusable(int k) const {
+    return (fused_mask_ & 2u) && fused_flags_ok_ && m2l_pairs2_ && !m2l_batches_.empty() && !shared_basis_ && ops_.d == 3 &&
+           ops_.p == cheb_.p && l2l_reads_parity(cheb_) && k <= m2l_rhs_chunk_;
 }
 
 int FmmTree::ensure_rhs_capacity(int k) {
@@ -616,6 +677,7 @@ int FmmTree::ensure_rhs_capacity(int k) {
     if (m2l_pairs_) { // zeroed once: the pad columns are never written
         dfree(&d_Mp_);
         CHK(dalloc(&d_Mp_, static_cast<size_t>(k) * C * m2l_npar_, true));
+        mp_current_k_ = 0;
     }
     if (shared_basis_) {
         dfree(&d_Mc_);
@@ -877,6 +939,9 @@ int FmmTree::upward(int k, const DownwardPlan *dp) {
     const HostTree &t = tree_;
     const int64_t C = t.n_cells();
     const bool part = dp && dp->restrict_upward;
+    mp_current_k_ = 0; // M is being rewritten; set again below when this pass wrote Mp beside it
+    const bool fuse_mp = !dp && m2m_fusable();
+    const M2lParityRowArgs mp_args = mp_row_args();
     multipoles_partial_ = part; // (a partition's share: nothing but the partitioned downward pass may read M until a whole upward pass has run)
     // reset_multipole_coefficients (bbfmm.rs:619-624): M is zero-initialised once; P2M and M2M assign
     // every leaf with sources and every parent, the other entries are never written.  A partition computes
@@ -899,8 +964,13 @@ int FmmTree::upward(int k, const DownwardPlan *dp) {
         const int rc = part ? launch_m2m(cheb_, k, C, dp->d_up_parents[level].p, static_cast<int>(dp->up_parents_h[level].size()),
                                          dp->d_part_child_ptr.p, dp->d_part_child_idx.p, d_octant_.p, d_M_.p, stream_)
                             : launch_m2m(cheb_, k, C, d_m2m_parents_[level].p, static_cast<int>(m2m_parents_[level].size()),
-                                         d_child_ptr_.p, d_child_idx_.p, d_octant_.p, d_M_.p, stream_);
+                                         d_child_ptr_.p, d_child_idx_.p, d_octant_.p, d_M_.p, stream_, fuse_mp ? &mp_args : nullptr,
+                                         fuse_mp ? d_Mp_.p : nullptr);
         if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "M2M: dynamic LDS attribute");
+    }
+    if (fuse_mp) { // levels 0 and 1 are nobody's children in these launches: their few rows through the standalone function
+        launch_m2l_parity_cells(d_M_.p, cheb_.n_pad, d_Mp_.p, mp_args, d_top_cells_.p, n_top_cells_, k, C, stream_);
+        mp_current_k_ = k;
     }
     phase_end(kPhM2M);
     HIPCHK(hipGetLastError());
@@ -920,6 +990,7 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     const HostTree &t = tree_;
     const int64_t C = t.n_cells();
     have_locals_ = false; // L is being rewritten; downward_tail says what it holds at the end
+    lp_pending_ = false;
     // reset_local_coefficients (bbfmm.rs:627-632): tiles without any V-list entry are not written by
     // stage 2, and P2L / L2L add onto L
     // (parity basis of stage 2: the same holds for Lp, cleared per pass of right-hand sides below, and the pass back to the
@@ -932,7 +1003,8 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     const int m2l_len = shared_basis_ ? basis_pad_ : cheb_.n_pad;
     const double *m_in = shared_basis_ ? d_Mc_.p : m2l_pairs_ ? d_Mp_.p : d_M_.p;
     const int s1_len = m2l_pairs_ ? m2l_npar_ : m2l_len, s1_ne16 = m2l_pairs_ ? m2l_ne16_ : 0; // stage 1's contraction
-    if (m2l_pairs_ && !m2l_batches_.empty()) { // the multipoles in the parity basis, once per matvec (part of stage 1's time)
+    // (a whole upward pass with the fused M2M has written Mp beside M: nothing to do)
+    if (m2l_pairs_ && !m2l_batches_.empty() && mp_current_k_ < k) { // the multipoles in the parity basis, once per matvec (part of stage 1's time)
         phase_begin();
         if (m2l_axes_ == 2)
             launch_m2l_parity2(d_M_.p, cheb_.n_pad, d_Mp_.p, m2l_npar_, m2l_s1_off_, ops_.p, ops_.n / (ops_.p * ops_.p), static_cast<int64_t>(k) * C, stream_);
@@ -950,11 +1022,21 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
     // The batches go through the bounded intermediate one after another (stage 1 fills the slots of the batch's
     // targets, stage 2 contracts them into L), m2l_rhs_chunk_ right-hand sides per pass.
     const int nb = static_cast<int>(m2l_batches_.size());
+    // The whole-tree pass of right-hand sides that fit Lp at once leaves the M2L part there: the fused L2L of downward_tail
+    // reads it.  Then Lp needs no clearing either unless a launch splits its contraction (the parts add atomically): an unsplit
+    // launch stores every column of every cell of its tiles, and L2L reads no other row (has_m2l).
+    const bool fuse_lp = s2_pairs && !dp && l2l_fusable(k);
+    bool clear_lp = true;
+    if (fuse_lp && (fused_mask_ & 4u)) {
+        clear_lp = false;
+        for (const M2lBatch &mb : m2l_batches_)
+            if (mb.t2_count > 0 && m2l_s2_pairs_ksplit(mb.t2_count, m2l_s2_plan_, k, !deterministic_) > 1) clear_lp = true;
+    }
     for (int k0 = 0; k0 < k; k0 += m2l_rhs_chunk_) {
         const int kb = std::min(m2l_rhs_chunk_, k - k0);
         const double *m_chunk = m_in + static_cast<size_t>(k0) * C * s1_len;
         double *l_chunk = s2_pairs ? d_Lp_.p : l_out + static_cast<size_t>(k0) * C * m2l_len;
-        if (s2_pairs) HIPCHK(hipMemsetAsync(d_Lp_.p, 0, static_cast<size_t>(kb) * C * lp_len * sizeof(double), stream_));
+        if (s2_pairs && clear_lp) HIPCHK(hipMemsetAsync(d_Lp_.p, 0, static_cast<size_t>(kb) * C * lp_len * sizeof(double), stream_));
         for (int b = 0; b < nb; ++b) {
             const M2lBatch &mb = m2l_batches_[static_cast<size_t>(b)];
             const int t1_first = dp ? dp->batch_t1[4 * b] : mb.t1_first, t1_count = dp ? dp->batch_t1[4 * b + 1] : mb.t1_count;
@@ -988,7 +1070,9 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
                                   cbuf_batch_len_, d_m2l_qlist_.p, l_chunk, stream_, !deterministic_);
             phase_end(kPhM2L2);
         }
-        if (s2_pairs) { // this pass's right-hand sides back to the node order (part of stage 2's time)
+        if (fuse_lp) {
+            lp_pending_ = true;
+        } else if (s2_pairs) { // this pass's right-hand sides back to the node order (part of stage 2's time)
             phase_begin();
             if (m2l_s2_axes_ == 2)
                 launch_m2l_unparity2(d_Lp_.p, m2l_s2_plan_, d_L_.p + static_cast<size_t>(k0) * C * cheb_.n_pad, ops_.n, cheb_.n_pad, ops_.p,
@@ -1013,7 +1097,12 @@ int FmmTree::downward_m2l(int k, const DownwardPlan *dp) {
 int FmmTree::downward_tail(int k, const DownwardPlan *dp, const TargetSet *wx) {
     const HostTree &t = tree_;
     const int64_t C = t.n_cells();
+    const bool fuse_lp = lp_pending_ && !dp; // (downward_m2l of this pass left the M2L part in Lp)
+    lp_pending_ = false;
+    const M2lUnparityRowArgs lp_args = lp_row_args();
     phase_begin();
+    // no pass has rewritten L: the rows P2L adds to start from zero, L2L assigns every other row it or the leaf pass reads
+    if (fuse_lp && t.adaptive) launch_zero_rows(d_x_cells_.p, static_cast<int>(x_cells_.size()), cheb_.n_pad, k, C, d_L_.p, stream_);
     if (t.adaptive && wx) { // targets = all sources: P2L and M2P share their kernel evaluations (X = W^T)
         launch_wx_sym(kernel_, cheb_, wx->n_wx_jobs, wx->wx_tb.p, wx->wx_te.p, wx->wx_range.p, wx->n_wxl_jobs, wx->wxl_tb.p, wx->wxl_te.p,
                       wx->wxl_range.p, d_w_idx_.p, d_centers_.p,
@@ -1032,7 +1121,8 @@ int FmmTree::downward_tail(int k, const DownwardPlan *dp, const TargetSet *wx) {
     phase_begin();
     for (int level = 2; level <= t.depth; ++level) { // children of level-1.. cells (bbfmm.rs:834-856)
         const int rc = launch_l2l(cheb_, k, C, d_level_cells_[level].p, static_cast<int>(level_cells_[level].size()), d_parent_.p,
-                                  d_octant_.p, dp ? dp->d_active.p : d_active_.p, d_L_.p, stream_);
+                                  d_octant_.p, dp ? dp->d_active.p : d_active_.p, d_L_.p, stream_, fuse_lp ? &lp_args : nullptr,
+                                  fuse_lp ? d_Lp_.p : nullptr, fuse_lp ? d_has_m2l_.p : nullptr, fuse_lp ? d_has_x_.p : nullptr);
         if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "L2L: dynamic LDS attribute");
     }
     phase_end(kPhL2L);
@@ -1102,12 +1192,12 @@ int FmmTree::leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStre
 }
 
 // L2P: needs the finished local expansions
-int FmmTree::leaf_pass_far(const TargetSet &ts, int k, bool with_grads) {
+int FmmTree::leaf_pass_far(const TargetSet &ts, int k, bool with_grads, double *user_out, int64_t ldo) {
     const int64_t C = tree_.n_cells();
     double *grad = with_grads ? ts.grad.p : nullptr;
     phase_begin();
     launch_l2p(cheb_, ts.n_jobs, ts.job_cell.p, ts.tgt_begin.p, ts.tgt_end.p, d_centers_.p, d_lengths_.p, ts.xyz_ptr,
-               ts.m, k, C, d_L_.p, ts.out.p, grad, stream_);
+               ts.m, k, C, d_L_.p, ts.out.p, grad, stream_, user_out ? ts.perm.p : nullptr, user_out, ldo);
     phase_end(kPhL2P);
     HIPCHK(hipGetLastError());
     return BBFMM_OK;
@@ -1200,10 +1290,13 @@ int FmmTree::evaluate(const double *w, int64_t rows, int k, int64_t ldw, const d
             if (wx) HIPCHK(hipMemsetAsync(ts.out.p, 0, static_cast<size_t>(k) * ts.m * sizeof(double), stream_));
             CHK(downward_tail(k, nullptr, wx ? &ts : nullptr));
             CHK(leaf_pass_near(ts, k, false, stream_, 3, wx));
-            CHK(leaf_pass_far(ts, k, false));
-            phase_begin();
-            launch_scatter_output(ts.out.p, ts.m, k, ts.perm.p, d_out_.p, N, 0, stream_);
-            phase_end(kPhScatter);
+            const bool l2p_scatters = (fused_mask_ & 8u) != 0; // (the resident target set: every source lies in one L2P job)
+            CHK(leaf_pass_far(ts, k, false, l2p_scatters ? d_out_.p : nullptr, N));
+            if (!l2p_scatters) {
+                phase_begin();
+                launch_scatter_output(ts.out.p, ts.m, k, ts.perm.p, d_out_.p, N, 0, stream_);
+                phase_end(kPhScatter);
+            }
             HIPCHK(hipGetLastError());
             double *pin_out = h_pin_ + static_cast<size_t>(k) * N; // behind the staged weights (put_weights sized the buffer)
             const auto t_queued = std::chrono::steady_clock::now();
@@ -1429,10 +1522,13 @@ int FmmTree::matvec_device(const double *d_w, int64_t ldw, int k, double *d_out,
     if (wx) HIPCHK(hipMemsetAsync(ts.out.p, 0, static_cast<size_t>(k) * ts.m * sizeof(double), stream_));
     CHK(downward(k, plan, wx ? &ts : nullptr));
     CHK(leaf_pass_near(ts, k, false, stream_, 3, wx));
-    CHK(leaf_pass_far(ts, k, false));
-    phase_begin();
-    launch_scatter_output(ts.out.p, ts.m, k, ts.perm.p, d_out, ldo, 0, stream_);
-    phase_end(kPhScatter);
+    const bool l2p_scatters = (fused_mask_ & 8u) != 0 && !have_part_; // (the resident target set: every source lies in one L2P job)
+    CHK(leaf_pass_far(ts, k, false, l2p_scatters ? d_out : nullptr, ldo));
+    if (!l2p_scatters) {
+        phase_begin();
+        launch_scatter_output(ts.out.p, ts.m, k, ts.perm.p, d_out, ldo, 0, stream_);
+        phase_end(kPhScatter);
+    }
     HIPCHK(hipGetLastError());
     if (sync) HIPCHK(hipStreamSynchronize(stream_));
     return BBFMM_OK;
@@ -1496,6 +1592,7 @@ int FmmTree::partition_subset_finish(const double *d_coarse, const int64_t *idx,
         HIPCHK(hipStreamWaitEvent(stream_, ev_comm_, 0));
     }
     phase_begin();
+    mp_current_k_ = 0; // (M gets the summed coarse prefix)
     if (cnt > 0)
         HIPCHK(hipMemcpyAsync(d_M_.p, d_coarse, static_cast<size_t>(cnt) * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     phase_end(kPhM2M);
@@ -1526,6 +1623,7 @@ int FmmTree::partition_finish_core(const double *d_coarse, hipStream_t comm_stre
         HIPCHK(hipEventRecord(ev_comm_, comm_stream));
         HIPCHK(hipStreamWaitEvent(stream_, ev_comm_, 0));
     }
+    mp_current_k_ = 0; // (M gets the summed coarse prefix)
     phase_begin();
     for (int j = 0; j < k && cnt > 0; ++j)
         HIPCHK(hipMemcpyAsync(d_M_.p + static_cast<size_t>(j) * C * cheb_.n_pad, d_coarse + static_cast<size_t>(j) * cnt,
@@ -1780,6 +1878,11 @@ int FmmTree::debug_get_coefficients(char which, int k, double *out) {
     const int64_t C = tree_.n_cells();
     const int n = ops_.n, n_pad = cheb_.n_pad;
     HIPCHK(hipStreamSynchronize(stream_));
+    if (which == 'P' || which == 'p') { // Mp, whole rows with their pads: k x C x m2l_npar_
+        if (!m2l_pairs_ || !d_Mp_.p) return fail(BBFMM_BAD_ARGUMENT, "no multipoles in the parity basis on this handle");
+        HIPCHK(hipMemcpy(out, d_Mp_.p, static_cast<size_t>(k) * C * m2l_npar_ * sizeof(double), hipMemcpyDeviceToHost));
+        return BBFMM_OK;
+    }
     HIPCHK(hipMemcpy2D(out, n * sizeof(double), src, n_pad * sizeof(double), n * sizeof(double),
                        static_cast<size_t>(k) * C, hipMemcpyDeviceToHost));
     return BBFMM_OK;

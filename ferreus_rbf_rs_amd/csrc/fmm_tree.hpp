@@ -288,7 +288,9 @@ class FmmTree {
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
     // M, L: n_cells x n (cell-major, one rhs).  L is accumulated into.
     int debug_apply_m2l_tables_host(const double *M, double *L) const;
+    // which: 'M' / 'L' (k x C x n, the pads dropped) or 'P' (Mp, k x C x debug_m2l_parity_len(), whole rows with their pads)
     int debug_get_coefficients(char which, int k, double *out);
+    int debug_m2l_parity_len() const { return m2l_pairs_ ? m2l_npar_ : 0; }
     int debug_partition_upward_counts(int64_t *counts_out, uint8_t *reads_out, int64_t *info_out) const;
 
   private:
@@ -309,7 +311,8 @@ class FmmTree {
     int leaf_pass(const TargetSet &ts, int k, bool with_grads, bool fixed_plan = false);
     int leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStream_t st, int parts, bool wx_done = false,
                        bool fixed_plan = false);
-    int leaf_pass_far(const TargetSet &ts, int k, bool with_grads);
+    // user_out / ldo: L2P writes the potentials in the caller's order there (ts.perm), no scatter pass behind it
+    int leaf_pass_far(const TargetSet &ts, int k, bool with_grads, double *user_out = nullptr, int64_t ldo = 0);
     int build_target_set(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                          std::vector<int32_t> *leaves_out = nullptr);
     // the same on the device (targets.hip) for batches of at least device_targets_min_ rows
@@ -416,6 +419,21 @@ class FmmTree {
     std::vector<int32_t> m2l_s2_node_;   // two axes: per column of Lp the up to four nodes of its orbit (-1: none) ...
     std::vector<int8_t> m2l_s2_sign_;    // ... their signs ...
     std::vector<int8_t> m2l_s2_part_;    // ... and its part (2 (odd along x) + (odd along y)); -1: padding
+    // The changes of basis inside M2M and L2L (BBFMM_FUSED_PASSES, read per handle).  Bit 1: the 3-D M2M
+    // kernel writes its children's rows of Mp; bit 2: the 3-D L2L kernel takes the M2L part from Lp; bit 4 (needs bit 2): Lp
+    // is not cleared when no stage-2 launch of the matvec splits its contraction; bit 8: L2P of a matvec at the sources writes
+    // the caller's order, no scatter pass.  0: the standalone passes everywhere.
+    unsigned fused_mask_ = 15;
+    int mp_current_k_ = 0;               // right-hand sides whose Mp a whole, fused upward pass wrote for the present M (0: none)
+    bool lp_pending_ = false;            // downward_m2l left the M2L part in Lp: downward_tail runs the fused L2L
+    bool fused_flags_ok_ = false;        // d_has_m2l_ / d_has_x_ describe the whole-tree plan
+    M2lParityRowArgs mp_row_args() const;
+    M2lUnparityRowArgs lp_row_args() const;
+    bool m2m_fusable() const;            // the whole-tree upward pass may write Mp
+    bool l2l_fusable(int k) const;       // the whole-tree downward pass of k right-hand sides may leave the M2L part in Lp
+    DevBuf<uint8_t> d_has_m2l_, d_has_x_; // per cell: in a stage-2 tile of some batch / receives P2L
+    DevBuf<int32_t> d_top_cells_;        // the cells of levels 0 and 1: no M2M launch has them as children
+    int n_top_cells_ = 0;
     // partition
     int part_rank_ = 0, part_world_ = 1;
     std::vector<int64_t> part_rows_, part_bounds_;

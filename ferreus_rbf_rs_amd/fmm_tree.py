@@ -651,7 +651,12 @@ class FmmTree:
 
     def debug_get_coefficients(self, which: str, k: int) -> np.ndarray:
         s = self.stats()
-        out = np.zeros((k, s.n_cells, s.n_nodes))
+        n = s.n_nodes
+        if which in ("P", "p"):  # Mp: the multipoles in stage 1's parity basis, whole rows with their pads
+            ln = ctypes.c_int32(0)
+            self._raise(self._lib.bbfmm_debug_m2l_parity_len(self._h, ctypes.byref(ln)))
+            n = ln.value
+        out = np.zeros((k, s.n_cells, n))
         self._raise(self._lib.bbfmm_debug_get_coefficients(self._h, which.encode()[0:1], k,
                                                            out.ctypes.data))
         return out

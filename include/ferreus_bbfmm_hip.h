@@ -793,6 +793,9 @@ int bbfmm_debug_reference_vectors(const bbfmm_handle *h, int32_t *out, int32_t *
  * the host as k x n_cells x n (rhs-major, cell-major), i.e. column c + j*n_cells of the
  * reference's n x (C*K) matrices (bbfmm.rs:234-242).  Per-phase parity checks. */
 int bbfmm_debug_get_coefficients(bbfmm_handle *h, char which, int32_t k, double *out);
+/* 'P': the multipoles in stage 1's parity basis as the stage reads them, k x n_cells x len with the pads of every row;
+ * len from bbfmm_debug_m2l_parity_len (0: the handle keeps none).  Debug only. */
+int bbfmm_debug_m2l_parity_len(const bbfmm_handle *h, int32_t *len);
 
 /* ------------------------------------------------------------------ iterative solvers
  * ferreus_rbf/src/iterative_solvers.rs: host FGMRES / stationary Schwarz
