@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libferreus_bbfmm_hip.so")
 
-HOST_SOURCES = ["tree.cpp", "operators.cpp", "fmm_tree.cpp", "fmm_m2l_tables.cpp", "fmm_plans.cpp", "device_group.cpp", "capi.cpp", "solver.cpp", "ddm.cpp", "ddm_solver.cpp", "schwarz.cpp", "interpolant.cpp", "closure_triangulate.cpp"]
+HOST_SOURCES = ["tree.cpp", "operators.cpp", "fmm_tree.cpp", "fmm_m2l_tables.cpp", "fmm_m2l_shared_basis.cpp", "fmm_m2l_debug.cpp", "fmm_plans.cpp", "device_group.cpp", "capi.cpp", "solver.cpp", "ddm.cpp", "ddm_solver.cpp", "schwarz.cpp", "interpolant.cpp", "closure_triangulate.cpp"]
 HIP_SOURCES = ["device_l2p.hip", "device_p2p.hip", "device_wx.hip", "device_p2m.hip", "device_m2l.hip", "device_transfer.hip", "device_gather.hip", "device_selftest.hip",  # longest first
                "ddm_kernels.hip", "targets.hip", "schwarz_kernels.hip", "tree_device.hip", "tree_lists_device.hip", "isosurface.hip", "isosurface_finish.hip", "isosurface_closure.hip", "isosurface_intersect.hip", "isosurface_follow.hip", "interpolant_terms.hip", "field_program.hip"]
 HEADERS = ["morton.hpp", "tree.hpp", "parallel.hpp", "kernels.hpp", "operators.hpp", "device.hpp", "device_common.hpp", "device_direct.hpp", "m2l_basis_rows.hpp",

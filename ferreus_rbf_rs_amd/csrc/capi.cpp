@@ -2061,6 +2061,20 @@ int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64
     return BBFMM_OK;
 }
 
+// Digests of the integer M2L tables, one per family, and the per-level flop counts (FmmTree::debug_m2l_table_digests).
+int bbfmm_debug_m2l_table_digests(const bbfmm_handle *h, uint64_t *digests, int32_t cap, int32_t *n_out, double *flops_level,
+                                  int32_t flops_cap, int32_t *n_levels_out) {
+    if (!h || !n_out) return BBFMM_BAD_ARGUMENT;
+    std::vector<uint64_t> v;
+    h->tree.debug_m2l_table_digests(&v);
+    *n_out = static_cast<int32_t>(v.size());
+    if (digests) std::copy(v.begin(), v.begin() + std::min<int32_t>(cap, *n_out), digests);
+    const std::vector<double> &fl = h->tree.m2l_flops_level();
+    if (n_levels_out) *n_levels_out = static_cast<int32_t>(fl.size());
+    if (flops_level) std::copy(fl.begin(), fl.begin() + std::min<int32_t>(flops_cap, static_cast<int32_t>(fl.size())), flops_level);
+    return BBFMM_OK;
+}
+
 // Debug only: parts into which the handle's most recent parity-basis stage-2 launch split the contraction (0: no launch yet).
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit) {
     if (!h || !ksplit) return BBFMM_BAD_ARGUMENT;

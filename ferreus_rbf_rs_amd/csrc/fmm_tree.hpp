@@ -283,6 +283,24 @@ class FmmTree {
     // pair, listed by its leader) or 2 (y pair), its slot offset, its partner's slot offset (-1: a single), its rank, then
     // the d components of t.
     void debug_m2l_pairs_axes_stage2(std::vector<int32_t> *out) const;
+    // Test hook: one 64-bit FNV-1a digest per family of the integer tables build_m2l_tables() produces, for host-only handles
+    // (upload() releases cslot and the zero lists of the others).  Every vector is hashed as its length, then its elements;
+    // no floating-point value is hashed.  The families, in the order of *out:
+    //   0 scalars: m2l_pairs_, m2l_pairs2_, m2l_axes_, m2l_s2_axes_, m2l_ne_, m2l_no_, m2l_ne16_, m2l_npar_, m2l_s1_off_,
+    //     m2l_s_ee_, m2l_s_eo_, m2l_s1_block_, m2l_slot_t_, m2l_max_blocks_, m2l_work_, m2l_s2_work_, the six fields of
+    //     m2l_s2_plan_, cbuf_batch_len_, cbuf_total_len_
+    //   1 partners and orbits: m2l_partner_, m2l_partner_y_, m2l_par_node_, m2l_par_sign_, m2l_s2_node_, m2l_s2_sign_, m2l_s2_part_
+    //   2 .. 4 per HostM2lClass, over m2l_host_ and then m2l_variants_:
+    //     2 lists and marks: src_tv, src_pair, src_kind, src_row0, src_row1, tgt_tv, tgt_off, tgt_pair, tgt_kind, then level,
+    //       octant, n_rows, r_pad16, n_t, k_pad, yb0, pad_cols, kp, kpy, tgt_pad
+    //     3 row tables: row_dst, row_dst2, blk_t0, row_tpos, row_off, row_tpos2, row_off2
+    //     4 cells, cbase, cslot
+    //   5 m2l_tiles1_h_, m2l_tile_idx1_h_
+    //   6 m2l_tiles_h_, m2l_tiles2_h_, m2l_qlist_h_
+    //   7 m2l_batches_, m2l_batch_of_class_, m2l_group_ops_, m2l_zero_h_, m2l_zero_ptr_
+    static constexpr int kM2lDigestFamilies = 8;
+    void debug_m2l_table_digests(std::vector<uint64_t> *out) const;
+    const std::vector<double> &m2l_flops_level() const { return m2l_flops_level_; } // per level: sum over its V pairs of 4 n r
     // Test hook: parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet).
     int debug_m2l_s2_last_ksplit() const { return m2l_s2_last_ksplit_; }
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
@@ -298,6 +316,40 @@ class FmmTree {
     int hip_fail(hipError_t e, const char *what);
     int upload();
     int build_m2l_tables();
+    // The stages of build_m2l_tables(), in the order it calls them (fmm_m2l_tables.cpp: the structs, and per stage what it
+    // reads and which members it writes; DESIGN.md section 5 has the map).
+    struct M2lSwitches;    // the BBFMM_M2L_* switches of this handle
+    struct M2lLists;       // per octant class: the ordered source / target lists, their inverse maps, the target marks; the batch of every (level, class)
+    struct M2lSlotLayout;  // slot offsets and lengths of the target classes of one level
+    struct M2lPairSplit;   // positions of a list: x pairs, y pairs, singles
+    struct M2lStage1Marks; // pair marks and stacked rows of a source list
+    struct M2lTargetOrder; // a candidate order of the target lists with its slot layouts and work
+    struct M2lLevel;       // (level, first class, lists, layout): what the per-level stages work on
+    struct M2lBuildState;  // what the levels accumulate for the launch lists
+    void clear_m2l_tables();
+    void init_m2l_parity_basis(const M2lSwitches &sw);
+    std::vector<int32_t> m2l_reflection_partners(int axis) const;
+    M2lPairSplit m2l_split_pairs(const std::vector<int> &list, bool with_y) const;
+    void m2l_order_stage1(bool with_y, std::vector<int> *list, std::vector<int> *carry) const;
+    M2lStage1Marks m2l_mark_stage1(int level, int axes, const std::vector<int> &tvs) const;
+    M2lTargetOrder m2l_target_order(const std::vector<std::vector<int>> &tgt, int axes) const;
+    M2lSlotLayout m2l_slot_layout(int level, const M2lTargetOrder &order) const;
+    std::vector<uint8_t> m2l_classes_present(int level) const;
+    void choose_m2l_stage1_axes(const M2lSwitches &sw, M2lLists *lists);
+    void choose_m2l_stage2_axes(const M2lSwitches &sw, M2lLists *lists, std::vector<M2lSlotLayout> *layouts);
+    void plan_m2l_batches(const M2lSwitches &sw, const std::vector<M2lSlotLayout> &layouts, M2lLists *lists);
+    int build_m2l_level(const M2lLevel &lv, const M2lSwitches &sw, M2lBuildState *st);
+    void sort_m2l_class_cells(const M2lLevel &lv, M2lBuildState *st);
+    bool m2l_stage1_rows(const M2lLevel &lv, int o, const std::vector<int> &tvs, HostM2lClass *hc);
+    int fill_m2l_classes(const M2lLevel &lv);
+    void fill_m2l_cslot(const M2lLevel &lv, M2lBuildState *st);
+    void m2l_zero_segments(const M2lLevel &lv, M2lBuildState *st) const;
+    void m2l_stage2_tiles(const M2lLevel &lv);
+    bool m2l_restricted_operator(const M2lLevel &lv, const HostM2lClass &hc, const std::vector<int> &tvs, const std::vector<int> &keep,
+                                 size_t first, size_t count, HostM2lClass *v);
+    int m2l_group_operators(const M2lLevel &lv, M2lBuildState *st);
+    int m2l_boundary_variants(const M2lLevel &lv, const M2lSwitches &sw, M2lBuildState *st);
+    int finish_m2l_launch_lists(const M2lLists &lists, const M2lBuildState &st);
     void fill_m2l_operator_arrays(const HostM2lClass &hc, std::vector<double> *vt_all,
                                   std::vector<double> *u_all) const;
     void fill_m2l_operator_arrays(const HostM2lClass &hc, double *vt_all, double *u_all) const;

@@ -1,5 +1,6 @@
 // Internals shared by the translation units of FmmTree (fmm_tree.cpp: creation, upload, passes, entry points;
-// fmm_m2l_tables.cpp: the stacked M2L tables and the shared-basis extension; fmm_plans.cpp: target sets, restricted
+// fmm_m2l_tables.cpp: the stacked M2L tables; fmm_m2l_shared_basis.cpp: the shared-basis extension; fmm_m2l_debug.cpp: the
+// read-only test hooks of the tables; fmm_plans.cpp: target sets, restricted
 // downward plans, target subsets, partitions): error macros, the device-buffer member templates, small helpers.
 #pragma once
 #include "fmm_tree.hpp"

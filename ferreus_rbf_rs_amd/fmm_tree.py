@@ -643,6 +643,20 @@ class FmmTree:
             i += 7 + n_blk + ne * (d + 3)
         return info, ops
 
+    M2L_DIGEST_FAMILIES = ("scalars", "partners_orbits", "class_lists", "class_rows", "class_cells", "tiles1", "tiles2", "batches")
+
+    def debug_m2l_table_digests(self):
+        """(digests, flops_level) of a host_only handle: one 64-bit FNV-1a digest per family of the integer M2L tables, as a
+        dict family -> hex string in the order of M2L_DIGEST_FAMILIES (csrc/fmm_tree.hpp lists what each family holds), and
+        the M2L flop count of every level, which is a sum in a fixed order and is compared as a value."""
+        n, nl = ctypes.c_int32(), ctypes.c_int32()
+        self._raise(self._lib.bbfmm_debug_m2l_table_digests(self._h, None, 0, ctypes.byref(n), None, 0, ctypes.byref(nl)))
+        assert n.value == len(self.M2L_DIGEST_FAMILIES)
+        dig, fl = np.zeros(n.value, dtype=np.uint64), np.zeros(max(nl.value, 1))
+        self._raise(self._lib.bbfmm_debug_m2l_table_digests(self._h, dig.ctypes.data, n.value, ctypes.byref(n), fl.ctypes.data,
+                                                            nl.value, ctypes.byref(nl)))
+        return {k: f"{int(v):016x}" for k, v in zip(self.M2L_DIGEST_FAMILIES, dig)}, [float(v) for v in fl[:nl.value]]
+
     def debug_m2l_s2_last_ksplit(self) -> int:
         """Parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet)."""
         ks = ctypes.c_int32()

@@ -773,6 +773,12 @@ int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int6
 int bbfmm_debug_m2l_pairs_axes(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
 int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
 int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
+/* One 64-bit FNV-1a digest per family of the integer M2L tables (FmmTree::debug_m2l_table_digests lists the families and
+ * their order), for BBFMM_FLAG_HOST_ONLY handles: *n_out = number of families, digests (capacity cap, may be NULL)
+ * receives the first min(cap, *n_out).  flops_level (capacity flops_cap, may be NULL) receives the M2L flop count of
+ * every level, *n_levels_out (may be NULL) their number: sums in a fixed order, compared as values, not hashed. */
+int bbfmm_debug_m2l_table_digests(const bbfmm_handle *h, uint64_t *digests, int32_t cap, int32_t *n_out, double *flops_level,
+                                  int32_t flops_cap, int32_t *n_levels_out);
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit); /* debug only */
 
 /* The Morton primitives of csrc/morton.hpp as the host tree build uses them (morton.rs:58-263; the
