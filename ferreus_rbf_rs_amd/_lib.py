@@ -209,6 +209,11 @@ SIGNATURES = {
     "bbfmm_debug_interpolant_terms": (ctypes.c_int, [c_i32, c_i32, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64]),
     "bbfmm_evaluate_interpolant": (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_f64,
                                                   c_p, c_i64, c_p, c_i64, c_p]),
+    "bbfmm_evaluate_device": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "bbfmm_evaluate_grid": (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "bbfmm_evaluate_grid_stats": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_debug_grid_coords": (ctypes.c_int, [c_i32, c_p, c_i64, c_i64, c_p, c_i64]),
+    "bbfmm_debug_split_runs": (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_i64, c_p]),
 }
 
 
@@ -233,6 +238,21 @@ class InterpolantTerms(ctypes.Structure):
     _fields_ = [("size", c_i64), ("d", c_i32), ("polynomial_degree", c_i32), ("k", c_i32), ("has_affine", c_i32),
                 ("coefficients", ctypes.c_void_p), ("ld_coefficients", c_i64), ("translation", c_f64 * 3), ("scale", c_f64 * 3),
                 ("B", c_f64 * 9), ("b", c_f64 * 3)]
+
+
+class Grid(ctypes.Structure):
+    """bbfmm_grid"""
+    _fields_ = [("size", c_i64), ("d", c_i32), ("reserved", c_i32), ("shape", c_i64 * 3), ("origin", c_f64 * 3),
+                ("steps", c_f64 * 9)]
+
+
+class EvaluateOptions(ctypes.Structure):
+    """bbfmm_evaluate_options"""
+    _fields_ = [("size", c_i64), ("batch_independent", c_i32), ("max_job_targets", c_i32), ("batch_bytes", c_i64),
+                ("outputs_on_device", c_i32)]
+
+
+GRID_STATS = ("nodes", "slabs", "leaf_runs", "jobs", "largest_job", "w_jobs")
 
 
 class FieldOperand(ctypes.Structure):

@@ -317,7 +317,8 @@ int FmmTree::ensure_leaf_lookup() {
 // points_to_leaves, the stable grouping by leaf and the coordinate gather as kernels (targets.hip); the
 // host keeps the per-leaf part (M2P jobs from the W lists).  Same target set as the host path.
 int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
-                                     std::vector<int32_t> *leaves_out, const double *const *d_x) {
+                                     std::vector<int32_t> *leaves_out, const double *const *d_x, int32_t cap,
+                                     TargetSetStats *stats) {
     const HostTree &t = tree_;
     CHK(ensure_leaf_lookup());
     const int64_t C = t.n_cells();
@@ -327,7 +328,7 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
     const size_t sm = static_cast<size_t>(m);
     const size_t o_x = 0, o_cell = o_x + (d_x ? 0 : up(sm * 8 * d_)), o_sorted = o_cell + up(sm * 4), o_heads = o_sorted + up(sm * 4),
                  o_scal = o_heads + up(sm), o_temp = o_scal + 256;
-    const size_t temp_bytes = group_targets_temp_bytes(m, end_bit);
+    const size_t temp_bytes = std::max(group_targets_temp_bytes(m, end_bit), cap > 0 ? split_runs_temp_bytes(std::min<int64_t>(m, C)) : size_t(0));
     const size_t need = o_temp + temp_bytes;
     if (need > d_tscratch_.n) {
         dfree(&d_tscratch_);
@@ -349,11 +350,11 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
     int32_t *d_runs = reinterpret_cast<int32_t *>(base + o_scal + 8);
     HIPCHK(hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), stream_));
     ts->m = m;
-    const size_t cap = static_cast<size_t>(std::min<int64_t>(m, C));
+    const size_t run_cap = static_cast<size_t>(std::min<int64_t>(m, C));
     CHK(talloc(&ts->perm, sm));
-    CHK(talloc(&ts->job_cell, cap));
-    CHK(talloc(&ts->tgt_begin, cap));
-    CHK(talloc(&ts->tgt_end, cap));
+    CHK(talloc(&ts->job_cell, run_cap));
+    CHK(talloc(&ts->tgt_begin, run_cap));
+    CHK(talloc(&ts->tgt_end, run_cap));
     for (int a = 0; a < 3; ++a) {
         if (a < d_) {
             CHK(talloc(&ts->xyz[a], sm));
@@ -383,14 +384,56 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
                                                   " lies outside the tree extents");
     }
     ts->n_jobs = scal.runs;
+    if (cap > 0 && scal.runs > 0) { // jobs of at most cap targets (targets.hpp): every kernel of the leaf pass takes (cell, begin, end) per job
+        const int64_t n_runs = scal.runs;
+        const size_t jcap = static_cast<size_t>(split_jobs_capacity(n_runs, m, cap));
+        DevBuf<int32_t> cnt, offs, jc2, tb2, te2;
+        int32_t n_cut = 0;
+        int rc = talloc(&cnt, static_cast<size_t>(n_runs));
+        if (rc == BBFMM_OK) rc = talloc(&offs, static_cast<size_t>(n_runs));
+        if (rc == BBFMM_OK) rc = talloc(&jc2, jcap);
+        if (rc == BBFMM_OK) rc = talloc(&tb2, jcap);
+        if (rc == BBFMM_OK) rc = talloc(&te2, jcap);
+        if (rc == BBFMM_OK) {
+            const int src = split_runs(ts->job_cell.p, ts->tgt_begin.p, ts->tgt_end.p, n_runs, cap, cnt.p, offs.p, jc2.p, tb2.p, te2.p,
+                                       static_cast<int64_t>(jcap), d_runs, base + o_temp, temp_bytes, stream_);
+            if (src != 0) rc = hip_fail(static_cast<hipError_t>(src), "cut the target runs into jobs");
+        }
+        if (rc == BBFMM_OK) {
+            hipError_t e = hipMemcpyAsync(&n_cut, d_runs, sizeof(int32_t), hipMemcpyDeviceToHost, stream_);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+            if (e != hipSuccess) rc = hip_fail(e, "read the number of cut jobs");
+        }
+        if (rc == BBFMM_OK && (n_cut < n_runs || static_cast<size_t>(n_cut) > jcap))
+            rc = fail(BBFMM_DEVICE_ERROR, "cut of the target runs: job count out of range");
+        if (rc != BBFMM_OK) { // nothing of the cut outlives a failed call (buffers past the arena are real allocations)
+            (void)hipStreamSynchronize(stream_);
+            dfree(&cnt);
+            dfree(&offs);
+            dfree(&jc2);
+            dfree(&tb2);
+            dfree(&te2);
+            return rc;
+        }
+        dfree(&cnt);
+        dfree(&offs);
+        dfree(&ts->job_cell);
+        dfree(&ts->tgt_begin);
+        dfree(&ts->tgt_end);
+        ts->job_cell = jc2;
+        ts->tgt_begin = tb2;
+        ts->tgt_end = te2;
+        ts->n_jobs = n_cut;
+    }
+    if (stats) stats->runs = scal.runs, stats->jobs = ts->n_jobs, stats->largest = 0, stats->w_jobs = 0;
     std::vector<int32_t> wtb, wte;
     std::vector<int64_t> wb, we;
-    if (leaves_out || !t.w.idx.empty()) {
-        const size_t nj = static_cast<size_t>(scal.runs);
+    if (leaves_out || !t.w.idx.empty() || stats) {
+        const size_t nj = static_cast<size_t>(ts->n_jobs);
         std::vector<int32_t> jc(nj), tb(nj), te(nj);
         if (nj) {
             HIPCHK(hipMemcpyAsync(jc.data(), ts->job_cell.p, nj * 4, hipMemcpyDeviceToHost, stream_));
-            if (!t.w.idx.empty()) {
+            if (!t.w.idx.empty() || stats) {
                 HIPCHK(hipMemcpyAsync(tb.data(), ts->tgt_begin.p, nj * 4, hipMemcpyDeviceToHost, stream_));
                 HIPCHK(hipMemcpyAsync(te.data(), ts->tgt_end.p, nj * 4, hipMemcpyDeviceToHost, stream_));
             }
@@ -398,8 +441,11 @@ int FmmTree::build_target_set_device(const double *x, int64_t m, int64_t ldx, Ta
         }
         if (!t.w.idx.empty())
             for (size_t j = 0; j < nj; ++j) add_w_jobs(t, jc[j], tb[j], te[j], &wtb, &wte, &wb, &we, deterministic_);
-        if (leaves_out) leaves_out->swap(jc);
+        if (stats)
+            for (size_t j = 0; j < nj; ++j) stats->largest = std::max<int64_t>(stats->largest, te[j] - tb[j]);
+        if (leaves_out) leaves_out->swap(jc); // (cell of every job: a leaf repeats when cap cut it)
     }
+    if (stats) stats->w_jobs = static_cast<int64_t>(wtb.size());
     ts->n_w_jobs = static_cast<int>(wtb.size());
     CHK(tupload(&ts->w_tgt_begin, wtb));
     CHK(tupload(&ts->w_tgt_end, wte));

@@ -1,5 +1,6 @@
 // FmmTree host orchestration: creation, upload, the passes and the entry points.  See fmm_tree.hpp.
 #include "fmm_tree_impl.hpp"
+#include "interpolant_terms.hpp"
 
 namespace bbfmm {
 
@@ -1489,6 +1490,79 @@ int FmmTree::evaluate_leaves_device(const double *d_x0, const double *d_x1, cons
         (void)hipStreamSynchronize(stream_);
     }
     free_target_set(&ts);
+    const int arc = arena_end();
+    return rc == BBFMM_OK ? arc : rc;
+}
+
+int FmmTree::evaluate_device(const double *d_x, int64_t m, int64_t ldx, const InterpolantTerms *terms, double *d_values, int64_t ldo,
+                             double *d_grad, int64_t ldg, bool batch_independent, int32_t max_job_targets, int64_t *bad_point_index,
+                             TargetSetStats *stats) {
+    if (stats) *stats = TargetSetStats();
+    if (host_only_) return fail(BBFMM_DEVICE_ERROR, "handle was created with BBFMM_FLAG_HOST_ONLY");
+    if (nrhs_ < 1 || !have_locals_) return fail(BBFMM_BAD_ARGUMENT, "set_local_coefficients must be called first");
+    if (multipoles_partial_) return fail(BBFMM_BAD_ARGUMENT, kPartialMultipoles);
+    const int k = nrhs_;
+    if (m < 0 || max_job_targets < 0 || (m > 0 && (!d_x || !d_values || ldx < m || ldo < m || (d_grad && ldg < m))))
+        return fail(BBFMM_BAD_ARGUMENT, "bad device target/output arrays");
+    if (m >= (int64_t(1) << 31)) return fail(BBFMM_BAD_ARGUMENT, "more than 2^31-1 target points");
+    if (terms && (terms->d != d_ || terms->k != k)) return fail(BBFMM_BAD_ARGUMENT, "the terms must have the tree's dimension and the column count of the weights");
+    if (d_grad && !kernel_supports_gradients(kernel_.id))
+        return fail(BBFMM_KERNEL_NO_GRADIENTS, "FMM evaluation failed: gradient evaluation requested but kernel does not support gradients");
+    if (m == 0) return BBFMM_OK;
+    part_pending_k_ = 0;
+    last_eval_at_sources_ = last_eval_rows_of_sources_ = false;
+    const int nb = terms ? terms_basis_size(terms->d, terms->degree) : 0;
+    const bool affine = terms && terms->has_affine;
+    const size_t sm = static_cast<size_t>(m);
+    const double *x[3] = {d_x, d_ > 1 ? d_x + ldx : nullptr, d_ > 2 ? d_x + 2 * ldx : nullptr};
+    TargetSet ts;
+    DevBuf<double> xt, lam;
+    InterpolantTerms t;
+    arena_begin();
+    int rc = BBFMM_OK;
+    const double *q[3] = {x[0], x[1], x[2]};
+    if (terms) {
+        t = *terms;
+        if (nb > 0) { // the coefficients packed on the device
+            std::vector<double> packed(static_cast<size_t>(nb) * k);
+            for (int c = 0; c < k; ++c)
+                for (int j = 0; j < nb; ++j) packed[static_cast<size_t>(c) * nb + j] = terms->lambda[static_cast<size_t>(c) * terms->ld_lambda + j];
+            rc = tupload(&lam, packed);
+            t.lambda = lam.p;
+            t.ld_lambda = nb;
+        }
+        if (rc == BBFMM_OK && affine) { // the tree is asked at x B + b
+            rc = talloc(&xt, sm * d_);
+            if (rc == BBFMM_OK) {
+                double *y[3] = {xt.p, d_ > 1 ? xt.p + sm : nullptr, d_ > 2 ? xt.p + 2 * sm : nullptr};
+                if (terms_affine_soa_device(t, x[0], x[1], x[2], m, y[0], y[1], y[2], stream_) != 0)
+                    rc = fail(BBFMM_DEVICE_ERROR, "the trend's map of the device targets failed");
+                for (int a = 0; a < 3; ++a) q[a] = y[a];
+            }
+        }
+    }
+    if (rc == BBFMM_OK) rc = build_target_set_device(nullptr, m, m, &ts, bad_point_index, nullptr, q, max_job_targets, stats);
+    if (rc == BBFMM_OK) rc = talloc(&ts.out, static_cast<size_t>(k) * sm);
+    if (rc == BBFMM_OK && d_grad) rc = talloc(&ts.grad, static_cast<size_t>(k) * d_ * sm);
+    if (rc == BBFMM_OK) rc = leaf_pass(ts, k, d_grad != nullptr, batch_independent);
+    if (rc == BBFMM_OK) {
+        phase_begin();
+        launch_scatter_output(ts.out.p, m, k, ts.perm.p, d_values, ldo, 0, stream_);
+        if (d_grad) launch_scatter_output(ts.grad.p, m, k * d_, ts.perm.p, d_grad, ldg, 0, stream_);
+        phase_end(kPhScatter);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = hip_fail(e, "scatter device-target values");
+    }
+    if (rc == BBFMM_OK && terms && (nb > 0 || (affine && d_grad)) &&
+        terms_field_soa_device_k(t, x[0], x[1], x[2], m, d_values, ldo, d_grad, ldg, stream_) != 0)
+        rc = fail(BBFMM_DEVICE_ERROR, "the terms kernel failed at the device targets");
+    if (stream_ || rc == BBFMM_OK) { // the target set's arena buffers are reused by the next call
+        const hipError_t e = hipStreamSynchronize(stream_);
+        if (rc == BBFMM_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    }
+    free_target_set(&ts);
+    dfree(&xt);
+    dfree(&lam);
     const int arc = arena_end();
     return rc == BBFMM_OK ? arc : rc;
 }

@@ -147,6 +147,10 @@ struct DownwardPlan {
     DevBuf<uint16_t> d_qlist;
 };
 
+struct TargetSetStats { // of one build_target_set_device
+    int64_t runs = 0, jobs = 0, largest = 0, w_jobs = 0; // leaves with targets, jobs after the cut, targets of the largest job, M2P jobs
+};
+
 struct SubsetPlan { // cached target subset of bbfmm_fast_matrix_vector_product (rbf.rs:119-133)
     uint64_t key = 0;
     int64_t n_idx = 0;
@@ -157,6 +161,7 @@ struct SubsetPlan { // cached target subset of bbfmm_fast_matrix_vector_product 
 };
 
 class DeviceGroup;
+struct InterpolantTerms; // interpolant_terms.hpp
 
 class FmmTree {
     friend class DeviceGroup; // one handle over several devices (device_group.hpp): drives the parts' passes directly
@@ -184,6 +189,18 @@ class FmmTree {
     // differently; every other caller keeps the default and its bits.
     int evaluate_leaves_device(const double *d_x0, const double *d_x1, const double *d_x2, int64_t m, double *d_out,
                                int64_t *bad_point_index, double *d_grad = nullptr, bool batch_independent = false);
+    // The general pass at device targets: Leaves mode (after set_local_coefficients) for all k = nrhs columns at m targets
+    // given as device SoA, column a at d_x + a * ldx.  Values m x k column-major to d_values (leading dimension ldo), with
+    // d_grad the gradients too, component a of column c in column c * d + a (leading dimension ldg): the layout of the host
+    // entries, in the caller's row order, on the handle's stream, which is idle on return.  terms (may be null; k columns,
+    // HOST coefficients): the trend's map of the targets runs before the pass, trend_gradients and polynomial_terms behind
+    // it (interpolant_terms.hpp).  batch_independent: as for evaluate_leaves_device.  max_job_targets > 0: the jobs of the
+    // leaf pass hold at most that many targets (build_target_set_device); 0: one job per leaf.  stats (may be null): the
+    // target set of this call.
+    int evaluate_device(const double *d_x, int64_t m, int64_t ldx, const InterpolantTerms *terms, double *d_values, int64_t ldo,
+                        double *d_grad, int64_t ldg, bool batch_independent, int32_t max_job_targets, int64_t *bad_point_index,
+                        TargetSetStats *stats = nullptr);
+    int nrhs() const { return nrhs_; }
     bool supports_gradients() const;
     int evaluate(const double *w, int64_t rows, int k, int64_t ldw, const double *x, int64_t m, int64_t ldx,
                  double *out, int64_t ldo, double *grad, int64_t ldg, bool with_grads, bool leaves_only,
@@ -369,8 +386,11 @@ class FmmTree {
                          std::vector<int32_t> *leaves_out = nullptr);
     // the same on the device (targets.hip) for batches of at least device_targets_min_ rows
     // d_x (3 device arrays): targets already on the device, x unused
+    // cap > 0: every run (a leaf's targets) is cut into jobs of at most cap targets (targets.hpp split_runs), the W jobs
+    // then come per cut job; cap = 0: one job per leaf, the target set as it always was.  stats: what was built.
     int build_target_set_device(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
-                                std::vector<int32_t> *leaves_out, const double *const *d_x = nullptr);
+                                std::vector<int32_t> *leaves_out, const double *const *d_x = nullptr, int32_t cap = 0,
+                                TargetSetStats *stats = nullptr);
     int ensure_leaf_lookup();
     int build_target_set_host(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                               std::vector<int32_t> *leaves_out);

@@ -176,7 +176,40 @@ __global__ __launch_bounds__(kThreads) void field_soa_kernel(InterpolantTerms t,
     }
 }
 
+// t.k columns: value column c at vals + c * ldv, gradient column c * t.d + a at grad + (c * t.d + a) * ldg; per point and
+// column the arithmetic of field_soa_kernel (the monomials are formed once per point)
+__global__ __launch_bounds__(kThreads) void field_soa_k_kernel(InterpolantTerms t, const double *__restrict__ x0,
+                                                               const double *__restrict__ x1, const double *__restrict__ x2, int64_t m,
+                                                               double *__restrict__ vals, int64_t ldv, double *__restrict__ grad,
+                                                               int64_t ldg) {
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < m; i += (int64_t)gridDim.x * kThreads) {
+        const double p[3] = {x0[i], t.d > 1 ? x1[i] : 0.0, t.d > 2 ? x2[i] : 0.0};
+        double mono[kMaxMonomials], dm[kMaxMonomials][3];
+        const int nb = monomials_and_gradients(t, p, mono, grad ? dm : nullptr);
+        for (int c = 0; c < t.k; ++c) {
+            double v = vals[c * ldv + i], g[3] = {0, 0, 0};
+            if (grad) {
+                for (int a = 0; a < t.d; ++a) g[a] = grad[(c * t.d + a) * ldg + i];
+                if (t.has_affine) trend_gradient_column(t, g);
+            }
+            if (nb > 0) polynomial_column(t, nb, mono, dm, c, &v, grad ? g : nullptr);
+            vals[c * ldv + i] = v;
+            if (grad)
+                for (int a = 0; a < t.d; ++a) grad[(c * t.d + a) * ldg + i] = g[a];
+        }
+    }
+}
+
 } // namespace
+
+int terms_field_soa_device_k(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *vals,
+                             int64_t ldv, double *grad, int64_t ldg, hipStream_t stream) {
+    if (m <= 0) return 0;
+    if (t.d < 1 || t.d > 3 || t.k < 1 || !vals || ldv < m || (grad && ldg < m) || !x0 || (t.d > 1 && !x1) || (t.d > 2 && !x2)) return 1;
+    hipLaunchKernelGGL(field_soa_k_kernel, dim3(grid_for(m)), dim3(kThreads), 0, stream, t, x0, x1, x2, m, vals, ldv, grad, ldg);
+    TERMS_HIP(hipGetLastError());
+    return 0;
+}
 
 int terms_affine_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *y0,
                             double *y1, double *y2, hipStream_t stream) {

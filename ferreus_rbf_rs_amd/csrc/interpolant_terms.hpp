@@ -219,6 +219,11 @@ int terms_affine_soa_device(const InterpolantTerms &t, const double *x0, const d
                             double *y1, double *y2, hipStream_t stream);
 int terms_field_soa_device(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *vals,
                            double *grad, hipStream_t stream);
+// The K-column variant (FmmTree::evaluate_device): t.k value columns, column c at vals + c * ldv, and gradient column
+// c * t.d + a at grad + (c * t.d + a) * ldg, the layout of the host entries; t.lambda a device pointer.  (The trend's map of
+// the targets has no column count: terms_affine_soa_device serves every k.)
+int terms_field_soa_device_k(const InterpolantTerms &t, const double *x0, const double *x1, const double *x2, int64_t m, double *vals,
+                             int64_t ldv, double *grad, int64_t ldg, hipStream_t stream);
 int remove_duplicates_device(const double *points, int64_t n, int d, int64_t ld, const DedupGrid &g, int64_t *keep,
                              int64_t *n_keep, int64_t *rounds);
 

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -108,6 +109,39 @@ __global__ __launch_bounds__(256) void gather_targets_kernel(const double *__res
     if (out2) out2[i] = in2[p];
 }
 
+__global__ __launch_bounds__(256) void split_count_kernel(const int32_t *__restrict__ tgt_begin, const int32_t *__restrict__ tgt_end,
+                                                          int64_t n_runs, int32_t cap, int32_t *__restrict__ cnt) {
+    const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (r < n_runs) cnt[r] = static_cast<int32_t>(split_job_count(static_cast<int64_t>(tgt_end[r]) - tgt_begin[r], cap));
+}
+
+// one thread per job: its run is the last one whose offset is at most the job's index (a run of a coarse leaf has
+// thousands of jobs, so a thread per run would write them one after another)
+__global__ __launch_bounds__(256) void split_fill_kernel(const int32_t *__restrict__ job_cell, const int32_t *__restrict__ tgt_begin,
+                                                         const int32_t *__restrict__ tgt_end, int64_t n_runs,
+                                                         const int32_t *__restrict__ cnt, const int32_t *__restrict__ offs,
+                                                         int64_t capacity, int32_t *__restrict__ out_cell,
+                                                         int32_t *__restrict__ out_begin, int32_t *__restrict__ out_end,
+                                                         int32_t *__restrict__ n_jobs) {
+    const int64_t total = static_cast<int64_t>(offs[n_runs - 1]) + cnt[n_runs - 1];
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+    int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i == 0) *n_jobs = static_cast<int32_t>(total);
+    for (; i < total && i < capacity; i += stride) {
+        int64_t lo = 0, hi = n_runs; // first run with offs > i
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (offs[mid] <= i) lo = mid + 1;
+            else hi = mid;
+        }
+        const int64_t r = lo - 1; // offs[0] = 0 <= i, so r >= 0; runs without jobs share their successor's offset and are skipped
+        const int64_t b = tgt_begin[r], n = static_cast<int64_t>(tgt_end[r]) - b, q = cnt[r], j = i - offs[r];
+        out_cell[i] = job_cell[r];
+        out_begin[i] = static_cast<int32_t>(split_job_edge(b, n, q, j));
+        out_end[i] = static_cast<int32_t>(split_job_edge(b, n, q, j + 1));
+    }
+}
+
 inline unsigned blocks(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
 
 size_t sort_bytes(int64_t m, int end_bit) {
@@ -152,6 +186,43 @@ int group_targets(const int32_t *cell, int64_t m, int end_bit, int32_t *cell_sor
     // at most one run per row; the launch covers the capacity and reads the count on the device
     hipLaunchKernelGGL(runs_kernel, dim3(blocks(m)), dim3(256), 0, s, cell_sorted, m, n_runs, tgt_begin, job_cell, tgt_end);
     return static_cast<int>(hipGetLastError());
+}
+
+size_t split_runs_temp_bytes(int64_t n_runs) {
+    if (n_runs <= 0) return 0;
+    size_t b = 0;
+    (void)rocprim::exclusive_scan(nullptr, b, static_cast<const int32_t *>(nullptr), static_cast<int32_t *>(nullptr), int32_t(0),
+                                  static_cast<size_t>(n_runs), rocprim::plus<int32_t>());
+    return b;
+}
+
+int split_runs(const int32_t *job_cell, const int32_t *tgt_begin, const int32_t *tgt_end, int64_t n_runs, int32_t cap, int32_t *cnt,
+               int32_t *offs, int32_t *out_cell, int32_t *out_begin, int32_t *out_end, int64_t capacity, int32_t *n_jobs, void *temp,
+               size_t temp_bytes, hipStream_t s) {
+    if (n_runs <= 0 || cap < 1) return static_cast<int>(hipMemsetAsync(n_jobs, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(split_count_kernel, dim3(blocks(n_runs)), dim3(256), 0, s, tgt_begin, tgt_end, n_runs, cap, cnt);
+    size_t b = temp_bytes;
+    const hipError_t e = rocprim::exclusive_scan(temp, b, cnt, offs, int32_t(0), static_cast<size_t>(n_runs), rocprim::plus<int32_t>(), s);
+    if (e != hipSuccess) return static_cast<int>(e);
+    const unsigned fill_blocks = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((capacity + 255) / 256, 65536)));
+    hipLaunchKernelGGL(split_fill_kernel, dim3(fill_blocks), dim3(256), 0, s, job_cell, tgt_begin, tgt_end, n_runs, cnt, offs, capacity,
+                       out_cell, out_begin, out_end, n_jobs);
+    return static_cast<int>(hipGetLastError());
+}
+
+int64_t split_runs_host(const int32_t *job_cell, const int32_t *tgt_begin, const int32_t *tgt_end, int64_t n_runs, int32_t cap,
+                        int32_t *out_cell, int32_t *out_begin, int32_t *out_end) {
+    int64_t o = 0;
+    for (int64_t r = 0; r < n_runs; ++r) {
+        const int64_t b = tgt_begin[r], n = static_cast<int64_t>(tgt_end[r]) - b, q = split_job_count(n, cap);
+        for (int64_t j = 0; j < q; ++j, ++o) {
+            if (!out_cell) continue;
+            out_cell[o] = job_cell[r];
+            out_begin[o] = static_cast<int32_t>(split_job_edge(b, n, q, j));
+            out_end[o] = static_cast<int32_t>(split_job_edge(b, n, q, j + 1));
+        }
+    }
+    return o;
 }
 
 void launch_gather_targets(const double *in0, const double *in1, const double *in2, const int32_t *perm, int64_t m,

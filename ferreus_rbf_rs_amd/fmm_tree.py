@@ -275,6 +275,126 @@ class FmmTree:
         return self._eval(self._lib.bbfmm_evaluate_leaves_with_gradients, weights, target_points,
                           True, True)
 
+    # -- device-resident targets and regular grids (bbfmm_evaluate_device, bbfmm_evaluate_grid)
+    def _evaluate_options(self, batch_independent, max_job_targets, batch_bytes=0, outputs_on_device=False):
+        return L.EvaluateOptions(ctypes.sizeof(L.EvaluateOptions), -1 if batch_independent is None else int(bool(batch_independent)),
+                                 -1 if max_job_targets is None else int(max_job_targets), int(batch_bytes), int(bool(outputs_on_device)))
+
+    def _terms_c(self, terms):
+        return None if terms is None else terms.with_columns(self._nrhs)._c()
+
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.device())
+
+    @staticmethod
+    def _torch_columns(m, cols, device):
+        """(m, cols) float64 with column-major storage, the layout of the C ABI"""
+        import torch
+        return torch.empty((cols, max(m, 1)), dtype=torch.float64, device=device)[:, :m].t()
+
+    def evaluate_device(self, x, *, gradients=False, terms=None, batch_independent=None, max_job_targets=None):
+        """Leaves mode (set_local_coefficients first) at targets that live on the tree's device: x a float64 torch tensor
+        (m, d), or a tuple of d contiguous columns of m.  The SoA copy is made by torch, nothing touches the host.  Returns
+        a tensor (m, K) for the K weight columns and, with gradients, also (m, K, d); both are views of the column-major
+        result.  terms: rbf.FieldTerms of an interpolant (global trend before the pass, polynomial and trend gradients
+        behind it).  batch_independent: None is the tree's deterministic flag.  max_job_targets: jobs of the leaf pass
+        hold at most this many targets (0: one job per leaf, None: the library's default)."""
+        import torch
+        dev, d, k = self._torch_device(), self.dim, self._nrhs
+        if k < 1:
+            raise ValueError("set_local_coefficients must be called first")
+        if isinstance(x, (tuple, list)):
+            if len(x) != d:
+                raise ValueError(f"expected {d} coordinate columns, got {len(x)}")
+            soa = torch.stack([torch.as_tensor(c).reshape(-1) for c in x])
+        else:
+            if x.ndim != 2 or x.shape[1] != d:
+                raise ValueError(f"target_points must be (m, {d}), got {tuple(x.shape)}")
+            soa = x.t()
+        if soa.dtype != torch.float64 or soa.device != dev:
+            raise TypeError(f"device targets must be float64 tensors on {dev}")
+        soa = soa.contiguous()
+        m = soa.shape[1]
+        vals = self._torch_columns(m, k, dev)
+        grad = self._torch_columns(m, k * d, dev) if gradients else None
+        torch.cuda.synchronize(dev)                  # the tree's passes run on its own stream
+        bad = ctypes.c_int64(-1)
+        opts = self._evaluate_options(batch_independent, max_job_targets)
+        c = self._terms_c(terms)
+        rc = self._lib.bbfmm_evaluate_device(self._h, int(bool(gradients)), soa.data_ptr() if m else None, m, max(m, 1),
+                                             None if c is None else ctypes.byref(c), vals.data_ptr(), max(m, 1),
+                                             grad.data_ptr() if grad is not None else None, max(m, 1), ctypes.byref(opts),
+                                             ctypes.byref(bad))
+        self._raise(rc, bad, True)
+        if not gradients:
+            return vals
+        return vals, torch.as_strided(grad, (m, k, d), (1, d * max(m, 1), max(m, 1)), grad.storage_offset())
+
+    def last_grid_stats(self) -> dict:
+        """nodes, slabs, leaf_runs, jobs, largest_job, w_jobs of the last evaluate_grid"""
+        s = np.zeros(8, dtype=np.int64)
+        self._raise(self._lib.bbfmm_evaluate_grid_stats(self._h, s.ctypes.data))
+        return dict(zip(L.GRID_STATS, (int(v) for v in s)))
+
+    def _grid(self, origin, steps, shape):
+        d = self.dim
+        origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+        steps = np.asarray(steps, dtype=np.float64)
+        shape = [int(n) for n in np.asarray(shape).reshape(-1)]
+        if origin.size != d or steps.shape != (d, d) or len(shape) != d or min(shape) < 0:
+            raise ValueError(f"a grid of a {d}-D tree needs an origin of {d} coordinates, ({d}, {d}) steps and {d} counts >= 0")
+        return make_grid(origin, steps, shape), shape
+
+    def evaluate_grid(self, origin, steps, shape, *, gradients=False, terms=None, out="numpy", batch_bytes=0,
+                      batch_independent=None, max_job_targets=None, return_stats=False):
+        """Leaves mode at the nodes of a regular grid: node (i0, i1, i2) lies at origin + i0 steps[0] + i1 steps[1] +
+        i2 steps[2] (row j of `steps` is the world step of index j; a rotated block model is a non-diagonal `steps`).  The
+        coordinates are made on the device slab by slab (batch_bytes of device memory each, 0: the default) and never
+        exist on the host.  Returns values of shape (*shape, K) and, with gradients, (*shape, K, d): views of the
+        column-major result, numpy arrays or (out="torch") tensors on the tree's device.  return_stats: also
+        last_grid_stats().  The other options are those of evaluate_device."""
+        if out not in ("numpy", "torch"):
+            raise ValueError('out is "numpy" or "torch"')
+        d, k = self.dim, self._nrhs
+        if k < 1:
+            raise ValueError("set_local_coefficients must be called first")
+        g, shape = self._grid(origin, steps, shape)
+        m = int(np.prod(shape))
+        ld = max(m, 1)
+        if out == "torch":
+            import torch
+            dev = self._torch_device()
+            vals = self._torch_columns(m, k, dev)
+            grad = self._torch_columns(m, k * d, dev) if gradients else None
+            torch.cuda.synchronize(dev)
+            vp, gp = vals.data_ptr(), (grad.data_ptr() if gradients else None)
+        else:
+            vals = np.zeros((m, k), order="F")
+            grad = np.zeros((m, k * d), order="F") if gradients else None
+            vp, gp = vals.ctypes.data, (grad.ctypes.data if gradients else None)
+        bad = ctypes.c_int64(-1)
+        opts = self._evaluate_options(batch_independent, max_job_targets, batch_bytes, out == "torch")
+        c = self._terms_c(terms)
+        rc = self._lib.bbfmm_evaluate_grid(self._h, int(bool(gradients)), ctypes.byref(g), None if c is None else ctypes.byref(c),
+                                           vp, ld, gp, ld, ctypes.byref(opts), ctypes.byref(bad))
+        self._raise(rc, bad, True)
+        # row r = C order of the indices, column-major columns: (*shape, K) and (*shape, K, d) without a copy
+        row = [int(np.prod(shape[j + 1:])) for j in range(d)]
+        if out == "torch":
+            import torch
+            res = [torch.as_strided(vals, (*shape, k), (*row, ld), vals.storage_offset())]
+            if gradients:
+                res.append(torch.as_strided(grad, (*shape, k, d), (*row, d * ld, ld), grad.storage_offset()))
+        else:
+            as_strided = np.lib.stride_tricks.as_strided
+            res = [as_strided(vals, (*shape, k), tuple(8 * s for s in (*row, ld)))]
+            if gradients:
+                res.append(as_strided(grad, (*shape, k, d), tuple(8 * s for s in (*row, d * ld, ld))))
+        if return_stats:
+            res.append(self.last_grid_stats())
+        return res[0] if len(res) == 1 else tuple(res)
+
     # -- isosurfaces (isosurface.py)
     def build_isosurfaces(self, extents, resolution, isovalues, *, drift=None, return_field=False, batch_bytes=0,
                           cluster="none", return_stats=False, finish="raw", self_intersections="ignore", follow="dense",
@@ -681,6 +801,58 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_apply_m2l_tables_host(self._h, M.ctypes.data,
                                                                 Lc.ctypes.data))
         return Lc
+
+
+def make_grid(origin, steps, shape) -> L.Grid:
+    """bbfmm_grid of a d-D grid: origin (d,), steps (d, d) with row j the world step of index j, shape (d,)"""
+    origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+    d = origin.size
+    steps = np.asarray(steps, dtype=np.float64)
+    shape = [int(n) for n in np.asarray(shape).reshape(-1)]
+    if not 1 <= d <= 3 or steps.shape != (d, d) or len(shape) != d:
+        raise ValueError("a d-D grid needs an origin of d coordinates, (d, d) steps and d counts, d = 1..3")
+    g = L.Grid()
+    g.size, g.d = ctypes.sizeof(L.Grid), d
+    for a in range(3):
+        g.shape[a] = shape[a] if a < d else 1
+    for j in range(d):
+        g.origin[j] = origin[j]
+        for a in range(d):
+            g.steps[3 * j + a] = steps[j, a]
+    return g
+
+
+def debug_grid_coords(where: int, origin, steps, shape, r0: int, n: int) -> np.ndarray:
+    """Rows [r0, r0 + n) of the grid (C order) as an (n, d) column-major array, through the one definition of
+    csrc/evaluate_grid.hpp: where = 0 the host loop (no device needed), where = 1 the kernel."""
+    g = make_grid(origin, steps, shape)
+    out = np.zeros((n, g.d), order="F")
+    rc = L.load().bbfmm_debug_grid_coords(int(where), ctypes.byref(g), int(r0), int(n), out.ctypes.data, max(n, 1))
+    if rc != L.OK:
+        raise (RuntimeError if rc == L.DEVICE_ERROR else ValueError)(f"bbfmm_debug_grid_coords failed with status {rc}")
+    return out
+
+
+def debug_split_runs(where: int, tgt_begin, tgt_end, job_cell, cap: int):
+    """(begin, end, cell) of the jobs the runs are cut into with at most cap targets each (csrc/targets.hpp): where = 0
+    the host loop, where = 1 the count / scan / fill kernels."""
+    tb = np.ascontiguousarray(tgt_begin, dtype=np.int32)
+    te = np.ascontiguousarray(tgt_end, dtype=np.int32)
+    jc = np.ascontiguousarray(job_cell, dtype=np.int32)
+    if not tb.shape == te.shape == jc.shape or tb.ndim != 1:
+        raise ValueError("one begin, end and cell per run")
+    lib, n, nj = L.load(), tb.size, ctypes.c_int64(0)
+
+    def check(rc):
+        if rc != L.OK:
+            raise (RuntimeError if rc == L.DEVICE_ERROR else ValueError)(f"bbfmm_debug_split_runs failed with status {rc}")
+
+    check(lib.bbfmm_debug_split_runs(int(where), tb.ctypes.data, te.ctypes.data, jc.ctypes.data, n, int(cap), None, None, None, 0,
+                                     ctypes.byref(nj)))
+    ob, oe, oc = (np.zeros(max(nj.value, 1), dtype=np.int32) for _ in range(3))
+    check(lib.bbfmm_debug_split_runs(int(where), tb.ctypes.data, te.ctypes.data, jc.ctypes.data, n, int(cap), ob.ctypes.data,
+                                     oe.ctypes.data, oc.ctypes.data, nj.value, ctypes.byref(nj)))
+    return ob[:nj.value], oe[:nj.value], oc[:nj.value]
 
 
 def fp64_valu_selftest():

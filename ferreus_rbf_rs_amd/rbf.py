@@ -698,11 +698,47 @@ class RBFInterpolator:
         return evaluate_interpolant(self._evaluator, LEAVES, self._coefficients.point_coefficients, self._targets(targets), self.terms(),
                                     with_gradients)
 
-    def evaluate_targets(self, targets) -> np.ndarray:
+    @staticmethod
+    def _is_tensor(x) -> bool:
+        return type(x).__module__.split(".")[0] == "torch"
+
+    def _leaves_device(self, targets, with_gradients):
+        """torch tensors on the evaluator's device: FmmTree.evaluate_device, tensors back (gradients as (m, K d))"""
+        if self._evaluator is None:
+            raise ValueError("build_evaluator must be called first")
+        out = self._evaluator.evaluate_device(targets, gradients=with_gradients, terms=self.terms())
+        if not with_gradients:
+            return out
+        v, g = out
+        m, k, d = g.shape
+        return v, g.as_strided((m, k * d), (1, max(m, 1)), g.storage_offset())
+
+    def evaluate_targets(self, targets):
+        if self._is_tensor(targets):
+            return self._leaves_device(targets, False)
         return self._leaves(targets, False)
 
     def evaluate_targets_with_gradients(self, targets):
+        if self._is_tensor(targets):
+            return self._leaves_device(targets, True)
         return self._leaves(targets, True)
+
+    def evaluate_grid(self, origin, spacing, shape, *, axes=None, gradients=False, out="numpy", **options):
+        """The interpolant on a regular grid (a block model, a section, a volume): node (i0, i1, i2) lies at origin +
+        sum_j i_j spacing[j] axes[j]; axes (d, d), row j the direction of index j, defaults to the identity.  Uses the tree
+        of build_evaluator.  Values (*shape, K) and with gradients (*shape, K, d); options: those of FmmTree.evaluate_grid
+        (batch_bytes, batch_independent, max_job_targets, return_stats)."""
+        if self._evaluator is None:
+            raise ValueError("build_evaluator must be called first")
+        d = self.dimensions
+        spacing = np.asarray(spacing, dtype=np.float64).reshape(-1)
+        if spacing.size == 1:
+            spacing = np.repeat(spacing, d)
+        axes = np.eye(d) if axes is None else np.asarray(axes, dtype=np.float64).reshape(d, d)
+        if spacing.size != d:
+            raise ValueError(f"spacing: one value, or one per axis ({d})")
+        return self._evaluator.evaluate_grid(origin, spacing[:, None] * axes, shape, gradients=gradients, terms=self.terms(), out=out,
+                                             **options)
 
     # ---- isosurfaces
     def build_isosurfaces(self, extents, resolution: float, isovalues, boundary_closure: Optional[BoundaryClosure] = None, *,

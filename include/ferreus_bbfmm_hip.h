@@ -1077,6 +1077,73 @@ int bbfmm_evaluate_interpolant(bbfmm_handle *h, int32_t mode, int32_t with_gradi
                                double nugget, double *values_out, int64_t ldo, double *grad_out, int64_t ldg,
                                int64_t *bad_point_index);
 
+/* ---- Evaluation at device-resident targets and on regular grids (Leaves mode: bbfmm_set_local_coefficients first,
+ * BBFMM_BAD_ARGUMENT otherwise; all k columns of the weights).
+ *
+ * A regular grid.  size = sizeof(bbfmm_grid).  steps is 3 x 3 row-major whatever d is: row j (steps[3 j + a]) is the
+ * world step of index j, so a rotated block model is a non-diagonal steps.  Rows are in C order,
+ * r = (i0 n1 + i1) n2 + i2.  Axes at or beyond d are absent: their shape counts as 1 and they add no term.  The node is
+ *   x_a = ((origin_a + (double)i0 S[0][a]) + (double)i1 S[1][a]) + (double)i2 S[2][a],
+ * every product and sum rounded, in this order, never fused, on the host and on the device alike. */
+typedef struct bbfmm_grid {
+    int64_t size;
+    int32_t d; /* 1..3, the tree's */
+    int32_t reserved;
+    int64_t shape[3];
+    double origin[3];
+    double steps[9];
+} bbfmm_grid;
+
+/* Options of the two entries below.  size: sizeof(bbfmm_evaluate_options) as the caller was compiled; fields beyond it,
+ * and a NULL struct, take the defaults.
+ *   batch_independent: -1 (the default) the handle's BBFMM_FLAG_DETERMINISTIC flag, 0 / 1: the near field and M2P split a
+ *     job's targets the same way whatever their number, so that on a deterministic handle a target's value is the same
+ *     double whichever other targets, slab or job cut share the call;
+ *   max_job_targets: the jobs of the leaf pass (P2P, M2P, L2P) hold at most this many targets: a leaf with n targets is
+ *     cut into q = ceil(n / cap) jobs, job j taking [floor(j n / q), floor((j + 1) n / q)) of them.  0: one job per leaf,
+ *     the target set of every other entry point.  -1 (the default): the library's choice;
+ *   batch_bytes (grid): device memory of one slab (<= 0: 2 GiB, the isosurfacer's default);
+ *   outputs_on_device (grid): values_out / grad_out are device pointers on the handle's device. */
+typedef struct bbfmm_evaluate_options {
+    int64_t size;
+    int32_t batch_independent;
+    int32_t max_job_targets;
+    int64_t batch_bytes;
+    int32_t outputs_on_device;
+} bbfmm_evaluate_options;
+
+/* m targets on the handle's device as SoA, column a at d_x + a * ldx.  Values m x k column-major to d_values (device,
+ * leading dimension ldo); with_gradients: component a of column c to column c * d + a of d_grad (leading dimension ldg),
+ * as in the host entries; both in the caller's row order.  terms (NULL: none; k = the weights' columns, host
+ * coefficients): the trend's map of the targets runs before the pass, trend_gradients and polynomial_terms behind it, on
+ * the handle's stream, which is idle on return.  A row outside the tree: BBFMM_POINT_OUTSIDE_TREE with the smallest such
+ * row in *bad_point_index.  On a device group the call runs on the primary part. */
+int bbfmm_evaluate_device(bbfmm_handle *h, int32_t with_gradients, const double *d_x, int64_t m, int64_t ldx,
+                          const bbfmm_interpolant_terms *terms, double *d_values, int64_t ldo, double *d_grad, int64_t ldg,
+                          const bbfmm_evaluate_options *options, int64_t *bad_point_index);
+
+/* The same at the nodes of a grid, rows in C order: slabs of whole leading-index planes sized to batch_bytes (a plane
+ * that does not fit is cut by rows; a slab holds fewer than 2^31 rows), each slab coordinates -> the pass above -> its
+ * rows of values_out / grad_out (host arrays, or device arrays with outputs_on_device).  ldo, ldg >= the grid's rows.
+ * A zero in shape is an empty grid and BBFMM_OK. */
+int bbfmm_evaluate_grid(bbfmm_handle *h, int32_t with_gradients, const bbfmm_grid *grid, const bbfmm_interpolant_terms *terms,
+                        double *values_out, int64_t ldo, double *grad_out, int64_t ldg, const bbfmm_evaluate_options *options,
+                        int64_t *bad_point_index);
+
+/* Of the handle's last grid call: nodes, slabs, leaf runs (leaves with targets, summed over the slabs), jobs after the
+ * cut, targets of the largest job, M2P (W) jobs, 0, 0: eight values. */
+int bbfmm_evaluate_grid_stats(bbfmm_handle *h, int64_t *stats_out);
+
+/* Test hooks, where = 0 on the host and 1 on the device (one kernel between an upload and a download), one definition
+ * of the arithmetic behind both: rows [r0, r0 + n) of the grid as SoA columns, column a at out + a * ld; */
+int bbfmm_debug_grid_coords(int32_t where, const bbfmm_grid *grid, int64_t r0, int64_t n, double *out, int64_t ld);
+/* and the cut of n_runs runs (job_cell / tgt_begin / tgt_end, lengths >= 0) into jobs of at most cap >= 1 targets.
+ * out_*: capacity values each (NULL: the count alone); *n_jobs_out the number of jobs, BBFMM_BAD_ARGUMENT when it
+ * exceeds the capacity. */
+int bbfmm_debug_split_runs(int32_t where, const int32_t *tgt_begin, const int32_t *tgt_end, const int32_t *job_cell, int64_t n_runs,
+                           int32_t cap, int32_t *out_begin, int32_t *out_end, int32_t *out_cell, int64_t capacity,
+                           int64_t *n_jobs_out);
+
 #ifdef __cplusplus
 }
 #endif
