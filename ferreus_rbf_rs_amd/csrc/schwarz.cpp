@@ -220,6 +220,79 @@ int download_correction(Schwarz &S, const std::vector<double> &tail, double *out
     return BBFMM_OK;
 }
 
+// What bbfmm_schwarz_debug_apply_trace copies out after every level_step (the caller's buffers, see the header).
+struct SweepTrace {
+    int32_t max_steps = 0, n_steps = 0;
+    int32_t *info = nullptr;
+    double *vectors = nullptr, *small = nullptr;
+};
+
+int record_step(Schwarz &S, SweepTrace &T, size_t li, bool have_sl, bool coarse, bool add_poly, const std::vector<double> &tail) {
+    if (T.n_steps >= T.max_steps) return BBFMM_BAD_ARGUMENT;
+    const size_t n = static_cast<size_t>(S.n), nb = n * sizeof(double);
+    const int64_t nl = static_cast<int64_t>(S.ddm.levels[li].point_indices.size());
+    const bool proj = !coarse && S.basis;
+    int32_t *info = T.info + 5 * static_cast<size_t>(T.n_steps);
+    info[0] = static_cast<int32_t>(li);
+    info[1] = coarse;
+    info[2] = have_sl;
+    info[3] = add_poly;
+    info[4] = static_cast<int32_t>(tail.size());
+    double *v = T.vectors + 4 * n * static_cast<size_t>(T.n_steps), *sm = T.small + 32 * static_cast<size_t>(T.n_steps);
+    HIPOK(hipStreamSynchronize(S.stream));
+    std::fill(v, v + n, 0.0);
+    std::fill(sm, sm + 32, 0.0);
+    if (have_sl) HIPOK(hipMemcpy(v, S.d_y, static_cast<size_t>(nl) * sizeof(double), hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(v + n, S.d_res, nb, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(v + 2 * n, S.d_out, nb, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(v + 3 * n, S.d_sl, nb, hipMemcpyDeviceToHost));
+    if (proj) HIPOK(hipMemcpy(sm, S.d_proj, static_cast<size_t>(S.basis) * sizeof(double), hipMemcpyDeviceToHost));
+    std::copy(tail.begin(), tail.end(), sm + 16);
+    ++T.n_steps;
+    return BBFMM_OK;
+}
+
+// schwarz_preconditioner (schwarz.rs:32-82) on the device vectors: every fine level followed by a visit of the coarse
+// domain, whose last visit returns the polynomial tail.  The apply and the trace hook both run this loop.
+int sweep(Schwarz &S, std::vector<double> *tail, SweepTrace *trace) {
+    const size_t coarse = S.ddm.levels.size() - 1;
+    auto step = [&](size_t li, bool have_sl, bool is_coarse, bool add_poly) {
+        std::vector<double> produced;
+        int rc = level_step(S, li, have_sl, is_coarse, add_poly, is_coarse ? &produced : nullptr);
+        if (rc == BBFMM_OK && trace) rc = record_step(S, *trace, li, have_sl, is_coarse, add_poly, produced);
+        if (!produced.empty()) tail->swap(produced);
+        return rc;
+    };
+    int rc = BBFMM_OK;
+    bool have_sl = false; // sl = 0 until the first correction has been added
+    if (coarse > 0) {
+        for (size_t i = 0; i < coarse; ++i) {
+            if ((rc = step(i, have_sl, false, false))) return rc;
+            have_sl = true;
+            if ((rc = step(coarse, true, true, i == coarse - 1))) return rc;
+        }
+    } else {
+        if ((rc = step(coarse, false, true, true))) return rc;
+    }
+    return BBFMM_OK;
+}
+
+// BBFMM_VERBOSE: the stage times a sweep has accumulated, printed and cleared (by the apply and by the trace hook alike)
+void report_times(Schwarz &S, const char *what, std::chrono::steady_clock::time_point t_begin) {
+    if (!S.verbose) return;
+    std::fprintf(stderr, "[bbfmm] schwarz %s %.3f s: partial matvecs %.3f s, level solves %.3f s (of which exchange %.3f s), host %.3f s\n",
+                 what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), S.t_matvec, S.t_solve,
+                 S.t_exchange, S.t_host);
+    S.t_exchange = 0;
+    for (size_t l = 0; l < S.t_level.size(); ++l) {
+        std::fprintf(stderr, "[bbfmm]   level %zu: %lld domains, %lld entries, max m %d: solves %.3f s, matvecs %.3f s\n", l,
+                     (long long)S.levels[l].n_dom, (long long)S.levels[l].n_entries, S.levels[l].max_m, S.t_level[l],
+                     S.t_level_mv[l]);
+        S.t_level[l] = S.t_level_mv[l] = 0;
+    }
+    S.t_matvec = S.t_solve = S.t_host = 0;
+}
+
 } // namespace
 
 struct bbfmm_schwarz {
@@ -501,6 +574,8 @@ int bbfmm_debug_evaluate_monomials(const double *points, int64_t n, int32_t d, i
 
 const double *bbfmm_schwarz_monomial_matrix(const bbfmm_schwarz *h) { return (h && h->s.basis) ? h->s.mono.data() : nullptr; }
 
+const double *bbfmm_schwarz_debug_ortho_matrix(const bbfmm_schwarz *h) { return (h && h->s.basis) ? h->s.ortho.data() : nullptr; }
+
 int64_t bbfmm_schwarz_level_size(const bbfmm_schwarz *h, int32_t level) {
     if (!h || level < 0 || level >= static_cast<int32_t>(h->s.ddm.levels.size())) return -1;
     return static_cast<int64_t>(h->s.ddm.levels[static_cast<size_t>(level)].point_indices.size());
@@ -672,32 +747,47 @@ int bbfmm_schwarz_apply(void *user, const double *rg, double *sl, int64_t n) {
     const auto t_begin = std::chrono::steady_clock::now();
     int rc = upload_residual(S, rg);
     if (rc) return rc;
-    const size_t coarse = S.ddm.levels.size() - 1;
     std::vector<double> tail;
-    bool have_sl = false; // sl = 0 until the first correction has been added
-    if (coarse > 0) {
-        for (size_t i = 0; i < coarse; ++i) {
-            if ((rc = level_step(S, i, have_sl, false, false, nullptr))) return rc;
-            have_sl = true;
-            if ((rc = level_step(S, coarse, true, true, i == coarse - 1, &tail))) return rc;
-        }
-    } else {
-        if ((rc = level_step(S, coarse, false, true, true, &tail))) return rc;
-    }
+    if ((rc = sweep(S, &tail, nullptr))) return rc;
     if ((rc = download_correction(S, tail, sl))) return rc;
-    if (S.verbose) {
-        std::fprintf(stderr, "[bbfmm] schwarz apply %.3f s: partial matvecs %.3f s, level solves %.3f s (of which exchange %.3f s), host %.3f s\n",
-                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), S.t_matvec, S.t_solve,
-                     S.t_exchange, S.t_host);
-        S.t_exchange = 0;
-        for (size_t l = 0; l < S.t_level.size(); ++l) {
-            std::fprintf(stderr, "[bbfmm]   level %zu: %lld domains, %lld entries, max m %d: solves %.3f s, matvecs %.3f s\n", l,
-                         (long long)S.levels[l].n_dom, (long long)S.levels[l].n_entries, S.levels[l].max_m, S.t_level[l],
-                         S.t_level_mv[l]);
-            S.t_level[l] = S.t_level_mv[l] = 0;
-        }
-        S.t_matvec = S.t_solve = S.t_host = 0;
-    }
+    report_times(S, "apply", t_begin);
+    return BBFMM_OK;
+    SCHWARZ_END_GUARD
+}
+
+int32_t bbfmm_schwarz_debug_trace_steps(const bbfmm_schwarz *h) {
+    if (!h || h->s.ddm.levels.empty()) return 0;
+    const size_t coarse = h->s.ddm.levels.size() - 1;
+    return static_cast<int32_t>(coarse > 0 ? 2 * coarse : 1);
+}
+
+int bbfmm_schwarz_debug_apply_trace(bbfmm_schwarz *h, const double *rg, double *sl, int64_t n, int32_t max_steps,
+                                    int32_t *step_info, double *initial, double *vectors, double *small, int32_t *n_steps) {
+    if (!h || !rg || !sl || n != h->s.n + h->s.basis || !step_info || !initial || !vectors || !small || !n_steps ||
+        max_steps < bbfmm_schwarz_debug_trace_steps(h) || h->s.world > 1)
+        return BBFMM_BAD_ARGUMENT;
+    SCHWARZ_GUARD
+    SCHWARZ_BIND(h)
+    Schwarz &S = h->s;
+    *n_steps = 0;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc = upload_residual(S, rg);
+    if (rc) return rc;
+    const size_t nb = static_cast<size_t>(S.n) * sizeof(double);
+    HIPOK(hipStreamSynchronize(S.stream));
+    HIPOK(hipMemcpy(initial, S.d_res, nb, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(initial + S.n, S.d_out, nb, hipMemcpyDeviceToHost));
+    SweepTrace T;
+    T.max_steps = max_steps;
+    T.info = step_info;
+    T.vectors = vectors;
+    T.small = small;
+    std::vector<double> tail;
+    rc = sweep(S, &tail, &T);
+    *n_steps = T.n_steps;
+    if (rc) return rc;
+    if ((rc = download_correction(S, tail, sl))) return rc;
+    report_times(S, "apply (traced)", t_begin);
     return BBFMM_OK;
     SCHWARZ_END_GUARD
 }

@@ -326,6 +326,43 @@ class SchwarzPreconditioner:
             raise RuntimeError(f"bbfmm_schwarz_debug_level_solve failed with status {rc}")
         return z
 
+    def debug_apply_trace(self, residual):
+        """Test hook (bbfmm_schwarz_debug_apply_trace): the apply with the sweep's device vectors copied out after every level
+        step.  Returns (z, steps, initial): z as __call__ returns it; per step a dict with level, coarse, have_sl, add_poly, y
+        (the partial product on the level's rows; None without have_sl), res, out, sl (N each), proj (fine levels with a
+        basis, else None) and tail (None unless the step produced one); initial = dict(res, out) before the first step."""
+        r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1)
+        z = np.zeros_like(r)
+        n, cap = self.n, int(self._lib.bbfmm_schwarz_debug_trace_steps(self._h))
+        info = np.zeros((cap, 5), dtype=np.int32)
+        initial = np.zeros((2, n))
+        vectors = np.zeros((cap, 4, n))
+        small = np.zeros((cap, 32))
+        count = ctypes.c_int32(0)
+        rc = self._lib.bbfmm_schwarz_debug_apply_trace(self._h, r.ctypes.data, z.ctypes.data, r.size, cap, info.ctypes.data,
+                                                       initial.ctypes.data, vectors.ctypes.data, small.ctypes.data,
+                                                       ctypes.byref(count))
+        if rc != L.OK:
+            raise RuntimeError(f"bbfmm_schwarz_debug_apply_trace failed with status {rc}")
+        steps = []
+        for s in range(count.value):
+            level, coarse, have_sl, add_poly, n_tail = (int(v) for v in info[s])
+            nl = int(self._lib.bbfmm_schwarz_level_size(self._h, level))
+            steps.append({"level": level, "coarse": bool(coarse), "have_sl": bool(have_sl), "add_poly": bool(add_poly),
+                          "y": vectors[s, 0, :nl].copy() if have_sl else None, "res": vectors[s, 1].copy(),
+                          "out": vectors[s, 2].copy(), "sl": vectors[s, 3].copy(),
+                          "proj": small[s, :self.basis_size].copy() if (self.basis_size and not coarse) else None,
+                          "tail": small[s, 16:16 + n_tail].copy() if n_tail else None})
+        return z, steps, {"res": initial[0].copy(), "out": initial[1].copy()}
+
+    def debug_ortho(self):
+        """The orthonormal polynomial basis the sweep projects on (N x basis), or None."""
+        p = self._lib.bbfmm_schwarz_debug_ortho_matrix(self._h)
+        if not p:
+            return None
+        buf = (ctypes.c_double * (self.n * self.basis_size)).from_address(p)
+        return np.frombuffer(buf, dtype=np.float64).reshape((self.n, self.basis_size), order="F").copy(order="F")
+
     def close(self) -> None:
         """Release the factors and every device buffer now (also done when the last reference goes)."""
         h = getattr(self, "_h", None)

@@ -1002,6 +1002,19 @@ int bbfmm_ddm_debug_level_factor(const bbfmm_ddm_debug_level *h, double *out);
 int bbfmm_ddm_debug_level_solve(bbfmm_ddm_debug_level *h, const double *values, double *out, int64_t n, int32_t all_points);
 /* a bbfmm_apply_fn: user = bbfmm_schwarz*, vectors of N + basis_size doubles */
 int bbfmm_schwarz_apply(void *user, const double *residual, double *correction, int64_t n);
+/* Test hook: bbfmm_schwarz_apply with the device vectors of the sweep copied out after every level step.  The apply and the
+ * hook run the same loop; the hook alone waits for the stream and copies (unsharded handles only).
+ *   _trace_steps: the level steps of one apply (2 (levels - 1), or 1 for a single level)
+ *   step_info:  5 per step: level, coarse, have_sl, add_poly, values of the polynomial tail the step produced (0: none)
+ *   initial:    2 N: the level residual and the local-solve output as the sweep finds them (they persist between applies)
+ *   vectors:    4 N per step: the partial product (the level's size; zeros when have_sl is 0), the level residual, the
+ *               local-solve output, the running correction
+ *   small:      32 per step: the projection on the polynomial basis (fine levels with a basis) at 0, the tail at 16
+ * _debug_ortho_matrix: the orthonormal polynomial basis the sweep projects on (rbf.rs:493-495), N x basis column-major, or NULL. */
+int32_t bbfmm_schwarz_debug_trace_steps(const bbfmm_schwarz *h);
+int bbfmm_schwarz_debug_apply_trace(bbfmm_schwarz *h, const double *residual, double *correction, int64_t n, int32_t max_steps,
+                                    int32_t *step_info, double *initial, double *vectors, double *small, int32_t *n_steps);
+const double *bbfmm_schwarz_debug_ortho_matrix(const bbfmm_schwarz *h);
 
 /* ---- The interpolant around the tree: what ferreus_rbf::RBFInterpolator (ferreus_rbf/src/rbf.rs:304-1298) adds to the
  * kernel sum.  Arrays of points, values and gradients are column-major like every other entry's (column a at + a * ld);

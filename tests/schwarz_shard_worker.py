@@ -38,6 +38,11 @@ def main():
     z0 = whole(r)
     z1 = shard(r)
     z2 = shard(r)                                            # again: the exchange buffer is reused
+    try:                                                     # the trace hook is for unsharded handles: refused, no collective
+        shard.debug_apply_trace(r)
+        trace_refused = False
+    except RuntimeError:
+        trace_refused = True
     own = [shard.domains_owned(lv) for lv in range(shard.num_levels)]
     op = S.RbfSystemOperator(tree, m, whole.monomial_matrix, 0.0)
     rhs = np.concatenate([vals, np.zeros(m)])
@@ -46,7 +51,7 @@ def main():
     print(json.dumps({"rank": rank, "world": world, "levels": shard.num_levels,
                       "apply_equal": bool(np.array_equal(z0, z1) and np.array_equal(z1, z2)),
                       "apply_max_diff": float(np.abs(z0 - z1).max()), "apply_norm": float(np.abs(z0).max()),
-                      "owned": own, "factor_bytes_whole": whole.factor_bytes(), "factor_bytes_shard": shard.factor_bytes(),
+                      "owned": own, "trace_refused": trace_refused, "factor_bytes_whole": whole.factor_bytes(), "factor_bytes_shard": shard.factor_bytes(),
                       "iterations": [len(h0), len(h1)], "history_equal": bool([a[1] for a in h0] == [a[1] for a in h1]),
                       "solution_equal": bool(np.array_equal(x0, x1)), "final_residual": float(h1[-1][1])}), flush=True)
     dist.barrier()

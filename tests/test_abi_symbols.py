@@ -42,6 +42,13 @@ def test_ddm_debug_level_hook_is_declared_and_bound():
         assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n
 
 
+def test_schwarz_trace_hook_is_declared_and_bound():
+    names = ["bbfmm_schwarz_debug_trace_steps", "bbfmm_schwarz_debug_apply_trace", "bbfmm_schwarz_debug_ortho_matrix"]
+    lib = ctypes.CDLL(L.LIB_PATH)
+    for n in names:
+        assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n
+
+
 def test_params_defaults_match_reference():
     # FmmParams::new_defaults, ferreus_bbfmm/src/bbfmm.rs:96-103
     lib = L.load()
