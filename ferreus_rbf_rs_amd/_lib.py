@@ -168,6 +168,14 @@ SIGNATURES = {
     "bbfmm_schwarz_ddm_solver": (ctypes.c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_f64,
                                                 c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_rbf_system_apply": (ctypes.c_int, [c_p, c_p, c_p, c_i64]),
+    "bbfmm_rbf_system_device_create": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_f64, c_p]),
+    "bbfmm_rbf_system_device_destroy": (None, [c_p]),
+    "bbfmm_rbf_system_apply_device": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p]),
+    "bbfmm_fgmres_device": (ctypes.c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f64,
+                                           c_p, c_p, c_p, c_p, c_p, c_p]),
+    "bbfmm_schwarz_ddm_solver_device": (ctypes.c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_f64,
+                                                       c_p, c_p, c_p, c_p, c_p, c_p]),
+    "bbfmm_debug_solver_vector_op": (ctypes.c_int, [c_i32, c_i32, c_i64, c_p, c_p, c_p, c_f64, c_i32, c_p, c_i32, c_p, c_p]),
     "bbfmm_ddm_params_defaults": (None, [c_p]),
     "bbfmm_ddm_params_for_points": (None, [c_i64, c_p]),
     "bbfmm_ddm_build": (ctypes.c_int, [c_p, c_i64, c_i32, c_i64, c_p, c_p]),
@@ -188,6 +196,7 @@ SIGNATURES = {
     "bbfmm_schwarz_monomial_matrix": (c_p, [c_p]),
     "bbfmm_debug_evaluate_monomials": (ctypes.c_int, [c_p, c_i64, c_i32, c_i64, c_i32, c_p, c_p, c_p]),
     "bbfmm_schwarz_apply": (ctypes.c_int, [c_p, c_p, c_p, c_i64]),
+    "bbfmm_schwarz_apply_device": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p]),
     "bbfmm_schwarz_debug_trace_steps": (c_i32, [c_p]),
     "bbfmm_schwarz_debug_apply_trace": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p]),
     "bbfmm_schwarz_debug_ortho_matrix": (c_p, [c_p]),
@@ -278,6 +287,7 @@ class DdmParams(ctypes.Structure):
 
 # bbfmm_apply_fn, bbfmm_iteration_fn
 APPLY_FN = ctypes.CFUNCTYPE(ctypes.c_int, c_p, ctypes.POINTER(c_f64), ctypes.POINTER(c_f64), c_i64)
+APPLY_DEVICE_FN = ctypes.CFUNCTYPE(ctypes.c_int, c_p, c_p, c_p, c_i64, c_p)   # bbfmm_apply_device_fn (device pointers)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, c_p, c_i64)     # bbfmm_allreduce_fn
 ITERATION_FN = ctypes.CFUNCTYPE(None, c_p, c_i64, c_f64, c_f64)
 ACCURACY_ABSOLUTE, ACCURACY_RELATIVE = 0, 1

@@ -43,6 +43,7 @@ namespace bbfmm {
 void set_handle_error(bbfmm_handle *h, const char *message) { // interpolant.cpp: entry points outside this file
     if (h) h->err = message;
 }
+bool handle_is_host_only(const bbfmm_handle *h) { return h && h->tree.host_only(); } // solver_device.cpp, schwarz.cpp
 } // namespace bbfmm
 
 #define GUARD(h)                              \

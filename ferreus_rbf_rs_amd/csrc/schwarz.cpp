@@ -7,7 +7,8 @@
 // residuals, the partial products (bbfmm_matvec_subset_device), the local solves, the write-back and the
 // orthogonalisation against the polynomial basis all run on the tree's stream, and the correction comes
 // down once.  The first correction of a sweep skips its partial product: `sl` is still zero there and
-// K * 0 = 0 exactly (schwarz.rs:53-59 with sl = 0).
+// K * 0 = 0 exactly (schwarz.rs:53-59 with sl = 0).  For a driver whose vectors live on the device
+// (bbfmm_fgmres_device) bbfmm_schwarz_apply_device runs the same sweep between two device-to-device copies.
 #include "../../include/ferreus_bbfmm_hip.h"
 
 #include <algorithm>
@@ -26,6 +27,7 @@
 #include "ddm_monomials.hpp"
 #include "parallel.hpp"
 #include "schwarz_kernels.hpp"
+#include "solver_vectors.hpp"
 
 namespace {
 using namespace bbfmm;
@@ -298,6 +300,10 @@ void report_times(Schwarz &S, const char *what, std::chrono::steady_clock::time_
 struct bbfmm_schwarz {
     Schwarz s;
 };
+
+namespace bbfmm {
+bbfmm_handle *schwarz_tree(const bbfmm_schwarz *h) { return h ? h->s.tree : nullptr; } // solver_device.cpp
+} // namespace bbfmm
 
 namespace {
 // mono_points: NULL, or the points the monomials are evaluated at (a global trend's world points) with the cube scaling
@@ -751,6 +757,36 @@ int bbfmm_schwarz_apply(void *user, const double *rg, double *sl, int64_t n) {
     if ((rc = sweep(S, &tail, nullptr))) return rc;
     if ((rc = download_correction(S, tail, sl))) return rc;
     report_times(S, "apply", t_begin);
+    return BBFMM_OK;
+    SCHWARZ_END_GUARD
+}
+
+// The same sweep for a driver whose vectors live on the device (bbfmm_fgmres_device): the two bus legs of
+// upload_residual / download_correction become device-to-device copies on the tree's stream, the tail is written by a
+// kernel in the positions download_correction uses.
+int bbfmm_schwarz_apply_device(void *user, const double *d_rg, double *d_sl, int64_t n, void *stream) {
+    bbfmm_schwarz *h = static_cast<bbfmm_schwarz *>(user);
+    if (!h || !d_rg || !d_sl || n != h->s.n + h->s.basis || stream != static_cast<void *>(h->s.stream)) return BBFMM_BAD_ARGUMENT;
+    if (h->s.world > 1) return BBFMM_UNSUPPORTED; // (a sharded sweep ends its levels in host-side collectives)
+    SCHWARZ_GUARD
+    SCHWARZ_BIND(h)
+    Schwarz &S = h->s;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const size_t nb = static_cast<size_t>(S.n) * sizeof(double);
+    HIPOK(hipMemcpyAsync(S.d_rg, d_rg, nb, hipMemcpyDeviceToDevice, S.stream));
+    HIPOK(hipMemsetAsync(S.d_sl, 0, nb, S.stream));
+    std::vector<double> tail;
+    int rc = sweep(S, &tail, nullptr);
+    if (rc) return rc;
+    HIPOK(hipMemcpyAsync(d_sl, S.d_sl, nb, hipMemcpyDeviceToDevice, S.stream));
+    if (S.basis) { // the last `basis` rows: zero, the tail (when one was produced) at their end
+        if (S.basis > 16 || tail.size() > static_cast<size_t>(S.basis)) return BBFMM_BAD_ARGUMENT;
+        SolverTail t{};
+        for (size_t a = 0; a < tail.size(); ++a) t.v[static_cast<size_t>(S.basis) - tail.size() + a] = tail[a];
+        launch_solver_set_tail(t, S.basis, d_sl + S.n, S.stream);
+        HIPOK(hipGetLastError());
+    }
+    report_times(S, "apply (device vectors)", t_begin);
     return BBFMM_OK;
     SCHWARZ_END_GUARD
 }

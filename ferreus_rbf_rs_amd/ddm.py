@@ -292,6 +292,14 @@ class SchwarzPreconditioner:
         # cyclic collector happens to run; whoever passes the preconditioner to a solver holds it for the call anyway)
         self._op = _Operator(ctypes.cast(lib.bbfmm_schwarz_apply, ctypes.c_void_p), h, ())
         self._op.errors = []
+        # the device twin (bbfmm_schwarz_apply_device) for solvers that keep their vectors on the device
+        self._dop = _Operator(ctypes.cast(lib.bbfmm_schwarz_apply_device, ctypes.c_void_p), h, ())
+        self._dop.errors = []
+
+    def apply_device(self, residual):
+        """The sweep for a float64 torch tensor on the tree's device; returns a tensor there."""
+        from .solvers import _apply_native_device
+        return _apply_native_device(self._dop, self._tree, residual, "bbfmm_schwarz_apply_device")
 
     def __call__(self, residual):
         r = np.ascontiguousarray(residual, dtype=np.float64).reshape(-1)
@@ -370,6 +378,7 @@ class SchwarzPreconditioner:
             self._lib.bbfmm_schwarz_destroy(h)
             self._h = None
             self._op.user_ptr = None
+            self._dop.user_ptr = None
 
     def __del__(self):
         self.close()

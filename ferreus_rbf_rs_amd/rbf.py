@@ -164,11 +164,13 @@ class FmmParams:
 class Params:
     """Params (config.rs:96-190).  Beyond the reference: deterministic (BBFMM_FLAG_DETERMINISTIC on the trees) and
     ddm_params = "reference" (the default: DDMParams' defaults) | "for_points" (ddm.DDMParams.for_points(n), DESIGN.md
-    section 9) besides a DDMParams."""
+    section 9) besides a DDMParams; solver_vectors = "host" (the default) | "device": where the iterative solver keeps its
+    vectors (solvers.fgmres / schwarz_ddm_solver, vectors=)."""
 
     def __init__(self, kernel_type: RBFKernelType, solver_type: Optional[Solvers] = None,
                  ddm_params: Union[None, str, DDMParams] = None, fmm_params: Optional[FmmParams] = None,
-                 naive_solve_threshold: Optional[int] = None, test_unique: Optional[bool] = None, deterministic: bool = False):
+                 naive_solve_threshold: Optional[int] = None, test_unique: Optional[bool] = None, deterministic: bool = False,
+                 solver_vectors: str = "host"):
         self.kernel_type = RBFKernelType(kernel_type)
         self.solver_type = Solvers.FGMRES if solver_type is None else Solvers(solver_type)
         if isinstance(ddm_params, str) and ddm_params not in ("reference", "for_points"):
@@ -178,6 +180,9 @@ class Params:
         self.naive_solve_threshold = 4096 if naive_solve_threshold is None else int(naive_solve_threshold)
         self.test_unique = True if test_unique is None else bool(test_unique)
         self.deterministic = bool(deterministic)
+        if solver_vectors not in ("host", "device"):
+            raise ValueError('solver_vectors must be "host" or "device"')
+        self.solver_vectors = solver_vectors
 
     def ddm_for(self, n: int) -> _ddm.DDMParams:
         if self.ddm_params == "reference":
@@ -602,9 +607,9 @@ class RBFInterpolator:
             for c in range(k):                                                             # rbf.rs:536-574
                 rhs = np.concatenate([self._values[:, c], np.zeros(m)])
                 if self.params.solver_type is Solvers.FGMRES:
-                    x, hist = _solvers.fgmres(op, rhs, pre, None, 20, 5, tol, on_iteration)
+                    x, hist = _solvers.fgmres(op, rhs, pre, None, 20, 5, tol, on_iteration, vectors=self.params.solver_vectors)
                 else:
-                    x, hist = _solvers.schwarz_ddm_solver(op, rhs, pre, 100, tol, on_iteration)
+                    x, hist = _solvers.schwarz_ddm_solver(op, rhs, pre, 100, tol, on_iteration, vectors=self.params.solver_vectors)
                 self.residual_histories.append(hist)
                 point[:, c] = x[:n]
                 if m:

@@ -854,6 +854,67 @@ typedef struct bbfmm_rbf_system {
 } bbfmm_rbf_system;
 int bbfmm_rbf_system_apply(void *user, const double *x, double *y, int64_t n);
 
+/* ------------------------------------------------------------------ iterative solvers, vectors on the device
+ * The same two drivers with every vector in HBM ("Device-resident solvers"): x, r, the Krylov basis V and
+ * the preconditioned basis Z never leave the device, the dot products, norms and updates are kernels on one stream,
+ * and the host keeps only H, g and the Givens rotations.  Opt-in: the host entries above are unchanged. */
+
+/* d_y = Op(d_x) on DEVICE vectors of n doubles: enqueue the work on `stream` (a hipStream_t) and return BBFMM_OK or
+ * an error code (which the solver returns as is).  d_x and d_y never alias. */
+typedef int (*bbfmm_apply_device_fn)(void *user, const double *d_x, double *d_y, int64_t n, void *stream);
+
+/* IterativeSolver::matvec (rbf.rs:105-117) on device vectors: the device twin of bbfmm_rbf_system_apply.  Created once
+ * from the tree, basis_size, the N x basis_size column-major monomial matrix (host pointer, ld >= N; NULL with
+ * basis_size 0) and the nugget; the matrix is uploaded once.  An apply is bbfmm_matvec_device followed by one kernel:
+ * y[i] += nugget x[i] + sum_q P[i,q] x[N+q] (the polynomial sum first, then added, as the host entry does), and
+ * y[N .. N+basis_size) = 0 (rbf.rs:1346).  BBFMM_DEVICE_ERROR with a message in bbfmm_last_error(tree) on a
+ * BBFMM_FLAG_HOST_ONLY handle, BBFMM_UNSUPPORTED with a message on a device group (bbfmm_create_on_devices). */
+typedef struct bbfmm_rbf_system_device bbfmm_rbf_system_device;
+int bbfmm_rbf_system_device_create(bbfmm_handle *tree, int64_t basis_size, const double *monomial_matrix, int64_t ld,
+                                   double nugget, bbfmm_rbf_system_device **out);
+void bbfmm_rbf_system_device_destroy(bbfmm_rbf_system_device *s);
+/* a bbfmm_apply_device_fn: user = bbfmm_rbf_system_device*, n = N + basis_size, stream = bbfmm_stream(tree)
+ * (any other stream: BBFMM_BAD_ARGUMENT) */
+int bbfmm_rbf_system_apply_device(void *user, const double *d_x, double *d_y, int64_t n, void *stream);
+
+/*
+ * fgmres (iterative_solvers.rs:38-281) with b, x0 (NULL: zero) and x as DEVICE pointers and everything enqueued on
+ * `stream`: the algorithm of bbfmm_fgmres statement for statement (restarts, Givens rotations on the host, the
+ * residual measure from |g[j+1]| and from the true residual at a restart, the zero-residual return, the iteration
+ * count, the callback).  Reductions run in two stages without atomics -- one partial per 65,536 elements, the
+ * partials added in index order -- so a solve is bitwise reproducible and differs from bbfmm_fgmres only by the order
+ * of summation inside a chunk.  The host waits for the stream once per inner iteration (the new Hessenberg column and
+ * the norm, max_inner_iterations + 2 doubles at most) and once more per restart or return.  Work memory:
+ * 2 max_inner_iterations + 3 vectors of n doubles, allocated per call and freed on every return path.
+ * Native operators (bbfmm_rbf_system_apply_device, bbfmm_schwarz_apply_device) must belong to one tree whose stream is
+ * `stream`: BBFMM_BAD_ARGUMENT otherwise.  `stream` is a created stream: the null stream is refused (BBFMM_BAD_ARGUMENT) --
+ * work that the solver and a caller's operator (torch) enqueue on it was measured not to stay in order.
+ */
+int bbfmm_fgmres_device(int64_t n, bbfmm_apply_device_fn a, void *a_user, const double *d_b, bbfmm_apply_device_fn m,
+                        void *m_user, const double *d_x0, int32_t max_outer_iterations, int32_t max_inner_iterations,
+                        int32_t tolerance_type, double tolerance, bbfmm_iteration_fn callback, void *cb_user,
+                        double *d_x, int64_t *iterations, double *final_residual, void *stream);
+
+/* schwarz_ddm_solver (iterative_solvers.rs:229-281) in the same way: one wait per iteration (the residual norm). */
+int bbfmm_schwarz_ddm_solver_device(int64_t n, bbfmm_apply_device_fn matvec, void *a_user, const double *d_rhs,
+                                    bbfmm_apply_device_fn m, void *m_user, int32_t max_iterations,
+                                    int32_t tolerance_type, double tolerance, bbfmm_iteration_fn callback,
+                                    void *cb_user, double *d_x, int64_t *iterations, double *final_residual,
+                                    void *stream);
+
+/* Test hook: one vector kernel of the device solvers on the caller's HOST vectors (uploaded, run, downloaded).
+ *   op 0: out = a - b                         scalars_out[0] = sum out^2, [1] = max |out|   (the fused residual pass)
+ *   op 1: out = alpha' a
+ *   op 2: out = b + alpha' a                  scalars_out[0] = <c, out> (c NULL: <out, out>)
+ *   op 3: scalars_out[0] = <a, b>             op 4: ||a||_2         op 5: max |a|
+ *   op 6: out = b + sum_c coeffs[c] a[:, c]   (a: n x count column-major, the solution update)
+ * alpha' is read from a device scalar holding alpha: alpha_mode 0 alpha, 1 -alpha, 2 1/alpha (0 when alpha == 0);
+ * alpha_mode 3 passes alpha as a kernel argument.  offset (0 or 1): the device vectors start that many doubles past a
+ * 16-byte boundary (1: the kernels take their 8-byte path).  Reductions need n >= 1. */
+int bbfmm_debug_solver_vector_op(int32_t op, int32_t alpha_mode, int64_t n, const double *a, const double *b,
+                                 const double *c, double alpha, int32_t count, const double *coeffs, int32_t offset,
+                                 double *out, double *scalars_out);
+
 /* ------------------------------------------------------------------ domain decomposition (host part)
  * DDMTree::new (ferreus_rbf/src/preconditioning/domain_decomposition.rs:67-347), SURVEY.md 8(f)-1:
  * the multi-level overlapping decomposition of the Schwarz preconditioner -- which points form which
@@ -1002,6 +1063,12 @@ int bbfmm_ddm_debug_level_factor(const bbfmm_ddm_debug_level *h, double *out);
 int bbfmm_ddm_debug_level_solve(bbfmm_ddm_debug_level *h, const double *values, double *out, int64_t n, int32_t all_points);
 /* a bbfmm_apply_fn: user = bbfmm_schwarz*, vectors of N + basis_size doubles */
 int bbfmm_schwarz_apply(void *user, const double *residual, double *correction, int64_t n);
+/* schwarz_preconditioner (schwarz.rs:32-82) as a bbfmm_apply_device_fn: the same sweep with the residual taken from and
+ * the correction left in DEVICE memory (device-to-device copies in place of the two bus legs; the polynomial tail is
+ * written by a kernel).  user = bbfmm_schwarz*, n = N + basis_size, stream = the tree's stream (any other:
+ * BBFMM_BAD_ARGUMENT).  The coarse domain's polynomial tail is solved on the host as in bbfmm_schwarz_apply, so an apply
+ * with a drift waits for the stream once; a sharded preconditioner is refused (BBFMM_UNSUPPORTED). */
+int bbfmm_schwarz_apply_device(void *user, const double *d_residual, double *d_correction, int64_t n, void *stream);
 /* Test hook: bbfmm_schwarz_apply with the device vectors of the sweep copied out after every level step.  The apply and the
  * hook run the same loop; the hook alone waits for the stream and copies (unsharded handles only).
  *   _trace_steps: the level steps of one apply (2 (levels - 1), or 1 for a single level)

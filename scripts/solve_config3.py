@@ -28,6 +28,10 @@ ap.add_argument("--shared-basis", action="store_true",
                 help="extension: ONE tree with BBFMM_FLAG_M2L_SHARED_BASIS for the operator and the preconditioner (the "
                      "operator's products then carry the basis' truncation, about epsilon)")
 ap.add_argument("--clustered", action="store_true", help="points from a mixture of 12 Gaussian clusters instead of uniform")
+ap.add_argument("--vectors", choices=["host", "device", "both"], default="host",
+                help="where FGMRES keeps its vectors (solvers.fgmres vectors=); device needs one tree for the operator and the "
+                     "preconditioner; both: the two solves one after the other on the same operators, one result line each")
+ap.add_argument("--full-history", action="store_true", help="print the residuals with all their digits")
 a = ap.parse_args()
 kid = {"LinearRbf": 0, "ThinPlateSplineRbf": 1, "CubicRbf": 2, "Spheroidal3Rbf": 3}[a.kernel]
 n = a.points
@@ -53,15 +57,21 @@ pre = SchwarzPreconditioner(ptree, pts, st, DDMParams(leaf_threshold=a.leaf_thre
 t_ddm = time.time() - t0
 op = S.RbfSystemOperator(tree, st.basis_size, pre.monomial_matrix, a.nugget)
 rhs = np.concatenate([vals, np.zeros(st.basis_size)])
-marks = []
-t0 = time.time()
-x, hist = S.fgmres(op, rhs, pre, None, 20, 5, S.FittingAccuracy(a.tol), callback=lambda it, r, p: marks.append(time.time()))
-t_solve = time.time() - t0
 idx = rng.choice(n, 2000, replace=False)
-fit = op(x)[idx]
-print(json.dumps({"points": n, "kernel": a.kernel, "order": a.order, "precon_order": a.precon_order or a.order, "precon_shared_basis": bool(a.precon_shared_basis), "shared_basis": bool(a.shared_basis), "levels": pre.num_levels, "basis": st.basis_size,
-                  "fmm_tree_build_s": round(t_tree, 2), "ddm_build_and_factor_s": round(t_ddm, 2),
-                  "solve_s": round(t_solve, 2), "iterations": len(hist),
-                  "s_per_iteration": round(t_solve / max(len(hist), 1), 3),
-                  "residual_history": [float("%.3e" % r) for _, r in hist],
-                  "max_fit_error_on_sample": float(np.abs(fit - vals[idx]).max())}))
+
+
+def solve(vectors):
+    t0 = time.time()
+    x, hist = S.fgmres(op, rhs, pre, None, 20, 5, S.FittingAccuracy(a.tol), vectors=vectors)
+    t_solve = time.time() - t0
+    fit = op(x)[idx]
+    print(json.dumps({"vectors": vectors, "points": n, "kernel": a.kernel, "order": a.order, "precon_order": a.precon_order or a.order, "precon_shared_basis": bool(a.precon_shared_basis), "shared_basis": bool(a.shared_basis), "levels": pre.num_levels, "basis": st.basis_size,
+                      "fmm_tree_build_s": round(t_tree, 2), "ddm_build_and_factor_s": round(t_ddm, 2),
+                      "solve_s": round(t_solve, 2), "iterations": len(hist),
+                      "s_per_iteration": round(t_solve / max(len(hist), 1), 3),
+                      "residual_history": [r if a.full_history else float("%.3e" % r) for _, r in hist],
+                      "max_fit_error_on_sample": float(np.abs(fit - vals[idx]).max())}), flush=True)
+
+
+for vectors in (["host", "device"] if a.vectors == "both" else [a.vectors]):
+    solve(vectors)
