@@ -16,11 +16,11 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libferreus_bbfmm_hip.so")
 
-HOST_SOURCES = ["tree.cpp", "operators.cpp", "fmm_tree.cpp", "fmm_m2l_tables.cpp", "fmm_m2l_shared_basis.cpp", "fmm_m2l_debug.cpp", "fmm_plans.cpp", "device_group.cpp", "capi.cpp", "solver.cpp", "solver_device.cpp", "ddm.cpp", "ddm_solver.cpp", "schwarz.cpp", "interpolant.cpp", "closure_triangulate.cpp"]
+HOST_SOURCES = ["tree.cpp", "operators.cpp", "fmm_tree.cpp", "fmm_m2l_tables.cpp", "fmm_m2l_shared_basis.cpp", "fmm_m2l_debug.cpp", "fmm_plans.cpp", "device_group.cpp", "capi.cpp", "capi_isosurface.cpp", "capi_fields.cpp", "capi_evaluate.cpp", "capi_debug.cpp", "solver.cpp", "solver_device.cpp", "ddm.cpp", "ddm_solver.cpp", "schwarz.cpp", "interpolant.cpp", "closure_triangulate.cpp"]
 HIP_SOURCES = ["device_l2p.hip", "device_p2p.hip", "device_wx.hip", "device_p2m.hip", "device_m2l.hip", "device_transfer.hip", "device_gather.hip", "device_selftest.hip",  # longest first
                "ddm_kernels.hip", "targets.hip", "schwarz_kernels.hip", "tree_device.hip", "tree_lists_device.hip", "isosurface.hip", "isosurface_finish.hip", "isosurface_closure.hip", "isosurface_intersect.hip", "isosurface_follow.hip", "interpolant_terms.hip", "field_program.hip", "evaluate_grid.hip", "solver_vectors.hip"]
 HEADERS = ["morton.hpp", "tree.hpp", "parallel.hpp", "kernels.hpp", "operators.hpp", "device.hpp", "device_common.hpp", "device_direct.hpp", "m2l_basis_rows.hpp",
-           "fmm_tree.hpp", "fmm_tree_impl.hpp", "device_group.hpp", "targets.hpp", "ddm.hpp", "ddm_solver.hpp", "ddm_monomials.hpp", "schwarz_kernels.hpp", "tree_device.hpp", "isosurface.hpp", "isosurface_curvature.hpp", "isosurface_intersect.hpp", "isosurface_closure.hpp", "closure_triangulate.hpp", "interpolant_terms.hpp", "field_program.hpp", "evaluate_grid.hpp", "solver_vectors.hpp", os.path.join(ROOT, "include", "ferreus_bbfmm_hip.h")]
+           "fmm_tree.hpp", "fmm_tree_impl.hpp", "device_group.hpp", "targets.hpp", "ddm.hpp", "ddm_solver.hpp", "ddm_monomials.hpp", "schwarz_kernels.hpp", "tree_device.hpp", "isosurface.hpp", "isosurface_curvature.hpp", "isosurface_intersect.hpp", "isosurface_closure.hpp", "closure_triangulate.hpp", "interpolant_terms.hpp", "field_program.hpp", "evaluate_grid.hpp", "solver_vectors.hpp", "capi_handle.hpp", "capi_isosurface.hpp", os.path.join(ROOT, "include", "ferreus_bbfmm_hip.h")]
 
 
 def _digest(paths: list[str], extra: str = "") -> str:

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "capi_handle.hpp"
 #include "ferreus_bbfmm_hip.h"
 #include "interpolant_terms.hpp"
 #include "kernels.hpp"

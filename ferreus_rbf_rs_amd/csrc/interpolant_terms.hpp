@@ -16,15 +16,12 @@
 #endif
 
 struct bbfmm_interpolant_terms; // ferreus_bbfmm_hip.h
-struct bbfmm_handle;
 
 namespace bbfmm {
 
 struct InterpolantTerms;
 // the checked copy of the ABI's struct (interpolant.cpp); false on a bad one
 bool terms_from_abi(const ::bbfmm_interpolant_terms *in, InterpolantTerms *t);
-// the message bbfmm_last_error returns for h (capi.cpp)
-void set_handle_error(::bbfmm_handle *h, const char *message);
 
 constexpr int kMaxMonomials = 10; // quadratic in 3-D
 

@@ -183,6 +183,13 @@ struct Lattice {
     int64_t n_keys = 0, n_nodes = 0; // |K| and |E|
     // per row (j, k) of the box (index k * nj + j): the i ranges [begin, end] of E and of the keys (begin > end: none)
     std::vector<int32_t> e_rows, key_rows; // 2 ints per row
+    // the world coordinates of the first and the last node of the box on every axis
+    void node_box(double *box_lo, double *box_hi) const {
+        for (int a = 0; a < 3; ++a) {
+            box_lo[a] = lo_world[a] + static_cast<double>(lo[a]) * spacing[a];
+            box_hi[a] = lo_world[a] + static_cast<double>(lo[a] + dims[a] - 1) * spacing[a];
+        }
+    }
 };
 
 // Validates (finite extents with lo <= hi, finite resolution > 0, a lattice of at most 2^36 box nodes) and fills *out.

@@ -4,6 +4,7 @@
 // stream once per inner iteration (the new Hessenberg column and the norm) and once per restart or return.  Also the
 // device twin of the RBF system operator (rbf.rs:105-117) and the test hook of the vector kernels.
 #include "../../include/ferreus_bbfmm_hip.h"
+#include "capi_handle.hpp"
 #include "solver_vectors.hpp"
 
 #include <chrono>

@@ -54,9 +54,7 @@ struct SolverTail {
 };
 void launch_solver_set_tail(SolverTail t, int32_t count, double *out, hipStream_t s);
 
-// capi.cpp / schwarz.cpp: what the drivers ask the native operators' owners
-bool handle_is_host_only(const bbfmm_handle *h);
-void set_handle_error(bbfmm_handle *h, const char *message);
+// schwarz.cpp: the tree a Schwarz preconditioner was built on
 bbfmm_handle *schwarz_tree(const bbfmm_schwarz *h);
 // solver_device.cpp: the tree a native device operator belongs to (nullptr: not a native operator)
 bbfmm_handle *rbf_system_device_tree(const void *user);
