@@ -255,6 +255,12 @@ int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit) {
     return BBFMM_OK;
 }
 
+int bbfmm_debug_leaf_runs(const bbfmm_handle *h, int32_t *counts) {
+    if (!h || !counts) return BBFMM_BAD_ARGUMENT;
+    h->tree.debug_leaf_runs(counts);
+    return BBFMM_OK;
+}
+
 // Debug only: values per row of the multipoles in stage 1's parity basis (what debug_get_coefficients('P') returns per cell);
 // 0 when the handle has none.
 int bbfmm_debug_m2l_parity_len(const bbfmm_handle *h, int32_t *len) {

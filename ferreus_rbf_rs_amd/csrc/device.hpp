@@ -28,6 +28,7 @@ constexpr int kM2lBlkTwoDst = 1 << 30; // flag in M2lClass::blk_t0: some column 
 struct DevCheb { // lives in device memory; kernels take a pointer
     int p, d, n, n_pad;
     double polyn[kMaxOrder * kMaxOrder]; // T_k(node_j), row j
+    double q[kMaxOrder * kMaxOrder];     // S_j(x) = sum_k T_k(x) q[j][k]: 2 T_k(node_j) / p, k = 0: (2 T_0 - 1) / p (cheb_S_reg)
     double nodes[kMaxOrder];
     double xfer[2 * kMaxOrder * kMaxOrder]; // [side][child node a][parent node i]
 };
@@ -302,13 +303,26 @@ void launch_p2l(const KernelSpec &ks, const ChebRef &ch, int n_jobs, const int32
                 const int64_t *run_ptr, const int32_t *runs, const double *centers,
                 const double *lengths, const double *const *src_xyz, const double *w_sorted,
                 int64_t N, int K, int64_t C, double *L, hipStream_t s);
+// L2P over runs of leaves (values only, orders with at most kL2pRunMaxNodes nodes: l2p_runs_supported()).  A run is 2 to
+// kL2pRunLeaves consecutive jobs of the job list whose target ranges abut (tgt_end[j] == tgt_begin[j + 1]), each with at
+// most 64 targets and kL2pRunTargets in all: runs[2 r] its first job, runs[2 r + 1] the number of its jobs.  The jobs that
+// are in no run come a second time as a job list of their own (rest_*), for the one-leaf kernel.
+constexpr int kL2pRunLeaves = 8, kL2pRunTargets = 256, kL2pRunMaxNodes = 512;
+struct L2pRuns {
+    int n_runs = 0;
+    const int32_t *runs = nullptr;
+    int n_rest = 0;
+    const int32_t *rest_cell = nullptr, *rest_begin = nullptr, *rest_end = nullptr;
+};
+bool l2p_runs_supported(int p, int d);
 void launch_l2p(const ChebRef &ch, int n_jobs, const int32_t *leaf_cells, const int32_t *tgt_begin,
                 const int32_t *tgt_end, const double *centers, const double *lengths,
                 const double *const *tgt_xyz, int64_t n_tgt, int K, int64_t C, const double *L,
                 double *out_sorted, double *grad_sorted, hipStream_t s, const int32_t *perm = nullptr,
-                double *user_out = nullptr, int64_t ldo = 0);
+                double *user_out = nullptr, int64_t ldo = 0, const L2pRuns *runs = nullptr);
 // (perm / user_out / ldo, all or none: the potentials go to user_out[k ldo + perm[t]] = out_sorted[k n_tgt + t] + y, the
-// caller's order, and out_sorted keeps the near field alone; every target must lie in one job)
+// caller's order, and out_sorted keeps the near field alone; every target must lie in one job.
+// runs: NULL, or the job list's runs -- taken without gradients where l2p_runs_supported(), ignored otherwise)
 
 // Orders the device Chebyshev kernels are instantiated for (3-D: p <= 12).
 bool l2p_order_supported(int p, int d);

@@ -41,9 +41,11 @@ __device__ inline void axis_sizes(int p, int d, int &P0, int &P1, int &P2) {
 
 // ------------------------------------------------------------------ Chebyshev factors in registers
 // S_j(x) = (2 sum_k T_k(x) T_k(node_j) - 1)/p ; dS_j = (2/p) sum_k T'_k(x) T_k(node_j)
-// (chebyshev.rs:47-142)
+// (chebyshev.rs:47-142), with the constants in the table: q = DevCheb::q, q[j][k] = 2 T_k(node_j) / p and q[j][0] = 1 / p, so
+// S_j = sum_k T_k(x) q[j][k] and dS_j = sum_{k >= 1} T'_k(x) q[j][k] -- P multiply-adds per factor and no division (the
+// IEEE f64 division is a dozen instructions around a quarter-rate v_rcp_f64; there were P of them per axis and point).
 template <int P, bool GRAD>
-__device__ inline void cheb_S_reg(double x, const double *__restrict__ polyn, double (&S)[P], double (&dS)[P]) {
+__device__ inline void cheb_S_reg(double x, const double *__restrict__ q, double (&S)[P], double (&dS)[P]) {
     double T[P], dT[P];
     T[0] = 1.0;
     dT[0] = 0.0;
@@ -58,15 +60,15 @@ __device__ inline void cheb_S_reg(double x, const double *__restrict__ polyn, do
     }
 #pragma unroll
     for (int j = 0; j < P; ++j) {
-        double s = 0.0, ds = 0.0;
+        double s = q[j * P], ds = 0.0; // T_0 = 1, T'_0 = 0
 #pragma unroll
-        for (int k = 0; k < P; ++k) {
-            const double pk = polyn[j * P + k];
-            s += T[k] * pk;
-            if (GRAD) ds += dT[k] * pk;
+        for (int k = 1; k < P; ++k) {
+            const double qk = q[j * P + k];
+            s += T[k] * qk;
+            if (GRAD) ds += dT[k] * qk;
         }
-        S[j] = (s * 2.0 - 1.0) / (double)P;
-        dS[j] = GRAD ? ds * (2.0 / (double)P) : 0.0;
+        S[j] = s;
+        dS[j] = GRAD ? ds : 0.0;
     }
 }
 

@@ -27,18 +27,18 @@ __global__ __launch_bounds__((64 * p2m_waves<P, D>())) void p2m_kernel(const Dev
     constexpr int P1 = D > 1 ? P : 1, P2 = D > 2 ? P : 1, NPAIR = P1 * P2;
     constexpr int NPASS = (NPAIR + 63) / 64;
     constexpr int SROW = 3 * P + P2M_KB; // per point: S0[P], S1[P], S2[P], w[KB]
-    __shared__ double s_polyn[P * P];
+    __shared__ double s_q[P * P];
     constexpr int WAVES = p2m_waves<P, D>();
     __shared__ double s_pts[WAVES][P2M_PTS][SROW];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int i = tid; i < P * P; i += 64 * WAVES) s_polyn[i] = chp->polyn[i];
+    for (int i = tid; i < P * P; i += 64 * WAVES) s_q[i] = chp->q[i];
     __syncthreads();
     const int job = blockIdx.x * WAVES + wave;
     if (job >= n_leaves) return; // whole wave; no block barrier below
     const int n_pad = chp->n_pad;
     const int cell = leaf_cells[job];
     const int b = pt_begin[cell], e = pt_end[cell];
-    const double len = lengths[cell];
+    const double r = 1.0 / (lengths[cell] * 0.5); // one division per leaf, none per point
     const double cc[3] = {centers[cell * 3 + 0], centers[cell * 3 + 1], centers[cell * 3 + 2]};
     double(*sp)[SROW] = s_pts[wave];
     for (int k0 = 0; k0 < K; k0 += P2M_KB) {
@@ -54,18 +54,18 @@ __global__ __launch_bounds__((64 * p2m_waves<P, D>())) void p2m_kernel(const Dev
             if (lane < npts) {
                 const int pt = base + lane;
                 double S[P], dS[P];
-                cheb_S_reg<P, false>((src.x[pt] - cc[0]) / (len * 0.5), s_polyn, S, dS); // chebyshev.rs:841-845
+                cheb_S_reg<P, false>((src.x[pt] - cc[0]) * r, s_q, S, dS); // chebyshev.rs:841-845
 #pragma unroll
                 for (int jx = 0; jx < P; ++jx) sp[lane][jx] = S[jx];
                 if (D > 1) {
-                    cheb_S_reg<P, false>((src.y[pt] - cc[1]) / (len * 0.5), s_polyn, S, dS);
+                    cheb_S_reg<P, false>((src.y[pt] - cc[1]) * r, s_q, S, dS);
 #pragma unroll
                     for (int jx = 0; jx < P; ++jx) sp[lane][P + jx] = S[jx];
                 } else {
                     sp[lane][P] = 1.0;
                 }
                 if (D > 2) {
-                    cheb_S_reg<P, false>((src.z[pt] - cc[2]) / (len * 0.5), s_polyn, S, dS);
+                    cheb_S_reg<P, false>((src.z[pt] - cc[2]) * r, s_q, S, dS);
 #pragma unroll
                     for (int jx = 0; jx < P; ++jx) sp[lane][2 * P + jx] = S[jx];
                 } else {
@@ -133,15 +133,15 @@ __global__ __launch_bounds__(64 * P2M_WAVES) void p2m_mfma_kernel(const DevCheb 
     constexpr int SROW = 3 * P + 2; // per point: S0[P], S1[P], S2[P], w, one spare (rows start 16-byte aligned for even P)
     __shared__ double s_pts[P2M_WAVES][64][SROW];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // (the node values T_k(node_j) come through the scalar cache as SGPR operands: the same 8 P^2 bytes for every wave;
+    // (the table entries q[j][k] (2 T_k(node_j) / p) come through the scalar cache as SGPR operands: the same 8 P^2 bytes for every wave;
     // staged in LDS the compiler kept all P^2 of them in vector registers across the three axes)
-    const double *__restrict__ s_polyn = chp->polyn;
+    const double *__restrict__ s_q = chp->q;
     const int job = blockIdx.x * P2M_WAVES + wave;
     if (job >= n_leaves) return; // whole wave; no block barrier below
     const int n_pad = chp->n_pad;
     const int cell = leaf_cells[job];
     const int b = pt_begin[cell], e = pt_end[cell];
-    const double len = lengths[cell];
+    const double r = 1.0 / (lengths[cell] * 0.5); // one division per leaf, none per point
     const double cc[3] = {centers[cell * 3 + 0], centers[cell * 3 + 1], centers[cell * 3 + 2]};
     double(*sp)[SROW] = s_pts[wave];
     const int hi = lane >> 4, blk = (lane >> 2) & 3, lo = lane & 3;
@@ -165,13 +165,13 @@ __global__ __launch_bounds__(64 * P2M_WAVES) void p2m_mfma_kernel(const DevCheb 
                 double S[P], dS[P];
                 const int pt = base + min(lane, npts - 1);
                 const bool live = lane < npts;
-                cheb_S_reg<P, false>((src.x[pt] - cc[0]) / (len * 0.5), s_polyn, S, dS); // chebyshev.rs:841-845
+                cheb_S_reg<P, false>((src.x[pt] - cc[0]) * r, s_q, S, dS); // chebyshev.rs:841-845
 #pragma unroll
                 for (int jx = 0; jx < P; ++jx) sp[lane][jx] = live ? S[jx] : 0.0;
-                cheb_S_reg<P, false>((src.y[pt] - cc[1]) / (len * 0.5), s_polyn, S, dS);
+                cheb_S_reg<P, false>((src.y[pt] - cc[1]) * r, s_q, S, dS);
 #pragma unroll
                 for (int jx = 0; jx < P; ++jx) sp[lane][P + jx] = live ? S[jx] : 0.0;
-                cheb_S_reg<P, false>((src.z[pt] - cc[2]) / (len * 0.5), s_polyn, S, dS);
+                cheb_S_reg<P, false>((src.z[pt] - cc[2]) * r, s_q, S, dS);
 #pragma unroll
                 for (int jx = 0; jx < P; ++jx) sp[lane][2 * P + jx] = live ? S[jx] : 0.0;
             }

@@ -41,7 +41,55 @@ int FmmTree::build_source_target_set() {
     CHK(dupload(&ts.w_tgt_end, wte));
     CHK(dupload(&ts.w_begin, wb));
     CHK(dupload(&ts.w_end, we));
+    if ((leaf_mask_ & 1u) && l2p_runs_supported(cheb_.p, cheb_.d)) CHK(build_l2p_runs(&ts, jc, tb, te));
     CHK(build_sym_runs(&ts, jc, 0, t.n_points));
+    return BBFMM_OK;
+}
+
+// The runs of device.hpp L2pRuns for a job list known to the host, cut greedily in job order: a job of at most 64 targets
+// joins the open run while its range begins where the run ends and the run stays within kL2pRunLeaves jobs and
+// kL2pRunTargets targets; a run of one job, and every larger job, goes to the list for the one-leaf kernel.
+int FmmTree::build_l2p_runs(TargetSet *ts, const std::vector<int32_t> &jc, const std::vector<int32_t> &tb,
+                            const std::vector<int32_t> &te) {
+    std::vector<int32_t> runs, rc, rb, re;
+    const int64_t nj = static_cast<int64_t>(jc.size());
+    int64_t first = 0, count = 0;
+    auto close = [&]() {
+        if (count >= 2) {
+            runs.push_back(static_cast<int32_t>(first));
+            runs.push_back(static_cast<int32_t>(count));
+        } else if (count == 1) {
+            rc.push_back(jc[static_cast<size_t>(first)]);
+            rb.push_back(tb[static_cast<size_t>(first)]);
+            re.push_back(te[static_cast<size_t>(first)]);
+        }
+        count = 0;
+    };
+    for (int64_t j = 0; j < nj; ++j) {
+        const size_t sj = static_cast<size_t>(j);
+        const int64_t size = static_cast<int64_t>(te[sj]) - tb[sj];
+        if (size < 0 || size > 64) { // more than one batch: the one-leaf kernel
+            close();
+            first = j;
+            count = 1;
+            close();
+            continue;
+        }
+        if (count > 0 && (tb[sj] != te[sj - 1] || count == kL2pRunLeaves ||
+                          static_cast<int64_t>(te[sj]) - tb[static_cast<size_t>(first)] > kL2pRunTargets))
+            close();
+        if (count == 0) first = j;
+        ++count;
+    }
+    close();
+    ts->n_l2p_runs = ts->n_l2p_rest = 0;
+    if (runs.empty() || static_cast<int64_t>(runs.size() / 2) < l2p_runs_min_) return BBFMM_OK; // the one-leaf kernel for all
+    ts->n_l2p_runs = static_cast<int>(runs.size() / 2);
+    ts->n_l2p_rest = static_cast<int>(rc.size());
+    CHK(dupload(&ts->l2p_runs, runs));
+    CHK(dupload(&ts->l2p_rest_cell, rc));
+    CHK(dupload(&ts->l2p_rest_begin, rb));
+    CHK(dupload(&ts->l2p_rest_end, re));
     return BBFMM_OK;
 }
 
@@ -536,6 +584,11 @@ void FmmTree::free_target_set(TargetSet *ts) {
     dfree(&ts->job_cell);
     dfree(&ts->tgt_begin);
     dfree(&ts->tgt_end);
+    dfree(&ts->l2p_runs);
+    dfree(&ts->l2p_rest_cell);
+    dfree(&ts->l2p_rest_begin);
+    dfree(&ts->l2p_rest_end);
+    ts->n_l2p_runs = ts->n_l2p_rest = 0;
     dfree(&ts->w_tgt_begin);
     dfree(&ts->w_tgt_end);
     dfree(&ts->w_begin);

@@ -373,6 +373,7 @@ int FmmTree::upload() {
     hc.n = ops_.n;
     hc.n_pad = round_up(ops_.n, 32);
     std::copy(ops_.polyn.begin(), ops_.polyn.end(), hc.polyn);
+    std::copy(ops_.q.begin(), ops_.q.end(), hc.q);
     std::copy(ops_.nodes.begin(), ops_.nodes.end(), hc.nodes);
     std::copy(ops_.xfer.begin(), ops_.xfer.end(), hc.xfer);
     CHK(dalloc(&d_cheb_, 1));
@@ -600,6 +601,14 @@ int FmmTree::upload() {
         const char *e = std::getenv("BBFMM_FUSED_PASSES"); // read per handle
         fused_mask_ = e ? static_cast<unsigned>(std::atoi(e)) & 15u : 15u;
         if (!(fused_mask_ & 2u)) fused_mask_ &= ~4u;
+        const char *lp = std::getenv("BBFMM_LEAF_PASSES"); // read per handle
+        leaf_mask_ = lp ? static_cast<unsigned>(std::atoi(lp)) & 1u : 1u;
+        // fewer runs than four workgroups to a CU: the one-leaf kernel, whose workgroups are shorter (BBFMM_L2P_RUNS_MIN)
+        int n_cu = 256, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+            n_cu = 256;
+        const char *rm = std::getenv("BBFMM_L2P_RUNS_MIN");
+        l2p_runs_min_ = rm ? std::max(0, std::atoi(rm)) : 4 * n_cu;
         std::vector<uint8_t> has_m2l(static_cast<size_t>(C), 0), has_x(static_cast<size_t>(C), 0);
         fused_flags_ok_ = true;
         for (const M2lTileDesc &td : m2l_tiles2_h_) {
@@ -1196,9 +1205,10 @@ int FmmTree::leaf_pass_near(const TargetSet &ts, int k, bool with_grads, hipStre
 int FmmTree::leaf_pass_far(const TargetSet &ts, int k, bool with_grads, double *user_out, int64_t ldo) {
     const int64_t C = tree_.n_cells();
     double *grad = with_grads ? ts.grad.p : nullptr;
+    const L2pRuns runs{ts.n_l2p_runs, ts.l2p_runs.p, ts.n_l2p_rest, ts.l2p_rest_cell.p, ts.l2p_rest_begin.p, ts.l2p_rest_end.p};
     phase_begin();
     launch_l2p(cheb_, ts.n_jobs, ts.job_cell.p, ts.tgt_begin.p, ts.tgt_end.p, d_centers_.p, d_lengths_.p, ts.xyz_ptr,
-               ts.m, k, C, d_L_.p, ts.out.p, grad, stream_, user_out ? ts.perm.p : nullptr, user_out, ldo);
+               ts.m, k, C, d_L_.p, ts.out.p, grad, stream_, user_out ? ts.perm.p : nullptr, user_out, ldo, &runs);
     phase_end(kPhL2P);
     HIPCHK(hipGetLastError());
     return BBFMM_OK;

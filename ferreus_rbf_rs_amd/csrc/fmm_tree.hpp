@@ -80,6 +80,10 @@ struct TargetSet { // targets sorted by leaf, resident on the device
     DevBuf<int32_t> perm;      // sorted position -> caller's row
     DevBuf<int32_t> job_cell, tgt_begin, tgt_end; // leaves with targets
     int n_jobs = 0;
+    // the runs of abutting small jobs and the jobs outside them (device.hpp L2pRuns; the resident target set only, 0 runs:
+    // every job takes the one-leaf kernel)
+    int n_l2p_runs = 0, n_l2p_rest = 0;
+    DevBuf<int32_t> l2p_runs, l2p_rest_cell, l2p_rest_begin, l2p_rest_end;
     DevBuf<int32_t> w_tgt_begin, w_tgt_end;          // M2P jobs: (leaf, chunk of its W list)
     DevBuf<int64_t> w_begin, w_end;
     int n_w_jobs = 0;
@@ -320,6 +324,12 @@ class FmmTree {
     const std::vector<double> &m2l_flops_level() const { return m2l_flops_level_; } // per level: sum over its V pairs of 4 n r
     // Test hook: parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet).
     int debug_m2l_s2_last_ksplit() const { return m2l_s2_last_ksplit_; }
+    void debug_leaf_runs(int32_t *counts) const { // mask, runs, jobs outside the runs, jobs (of the resident target set)
+        counts[0] = static_cast<int32_t>(leaf_mask_);
+        counts[1] = src_targets_.n_l2p_runs;
+        counts[2] = src_targets_.n_l2p_rest;
+        counts[3] = src_targets_.n_jobs;
+    }
     // Test hook (host loops over the stacked M2L tables; needs BBFMM_FLAG_HOST_ONLY).
     // M, L: n_cells x n (cell-major, one rhs).  L is accumulated into.
     int debug_apply_m2l_tables_host(const double *M, double *L) const;
@@ -395,6 +405,7 @@ class FmmTree {
     int build_target_set_host(const double *x, int64_t m, int64_t ldx, TargetSet *ts, int64_t *bad_point_index,
                               std::vector<int32_t> *leaves_out);
     int build_source_target_set();
+    int build_l2p_runs(TargetSet *ts, const std::vector<int32_t> &jc, const std::vector<int32_t> &tb, const std::vector<int32_t> &te);
     int build_sym_runs(TargetSet *ts, const std::vector<int32_t> &job_cells, int64_t pb, int64_t pe, const std::vector<uint8_t> *part_active = nullptr);
     void free_target_set(TargetSet *ts);
     hipError_t columns_to_host(double *dst, int64_t ld, const double *d_src, int64_t m, int ncols);
@@ -496,6 +507,11 @@ class FmmTree {
     // is not cleared when no stage-2 launch of the matvec splits its contraction; bit 8: L2P of a matvec at the sources writes
     // the caller's order, no scatter pass.  0: the standalone passes everywhere.
     unsigned fused_mask_ = 15;
+    // The leaf passes over runs of leaves (BBFMM_LEAF_PASSES, read per handle).  Bit 1: L2P of the resident
+    // target set takes runs of abutting leaves, a lane per target (device.hpp L2pRuns), when there are at least l2p_runs_min_
+    // of them (BBFMM_L2P_RUNS_MIN; unset: four workgroups to a CU).  0: one leaf per wave everywhere.
+    unsigned leaf_mask_ = 1;
+    int l2p_runs_min_ = 1024;
     int mp_current_k_ = 0;               // right-hand sides whose Mp a whole, fused upward pass wrote for the present M (0: none)
     bool lp_pending_ = false;            // downward_m2l left the M2L part in Lp: downward_tail runs the fused L2L
     bool fused_flags_ok_ = false;        // d_has_m2l_ / d_has_x_ describe the whole-tree plan

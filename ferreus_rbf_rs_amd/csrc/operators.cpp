@@ -352,6 +352,14 @@ void precompute_operators(int p, int d, double radius, int depth, const KernelSp
     }
     o.polyn.resize(static_cast<size_t>(p) * p);
     for (int j = 0; j < p; ++j) cheb_T(p, o.nodes[j], &o.polyn[static_cast<size_t>(j) * p]);
+    o.q.resize(static_cast<size_t>(p) * p);
+    for (int j = 0; j < p; ++j) { // T_k(node_j) = cos(k theta_j)
+        const long double theta = acosl(-1.0L) * (static_cast<long double>(p - 1 - j) + 0.5L) / static_cast<long double>(p);
+        for (int k = 0; k < p; ++k) {
+            const long double t2 = k == 0 ? 1.0L : 2.0L * cosl(static_cast<long double>(k) * theta);
+            o.q[static_cast<size_t>(j) * p + k] = static_cast<double>(t2 / static_cast<long double>(p));
+        }
+    }
     o.nodes_nd.resize(static_cast<size_t>(n) * d);
     for (int i = 0; i < n; ++i)
         for (int a = 0; a < d; ++a) o.nodes_nd[static_cast<size_t>(i) * d + a] = o.nodes[cart_index(i, a, p, d)];

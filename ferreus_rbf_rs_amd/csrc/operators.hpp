@@ -22,6 +22,9 @@ struct Operators {
     int p = 0, d = 0, n = 0;
     std::vector<double> nodes;  // p, ascending (chebyshev.rs:32-40)
     std::vector<double> polyn;  // p x p row-major: polyn[j*p + k] = T_k(node_j) (chebyshev.rs:669-670)
+    // p x p row-major: S_j(x) = sum_k T_k(x) q[j*p + k], that is 2 T_k(node_j) / p and for k = 0 (2 T_0 - 1) / p = 1 / p,
+    // formed in long double and rounded once (the device's factor rows: no division, no trailing 2 s - 1)
+    std::vector<double> q;
     std::vector<double> nodes_nd; // n x d row-major, axis 0 slowest (chebyshev.rs:666)
     // 1-D child transfer S(child node a, parent node i), one p x p block per side
     // (chebyshev.rs:146-180): xfer[side][a*p + i].  The n x n M2M matrices of the

@@ -785,6 +785,13 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_m2l_s2_last_ksplit(self._h, ctypes.byref(ks)))
         return ks.value
 
+    def debug_leaf_runs(self) -> dict:
+        """The leaf passes over runs of leaves (BBFMM_LEAF_PASSES) of this handle: its mask, the runs of the resident target
+        set's job list, the jobs outside every run, and all its jobs."""
+        c = (ctypes.c_int32 * 4)()
+        self._raise(self._lib.bbfmm_debug_leaf_runs(self._h, c))
+        return {"mask": c[0], "runs": c[1], "rest": c[2], "jobs": c[3]}
+
     def debug_get_coefficients(self, which: str, k: int) -> np.ndarray:
         s = self.stats()
         n = s.n_nodes

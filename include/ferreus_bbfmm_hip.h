@@ -780,6 +780,9 @@ int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64
 int bbfmm_debug_m2l_table_digests(const bbfmm_handle *h, uint64_t *digests, int32_t cap, int32_t *n_out, double *flops_level,
                                   int32_t flops_cap, int32_t *n_levels_out);
 int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit); /* debug only */
+/* The leaf passes over runs of leaves (BBFMM_LEAF_PASSES): counts[0] the handle's mask, counts[1] the runs of the resident
+ * target set's job list, counts[2] its jobs outside every run, counts[3] all its jobs (0 runs: one leaf per wave). */
+int bbfmm_debug_leaf_runs(const bbfmm_handle *h, int32_t *counts); /* debug only */
 
 /* The Morton primitives of csrc/morton.hpp as the host tree build uses them (morton.rs:58-263; the
  * reference's byte lookup tables, morton_constants.rs:77-346, are replaced by bit arithmetic): checked
