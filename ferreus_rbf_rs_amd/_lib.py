@@ -156,6 +156,7 @@ SIGNATURES = {
     "bbfmm_debug_m2l_table_digests": (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p]),
     "bbfmm_debug_m2l_s2_last_ksplit": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_debug_leaf_runs": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_debug_group_state": (ctypes.c_int, [c_p, c_p, c_i64]),
     "bbfmm_debug_m2l_parity_len": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_debug_get_coefficients": (ctypes.c_int, [c_p, ctypes.c_char, c_i32, c_p]),
     "bbfmm_debug_morton_encode": (ctypes.c_uint64, [c_i32, c_p, ctypes.c_uint64]),

@@ -261,6 +261,20 @@ int bbfmm_debug_leaf_runs(const bbfmm_handle *h, int32_t *counts) {
     return BBFMM_OK;
 }
 
+// Debug only: what a device group holds and has queued (DeviceGroup::debug_state lists the values); a plain handle is one
+// part that owns itself, with zeros.  cap: room in out, at least 9 + the handle's parts.
+int bbfmm_debug_group_state(const bbfmm_handle *h, int64_t *out, int64_t cap) {
+    if (!h || !out) return BBFMM_BAD_ARGUMENT;
+    const int64_t need = bbfmm::DeviceGroup::kStateHeader + (h->group ? h->group->n_parts() : 1);
+    if (cap < need) return BBFMM_BAD_ARGUMENT;
+    std::fill(out, out + need, int64_t(0));
+    if (h->group)
+        h->group->debug_state(out);
+    else
+        out[0] = 1;
+    return BBFMM_OK;
+}
+
 // Debug only: values per row of the multipoles in stage 1's parity basis (what debug_get_coefficients('P') returns per cell);
 // 0 when the handle has none.
 int bbfmm_debug_m2l_parity_len(const bbfmm_handle *h, int32_t *len) {

@@ -89,7 +89,43 @@ struct ResidentWeights {
     explicit ResidentWeights(bool &f) : flag(f) { flag = true; }
     ~ResidentWeights() { flag = false; }
 };
+// FmmTree::mirrors_ for the length of one stage(): emptied again whatever way the call ends
+template <class V> struct MirrorScope {
+    V &m;
+    explicit MirrorScope(V &v) : m(v) { m.clear(); }
+    ~MirrorScope() { m.clear(); }
+};
 } // namespace
+
+int DeviceGroup::copy_between(double *dst, const Part &to, const double *src, const Part &from, size_t bytes, hipStream_t st) {
+    if (to.ldev != from.ldev && !(to.device == from.device && self_peer_refused_.load(std::memory_order_relaxed))) {
+        const hipError_t e = hipMemcpyPeerAsync(dst, to.device, src, from.device, bytes, st);
+        if (e == hipSuccess) {
+            n_peer_.fetch_add(1, std::memory_order_relaxed);
+            return BBFMM_OK;
+        }
+        if (to.device != from.device) return -static_cast<int>(e);
+        (void)hipGetLastError(); // own copies on one physical device and the runtime takes no peer copy within it
+        self_peer_refused_.store(true, std::memory_order_relaxed);
+    }
+    PHIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+    if (&to != &from) n_plain_.fetch_add(1, std::memory_order_relaxed);
+    return BBFMM_OK;
+}
+
+void DeviceGroup::debug_state(int64_t *out) const {
+    const FmmTree &P = *parts_[0].t;
+    out[0] = n_parts();
+    out[1] = own_copies_ ? 1 : 0;
+    out[2] = static_cast<int64_t>(P.mirrors_.size());
+    out[3] = P.mirror_pieces_;
+    out[4] = n_peer_.load();
+    out[5] = n_plain_.load();
+    out[6] = n_ev_w_waits_.load();
+    out[7] = n_w_in_.load();
+    out[8] = self_peer_refused_.load() ? 1 : 0;
+    for (int g = 0; g < n_parts(); ++g) out[kStateHeader + g] = parts_[static_cast<size_t>(g)].owner;
+}
 
 template <class F> int DeviceGroup::for_parts(F &&fn) {
     const int G = n_parts();
@@ -164,6 +200,10 @@ int DeviceGroup::init(FmmTree *primary, const GroupCreateArgs &a, const std::vec
         const char *e = std::getenv("BBFMM_GROUP_THREADS"); // 0: the calling thread queues every part's work (checker)
         threads_ = !e || std::atoi(e) != 0;
     }
+    {
+        const char *e = std::getenv("BBFMM_GROUP_OWN_COPIES"); // 1: parts on one device move data as parts on several do (checker)
+        own_copies_ = e && std::atoi(e) != 0;
+    }
     if (const char *e = std::getenv("BBFMM_GROUP_SHARD_MIN")) shard_min_rows_ = std::max<int64_t>(1, std::atoll(e));
     parts_.resize(static_cast<size_t>(G));
     parts_[0].t = primary;
@@ -171,9 +211,10 @@ int DeviceGroup::init(FmmTree *primary, const GroupCreateArgs &a, const std::vec
     for (int g = 0; g < G; ++g) {
         Part &p = parts_[static_cast<size_t>(g)];
         p.device = devices[static_cast<size_t>(g)];
+        p.ldev = own_copies_ ? g : p.device;
         p.owner = g;
         for (int h = 0; h < g; ++h)
-            if (parts_[static_cast<size_t>(h)].device == p.device) {
+            if (parts_[static_cast<size_t>(h)].ldev == p.ldev) {
                 p.owner = parts_[static_cast<size_t>(h)].owner;
                 distinct = false;
                 break;
@@ -321,7 +362,10 @@ int DeviceGroup::stage(const double *w, int64_t rows, int k, int64_t ldw) {
         o.t->bind_device();
         GHIP(hipStreamWaitEvent(o.t->stream_, p.ev_up, 0));
     }
-    P.mirrors_.clear();
+    // The mirrors name the other owners' d_w_in_ as they are NOW.  They must not outlive this call: the primary stages through
+    // the same function when it serves a call alone (FmmTree::put_weights), and the parts reallocate d_w_in_ on their own
+    // (matvec_device) -- a list left behind sent those weights to the other devices, towards memory that may have been freed.
+    const MirrorScope<decltype(P.mirrors_)> mirrors(P.mirrors_);
     for (size_t g = 1; g < parts_.size(); ++g) {
         Part &p = parts_[g];
         if (static_cast<size_t>(p.owner) != g) continue;
@@ -358,12 +402,13 @@ int DeviceGroup::run_upward(int k, const double *d_w_primary, int64_t ld_primary
         PHIP(hipStreamWaitEvent(t.stream_, p.ev_sent, 0)); // the last round's copies out of d_send
         const double *dw = o.t->d_w_in_.p;
         int64_t ld = n_;
-        if (d_w_primary && p.device == parts_[0].device) { // the caller's device buffer serves the parts on its device
+        if (d_w_primary && p.ldev == parts_[0].ldev) { // the caller's device buffer serves the parts on its device
             dw = d_w_primary;
             ld = ld_primary;
             if (g != 0) PHIP(hipStreamWaitEvent(t.stream_, ev_in_, 0));
         } else if (p.owner != g) {
             PHIP(hipStreamWaitEvent(t.stream_, o.ev_w, 0));
+            n_ev_w_waits_.fetch_add(1, std::memory_order_relaxed);
         }
         const int prc = t.matvec_partition_upward(dw, ld, k, p.d_send, p.comm, near_field);
         if (prc != BBFMM_OK) return prc;
@@ -372,11 +417,8 @@ int DeviceGroup::run_upward(int k, const double *d_w_primary, int64_t ld_primary
             for (int h = 0; h < G; ++h) PHIP(hipStreamWaitEvent(p.comm, parts_[static_cast<size_t>(h)].ev_sum, 0)); // slots free again
             for (int h = 0; h < G; ++h) {
                 const Part &q = parts_[static_cast<size_t>(h)];
-                double *dst = q.d_slots + static_cast<size_t>(g) * len;
-                if (q.device == p.device)
-                    PHIP(hipMemcpyAsync(dst, p.d_send, len * sizeof(double), hipMemcpyDeviceToDevice, p.comm));
-                else
-                    PHIP(hipMemcpyPeerAsync(dst, q.device, p.d_send, p.device, len * sizeof(double), p.comm));
+                const int crc = copy_between(q.d_slots + static_cast<size_t>(g) * len, q, p.d_send, p, len * sizeof(double), p.comm);
+                if (crc != BBFMM_OK) return crc;
             }
         }
         PHIP(hipEventRecord(p.ev_sent, p.comm));
@@ -654,6 +696,7 @@ int DeviceGroup::matvec_device(const double *d_w, int64_t ldw, int k, double *d_
     CHK(ensure_capacity(k, true));
     staged_k_ = dev_staged_k_ = 0; // the owners' staging buffers are overwritten with the caller's device weights
     all_complete_ = all_locals_ = false;
+    drop_mirrors();                // (no list outlives stage(); the buffers it would name may be reallocated below)
     P.bind_device();
     GHIP(hipEventRecord(ev_in_, P.stream_));
     // The primary keeps a copy as well (its parts read the caller's buffer itself): the partitioned upward pass leaves it with
@@ -680,9 +723,12 @@ int DeviceGroup::matvec_device(const double *d_w, int64_t ldw, int k, double *d_
         GHIP(hipStreamWaitEvent(p.t->stream_, ev_in_, 0));
         for (size_t h = 0; h < parts_.size(); ++h) // (parts sharing this device may still be reading the old copy)
             if (parts_[h].owner == g && static_cast<int>(h) != g) GHIP(hipStreamWaitEvent(p.t->stream_, parts_[h].ev_up, 0));
-        for (int j = 0; j < k; ++j)
-            GHIP(hipMemcpyPeerAsync(p.t->d_w_in_.p + static_cast<size_t>(j) * N, p.device, d_w + static_cast<size_t>(j) * ldw, parts_[0].device,
-                                    static_cast<size_t>(N) * sizeof(double), p.t->stream_));
+        for (int j = 0; j < k; ++j) {
+            const int crc = copy_between(p.t->d_w_in_.p + static_cast<size_t>(j) * N, p, d_w + static_cast<size_t>(j) * ldw, parts_[0],
+                                         static_cast<size_t>(N) * sizeof(double), p.t->stream_);
+            if (crc != BBFMM_OK) return part_fail(p, crc);
+            n_w_in_.fetch_add(1, std::memory_order_relaxed);
+        }
         GHIP(hipEventRecord(p.ev_w, p.t->stream_));
     }
     P.bind_device();
@@ -694,11 +740,8 @@ int DeviceGroup::matvec_device(const double *d_w, int64_t ldw, int k, double *d_
         const int prc = p.t->matvec_partition_finish_sorted(p.d_sum, p.d_seg, m_max, p.comm);
         if (prc != BBFMM_OK) return prc;
         double *dst = d_all_ + static_cast<size_t>(g) * k * m_max;
-        const size_t bytes = static_cast<size_t>(k) * m_max * sizeof(double);
-        if (p.device == parts_[0].device)
-            PHIP(hipMemcpyAsync(dst, p.d_seg, bytes, hipMemcpyDeviceToDevice, p.t->stream_));
-        else
-            PHIP(hipMemcpyPeerAsync(dst, parts_[0].device, p.d_seg, p.device, bytes, p.t->stream_));
+        const int crc = copy_between(dst, parts_[0], p.d_seg, p, static_cast<size_t>(k) * m_max * sizeof(double), p.t->stream_);
+        if (crc != BBFMM_OK) return crc;
         PHIP(hipEventRecord(p.ev_done, p.t->stream_));
         return BBFMM_OK;
     });
@@ -721,7 +764,10 @@ int DeviceGroup::complete_all(int k) {
     const int rc = for_parts([&](int g) -> int {
         Part &p = parts_[static_cast<size_t>(g)];
         const Part &o = parts_[static_cast<size_t>(p.owner)];
-        if (p.owner != g) PHIP(hipStreamWaitEvent(p.t->stream_, o.ev_w, 0));
+        if (p.owner != g) {
+            PHIP(hipStreamWaitEvent(p.t->stream_, o.ev_w, 0));
+            n_ev_w_waits_.fetch_add(1, std::memory_order_relaxed);
+        }
         const int prc = p.t->complete_upward_from(o.t->d_w_in_.p, k);
         if (prc != BBFMM_OK) return prc;
         PHIP(hipEventRecord(p.ev_up, p.t->stream_)); // (the part has read the staged copy)

@@ -21,7 +21,14 @@
 // multipoles from its device's copy of the staged weights and evaluates a contiguous share.  Row subsets (matvec_partial) are
 // dealt to the parts that own the rows.  What remains (few targets, other weights than set_weights') is served by part 0
 // alone after it has completed its multipoles.
+//
+// BBFMM_GROUP_OWN_COPIES=1 (read when the group is created; a checker): parts that share a physical device are treated as
+// sitting on different devices wherever the group decides whose copy of the weights a part reads and how data moves between
+// parts -- every part owns a copy, receives it as a mirror or by a peer copy, and exchanges slots and blocks by peer copies.
+// The control flow of a group over several devices then runs on one; every HIP call still names the physical device, so real
+// peer access, hipSetDevice between distinct devices and events across devices are NOT exercised by it.
 #pragma once
+#include <atomic>
 #include <memory>
 #include <string>
 #include <vector>
@@ -88,7 +95,20 @@ class DeviceGroup {
     // Before a call that part 0 serves alone.  same_weights: the call brings the weights of set_weights (or none).
     int prepare_primary(bool same_weights);
     // the primary has been given other weights / another product behind the group's back: nothing staged is valid any more
-    void primary_state_changed() { staged_k_ = dev_staged_k_ = 0; pending_k_ = 0; primary_complete_ = true; all_complete_ = all_locals_ = false; }
+    void primary_state_changed() {
+        staged_k_ = dev_staged_k_ = 0;
+        pending_k_ = 0;
+        primary_complete_ = true;
+        all_complete_ = all_locals_ = false;
+        drop_mirrors();
+    }
+    // bbfmm_debug_group_state: out[0] parts, [1] BBFMM_GROUP_OWN_COPIES on, [2] weight mirrors the primary holds now, then
+    // since creation [3] mirror pieces queued, [4] peer copies queued, [5] plain device copies between two parts queued,
+    // [6] waits for an owner's ev_w queued by the parts that read its copy, [7] columns of device-resident weights copied to
+    // the other owners (each also counted in [4] or [5]), [8] the runtime refused a peer copy within one device (the plain
+    // copy serves there); out[9 + g] the owner of part g.
+    static constexpr int kStateHeader = 9;
+    void debug_state(int64_t *out) const;
     bool weights_match_staged(const double *w, int64_t rows, int k, int64_t ldw) const;
     int last_path() const { return last_path_; } // 1: the last evaluate ran partitioned over the group, 0: on the primary
     void set_profiling(bool on);
@@ -99,8 +119,9 @@ class DeviceGroup {
     struct Part {
         FmmTree *t = nullptr;
         std::unique_ptr<FmmTree> own;
-        int device = 0;
-        int owner = 0;             // first part on the same device: holds the device's copy of the staged weights
+        int device = 0;            // physical: what every HIP call names
+        int ldev = 0;              // logical: what parts are compared by (= device; the part's index under BBFMM_GROUP_OWN_COPIES)
+        int owner = 0;             // first part on the same logical device: holds the device's copy of the staged weights
         hipStream_t comm = nullptr;
         hipEvent_t ev_w = nullptr;    // (owners) the staged weights have arrived
         hipEvent_t ev_up = nullptr;   // upward pass + near field queued: the part has read the staged weights
@@ -121,6 +142,11 @@ class DeviceGroup {
     template <class F> int finish_to_host(int k, F &&consume);
     template <class F> int for_parts(F &&fn);
     void free_buffers();
+    void drop_mirrors() { // the primary's list of weight mirrors belongs to one stage() (fmm_tree.hpp)
+        if (!parts_.empty() && parts_[0].t) parts_[0].t->mirrors_.clear();
+    }
+    // `bytes` from part `from` to part `to` on `st`: a device copy within one logical device, a peer copy between two
+    int copy_between(double *dst, const Part &to, const double *src, const Part &from, size_t bytes, hipStream_t st);
 
     std::vector<Part> parts_;
     std::vector<int64_t> bounds_;
@@ -152,7 +178,11 @@ class DeviceGroup {
     int subset_split(const int64_t *idx, int64_t n_idx, SubsetSplit **out);
     template <class F> int subset_product(SubsetSplit *sp, bool upward_pending, F &&consume);
     bool threads_ = true;
+    bool own_copies_ = false; // BBFMM_GROUP_OWN_COPIES
     int last_path_ = 0;
+    // debug_state (incremented where the calls are queued, by the parts' threads)
+    std::atomic<int64_t> n_peer_{0}, n_plain_{0}, n_ev_w_waits_{0}, n_w_in_{0};
+    std::atomic<bool> self_peer_refused_{false};
 };
 
 // Device list of a handle: "0,1,2,3", "all", or repeated ids for logical parts on one device ("0,0").  Empty / unset: none.

@@ -751,6 +751,7 @@ int FmmTree::stage_weights_to_device(const double *w, int64_t n, int k, int64_t 
     double *pin_in = h_pin_;
     double *dst = d_w_in_.p;
     std::atomic<int> err{0};
+    std::atomic<int64_t> mirrored{0};
     for (int j = 0; j < k; ++j) {
         const double *col = w + static_cast<size_t>(j) * ldw;
         const int64_t off = static_cast<int64_t>(j) * n;
@@ -765,10 +766,12 @@ int FmmTree::stage_weights_to_device(const double *w, int64_t n, int k, int64_t 
                 r = hipMemcpyAsync(mr.dst + off + b, pin_in + off + b, static_cast<size_t>(e - b) * sizeof(double), hipMemcpyHostToDevice,
                                    mr.stream);
                 if (r != hipSuccess) err.store(static_cast<int>(r));
+                mirrored.fetch_add(1, std::memory_order_relaxed);
             }
             if (!mirrors_.empty()) bind_device();
         });
     }
+    mirror_pieces_ += mirrored.load();
     if (err.load() != 0) return hip_fail(static_cast<hipError_t>(err.load()), "hipMemcpyAsync(weights)");
     return BBFMM_OK;
 }

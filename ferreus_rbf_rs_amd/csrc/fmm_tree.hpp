@@ -621,13 +621,16 @@ class FmmTree {
     size_t h_pin_n_ = 0;
     int ensure_pinned(size_t n);
     // A device group stages the caller's weights once (in the primary's pinned buffer) and sends every piece to the other
-    // devices of the group as well: (device, stream, destination of k x N doubles) per mirror.
+    // devices of the group as well: (device, stream, destination of k x N doubles) per mirror.  The list is the group's and
+    // lives for one DeviceGroup::stage() only: the destinations are the parts' d_w_in_, which the parts free and reallocate
+    // on their own, and a staging of the primary's alone (put_weights) must reach no other part.
     struct WeightMirror {
         int device;
         hipStream_t stream;
         double *dst;
     };
     std::vector<WeightMirror> mirrors_;
+    int64_t mirror_pieces_ = 0; // copies queued towards mirrors since creation (bbfmm_debug_group_state)
     int ensure_w_in(int k); // d_w_in_ holds k x N doubles
     // the whole upward pass from the weights staged in d_w_in_ (a device group's primary before a product the group does
     // not partition: arbitrary targets, target subsets, stored local expansions)

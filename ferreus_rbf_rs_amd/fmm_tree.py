@@ -792,6 +792,22 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_leaf_runs(self._h, c))
         return {"mask": c[0], "runs": c[1], "rest": c[2], "jobs": c[3]}
 
+    def debug_group_state(self) -> dict:
+        """What a device group holds and has queued (bbfmm_debug_group_state): parts, whether BBFMM_GROUP_OWN_COPIES was set when
+        the handle was created, the owner of every part's copy of the weights, the weight mirrors the primary holds now, and
+        counted since creation: mirror pieces, peer copies, plain device copies between parts, waits for another part's copy,
+        columns of device-resident weights copied to other parts; whether the runtime refused a peer copy within one device.
+        A plain handle reports one part and zeros."""
+        parts = self.device_count()
+        c = (ctypes.c_int64 * (9 + parts))()
+        self._raise(self._lib.bbfmm_debug_group_state(self._h, c, len(c)))
+        keys = ("parts", "own_copies", "live_mirrors", "mirror_pieces", "peer_copies", "plain_copies", "weight_waits", "weights_in",
+                "self_peer_refused")
+        st = {k: int(v) for k, v in zip(keys, c[:9])}
+        st["own_copies"], st["self_peer_refused"] = bool(st["own_copies"]), bool(st["self_peer_refused"])
+        st["owners"] = [int(v) for v in c[9:9 + parts]]
+        return st
+
     def debug_get_coefficients(self, which: str, k: int) -> np.ndarray:
         s = self.stats()
         n = s.n_nodes

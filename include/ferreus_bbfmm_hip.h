@@ -783,6 +783,15 @@ int bbfmm_debug_m2l_s2_last_ksplit(const bbfmm_handle *h, int32_t *ksplit); /* d
 /* The leaf passes over runs of leaves (BBFMM_LEAF_PASSES): counts[0] the handle's mask, counts[1] the runs of the resident
  * target set's job list, counts[2] its jobs outside every run, counts[3] all its jobs (0 runs: one leaf per wave). */
 int bbfmm_debug_leaf_runs(const bbfmm_handle *h, int32_t *counts); /* debug only */
+/* What a device group holds and has queued, for the tests that run its several-device paths on one device
+ * (BBFMM_GROUP_OWN_COPIES=1 when the handle is created: every part keeps its own copy of the weights and data moves between
+ * parts as between devices).  out (capacity cap >= 9 + parts): out[0] parts, out[1] the switch, out[2] the weight mirrors
+ * the primary holds now (0 outside a staging), then counted since creation where the calls are queued: out[3] pieces of
+ * staged weights sent to mirrors, out[4] peer copies, out[5] plain device copies between two parts, out[6] waits of a part
+ * for the arrival of another part's copy of the weights, out[7] columns of device-resident weights copied to other parts
+ * (each one also in out[4] or out[5]), out[8] 1 when the runtime refused a peer copy within one device and the plain copy
+ * serves instead; out[9 + g] the part whose copy of the weights part g reads.  A plain handle: one part, zeros. */
+int bbfmm_debug_group_state(const bbfmm_handle *h, int64_t *out, int64_t cap); /* debug only */
 
 /* The Morton primitives of csrc/morton.hpp as the host tree build uses them (morton.rs:58-263; the
  * reference's byte lookup tables, morton_constants.rs:77-346, are replaced by bit arithmetic): checked

@@ -48,6 +48,27 @@ print("OK")
     assert out.returncode == 0 and b"OK" in out.stdout, out.stderr.decode()[-2000:]
 
 
+def test_the_group_state_hook_is_declared_exported_and_bound():
+    from test_abi_symbols import declared_functions
+    name = "bbfmm_debug_group_state"
+    assert name in declared_functions() and name in L.SIGNATURES and hasattr(ctypes.CDLL(L.LIB_PATH), name)
+    assert L.SIGNATURES[name] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64])
+
+
+def test_a_host_only_handle_reports_one_part_that_owns_itself_whatever_the_switch_says(monkeypatch):
+    """BBFMM_GROUP_OWN_COPIES is read where a device group is created; a host-only handle has none."""
+    monkeypatch.setenv("BBFMM_GROUP_OWN_COPIES", "1")
+    t = F.FmmTree(_pts(), 4, F.KernelParams(F.FmmKernelType.LinearRbf), True, True, host_only=True)
+    assert t.debug_group_state() == {"parts": 1, "own_copies": False, "live_mirrors": 0, "mirror_pieces": 0, "peer_copies": 0,
+                                     "plain_copies": 0, "weight_waits": 0, "weights_in": 0, "self_peer_refused": False, "owners": [0]}
+    lib = L.load()
+    out = np.full(12, -1, dtype=np.int64)
+    assert lib.bbfmm_debug_group_state(t._h, out.ctypes.data, 9) == L.BAD_ARGUMENT       # no room for the one owner
+    assert lib.bbfmm_debug_group_state(None, out.ctypes.data, 12) == L.BAD_ARGUMENT and np.all(out == -1)
+    assert lib.bbfmm_debug_group_state(t._h, out.ctypes.data, 12) == 0
+    assert list(out) == [1] + [0] * 9 + [-1, -1]                                          # ten values written, no more
+
+
 @pytest.mark.parametrize("text,needle", [("0,,1", "malformed"), ("zero", "malformed"), ("0,-1", "malformed"), ("0;1", "malformed")])
 def test_a_malformed_environment_list_fails_loudly(text, needle):
     """bbfmm_create reads FERREUS_BBFMM_DEVICES itself (the reference's constructor has no argument for it): a list it cannot
