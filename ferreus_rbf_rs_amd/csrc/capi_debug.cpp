@@ -234,6 +234,13 @@ int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64
     return BBFMM_OK;
 }
 
+// The stage-2 kernel instance of the parity basis: ga, gb, ce, co, ya, yb (FmmTree::debug_m2l_s2_plan).
+int bbfmm_debug_m2l_s2_plan(const bbfmm_handle *h, int32_t *out) {
+    if (!h || !out) return BBFMM_BAD_ARGUMENT;
+    h->tree.debug_m2l_s2_plan(out);
+    return BBFMM_OK;
+}
+
 // Digests of the integer M2L tables, one per family, and the per-level flop counts (FmmTree::debug_m2l_table_digests).
 int bbfmm_debug_m2l_table_digests(const bbfmm_handle *h, uint64_t *digests, int32_t cap, int32_t *n_out, double *flops_level,
                                   int32_t flops_cap, int32_t *n_levels_out) {

@@ -353,4 +353,10 @@ void FmmTree::debug_m2l_pairs_axes_stage2(std::vector<int32_t> *out) const {
     }
 }
 
+void FmmTree::debug_m2l_s2_plan(int32_t out[6]) const {
+    const M2lS2PairsPlan &pl = m2l_s2_plan_;
+    const int32_t v[6] = {pl.ga, pl.gb, pl.ce, pl.co, pl.ya, pl.yb}; // (the one-axis plan leaves ya = yb = 0)
+    for (int i = 0; i < 6; ++i) out[i] = m2l_pairs2_ ? v[i] : 0;
+}
+
 } // namespace bbfmm

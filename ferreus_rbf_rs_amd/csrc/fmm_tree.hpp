@@ -304,6 +304,9 @@ class FmmTree {
     // pair, listed by its leader) or 2 (y pair), its slot offset, its partner's slot offset (-1: a single), its rank, then
     // the d components of t.
     void debug_m2l_pairs_axes_stage2(std::vector<int32_t> *out) const;
+    // Test hook: the kernel instance of stage 2 in the parity basis, out = {ga, gb, ce, co, ya, yb} of m2l_s2_plan_ (ya = yb =
+    // 0 with one axis); all zeros when the handle has no stage-2 pairs.  Made on the host: host-only handles answer too.
+    void debug_m2l_s2_plan(int32_t out[6]) const;
     // Test hook: one 64-bit FNV-1a digest per family of the integer tables build_m2l_tables() produces, for host-only handles
     // (upload() releases cslot and the zero lists of the others).  Every vector is hashed as its length, then its elements;
     // no floating-point value is hashed.  The families, in the order of *out:

@@ -779,6 +779,14 @@ class FmmTree:
                                                             nl.value, ctypes.byref(nl)))
         return {k: f"{int(v):016x}" for k, v in zip(self.M2L_DIGEST_FAMILIES, dig)}, [float(v) for v in fl[:nl.value]]
 
+    def debug_m2l_s2_plan(self) -> tuple:
+        """(ga, gb, ce, co, ya, yb): the kernel instance stage 2 runs in the parity basis -- column groups per chunk of the
+        x-even and x-odd half, chunks per half, and with two axes the y-even groups of a chunk (0, 0 with one axis).  All
+        zeros without stage-2 pairs.  The plan is made on the host: host_only handles answer too."""
+        out = (ctypes.c_int32 * 6)()
+        self._raise(self._lib.bbfmm_debug_m2l_s2_plan(self._h, out))
+        return tuple(int(v) for v in out)
+
     def debug_m2l_s2_last_ksplit(self) -> int:
         """Parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet)."""
         ks = ctypes.c_int32()

@@ -773,6 +773,10 @@ int bbfmm_debug_m2l_pairs(const bbfmm_handle *h, int32_t *out, int64_t cap, int6
 int bbfmm_debug_m2l_pairs_axes(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
 int bbfmm_debug_m2l_pairs_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out, int32_t *pairs_on);
 int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64_t cap, int64_t *n_out);
+/* The kernel instance stage 2 runs in the parity basis: out[6] = column groups per chunk of the x-even and of the x-odd half
+ * (ga, gb), chunks per half (ce, co), and with two axes the groups of a chunk that belong to its y-even part (ya, yb; 0, 0
+ * with one axis).  All zeros when the handle has no stage-2 pairs.  Made on the host: BBFMM_FLAG_HOST_ONLY handles answer. */
+int bbfmm_debug_m2l_s2_plan(const bbfmm_handle *h, int32_t *out);
 /* One 64-bit FNV-1a digest per family of the integer M2L tables (FmmTree::debug_m2l_table_digests lists the families and
  * their order), for BBFMM_FLAG_HOST_ONLY handles: *n_out = number of families, digests (capacity cap, may be NULL)
  * receives the first min(cap, *n_out).  flops_level (capacity flops_cap, may be NULL) receives the M2L flop count of

@@ -1,5 +1,6 @@
 """The clouds, weights and handles of the far-field tests: the smallest at which each pass can go wrong.  A plain helper
-module (no tests); tests/test_far_field_reference_host.py and tests/test_gpu_far_field_passes.py share it."""
+module (no tests); tests/test_far_field_reference_host.py, tests/test_gpu_far_field_passes.py and
+tests/test_gpu_far_field_orders.py share it."""
 import contextlib
 import os
 
@@ -47,10 +48,15 @@ def environment(env):
                 os.environ[k] = v
 
 
-def make_tree(pts, order, leaf_limit, env=None, kernel=(0, 1.0, 1.0), host_only=False, sparse=True, epsilon=1e-7):
+NO_COMPRESSION = 0
+
+
+def make_tree(pts, order, leaf_limit, env=None, kernel=(0, 1.0, 1.0), host_only=False, sparse=True, epsilon=1e-7,
+              compression=ACA):
     with environment(env or {}):
         return F.FmmTree(pts, order, F.KernelParams(F.KernelType(kernel[0]), base_range=kernel[1], total_sill=kernel[2]), True,
-                         sparse, params=F.FmmParams(leaf_limit, F.M2LCompressionType(ACA), epsilon, 1024), host_only=host_only)
+                         sparse, params=F.FmmParams(leaf_limit, F.M2LCompressionType(compression), epsilon, 1024),
+                         host_only=host_only)
 
 
 def on_grid(x):
@@ -152,6 +158,138 @@ def clustered_cloud():
 
 
 CLUSTERED_LIMIT = 30
+
+
+# ---- the stage-2 kernel instance of every order: debug_m2l_s2_plan() = (ga, gb, ce, co, ya, yb) under BBFMM_M2L_S2_AXES = 1
+# and = 2 (tests/test_far_field_reference_host.py enumerates host-only handles against this table and explains it)
+_S2_PLANS = {
+    3: {2: ((1, 1, 1, 1, 0, 0), (2, 2, 1, 1, 1, 1)), 3: ((2, 2, 1, 1, 0, 0), (2, 2, 1, 1, 1, 1)),
+        4: ((2, 2, 1, 1, 0, 0), (2, 2, 1, 1, 1, 1)), 5: ((5, 4, 1, 1, 0, 0), (5, 4, 1, 1, 3, 2)),
+        6: ((7, 7, 1, 1, 0, 0), (8, 8, 1, 1, 4, 4)), 7: ((13, 10, 1, 1, 0, 0), (13, 10, 1, 1, 7, 6)),
+        8: ((8, 8, 2, 2, 0, 0), (8, 8, 2, 2, 4, 4)), 9: ((13, 11, 2, 2, 0, 0), (14, 11, 2, 2, 8, 6)),
+        10: ((8, 8, 4, 4, 0, 0), (8, 8, 4, 4, 4, 4))},
+    2: {**{p: ((1, 1, 1, 1, 0, 0), (2, 2, 1, 1, 1, 1)) for p in (2, 3, 4, 5)},
+        **{p: ((2, 2, 1, 1, 0, 0), (2, 2, 1, 1, 1, 1)) for p in (6, 7, 8)},
+        **{p: ((4, 4, 1, 1, 0, 0), (4, 4, 1, 1, 2, 2)) for p in (9, 10)}, 11: ((5, 4, 1, 1, 0, 0), (5, 4, 1, 1, 3, 2)),
+        **{p: ((7, 7, 1, 1, 0, 0), (8, 8, 1, 1, 4, 4)) for p in (12, 13, 14)},
+        **{p: ((8, 8, 1, 1, 0, 0), (8, 8, 1, 1, 4, 4)) for p in (15, 16)}}}
+S2_PLANS = {(d, p, axes): plans[axes - 1] for d, rows in _S2_PLANS.items() for p, plans in rows.items() for axes in (1, 2)}
+# the instances (ga, gb, ya, yb) of 3-D orders 6, 8, 9 and 10, which orders 3, 4, 5 and 7 never select: what the GPU cases of
+# tests/test_gpu_far_field_orders.py cover between them
+GPU_INSTANCES = {(7, 7, 0, 0), (8, 8, 0, 0), (13, 11, 0, 0), (8, 8, 4, 4), (14, 11, 8, 6)}
+
+
+def assert_s2_plan(t, d, order, env=None):
+    """The handle runs the instance the table names for its axes (all zeros without stage-2 pairs); returns the instance."""
+    plan = t.debug_m2l_s2_plan()
+    if (env or {}).get("BBFMM_M2L_S2_PAIRS") == "0" or d < 2:
+        assert plan == (0,) * 6 and not t.debug_m2l_pairs(stage=2)[0]
+        return None
+    axes = t.debug_m2l_pairs_axes(stage=2)[0]["axes"]
+    if "BBFMM_M2L_S2_AXES" in (env or {}):
+        assert axes == int(env["BBFMM_M2L_S2_AXES"])
+    assert axes in (1, 2) and plan == S2_PLANS[d, order, axes], (plan, d, order, axes)
+    return plan[0], plan[1], plan[4], plan[5]
+
+
+# the columns of lattice_sources that on lattice8 reach every one of the 316 transfer vectors at level 3 between them:
+# FEW_COLUMNS (below) misses (-1, -3, 3) and (-1, 3, -3), which the interior cells (2, 3, 2) and (2, 2, 3) supply
+EVERY_VECTOR_COLUMNS = [0, 5, 10, 13, 14, 16, 18]
+
+
+# ---- two dimensions and one
+def lattice2d_cloud():
+    """16 x 16 cells of three points: depth 4, 256 leaves, the four classes with interior, edge and corner cells."""
+    return lattice(np.random.default_rng(60), 16, 2, 3)
+
+
+def assert_lattice2d(t, geo):
+    at4 = geo.level == 4
+    assert t.stats().depth == 4 and at4.sum() == 256 and geo.is_leaf[at4].all()
+    assert set(geo.octant[at4].tolist()) == set(range(4))
+    assert (np.diff(geo.lists["V"][0])[at4] == 27).any()               # the full V list of two dimensions
+
+
+def clustered2d_cloud():
+    return np.unique(clustered_points(np.random.default_rng(78), 3000, 2), axis=0)
+
+
+LINE_LIMIT = 5                                                         # a level-3 cell holds six points and splits
+LINE_CLUSTER = 5                                                       # the level-4 cell that holds the cluster
+
+
+def line_cloud():
+    """One dimension: 16 cells of three points and three more in one of them, which therefore splits once more: 51 points,
+    the least for a uniform level 4 (three points per cell as on the lattices) beside one deeper cell."""
+    pts = lattice(np.random.default_rng(61), 16, 1, 3)
+    extra = (LINE_CLUSTER + 0.15 + 0.7 * np.random.default_rng(62).random((3, 1))) / 16
+    return np.concatenate([pts, extra])
+
+
+def assert_line(t, geo):
+    """Depth at least 4; a cell of either parity with the full V list of one dimension (three cells: the offsets -2, 2, 3
+    from an even cell and -3, -2, 2 from an odd one, so no single cell sees all four vectors, the two together do); mixed
+    levels next to the cluster."""
+    at4 = geo.level == 4
+    assert t.stats().depth >= 4 and at4.sum() == 16 and t.stats().n_w > 0
+    full = at4 & (np.diff(geo.lists["V"][0]) == 3)
+    assert set(geo.octant[full].tolist()) == {0, 1}
+    tgt_full = full[geo.v_tgt]
+    assert set(geo.v_tidx[tgt_full].tolist()) == set(geo.v_tidx.tolist()) and len(set(geo.v_tidx.tolist())) == 4
+
+
+def leaf_at(geo, level, anchor):
+    c = np.nonzero((geo.level == level) & (geo.anchor == np.array(anchor)).all(axis=1))[0]
+    assert len(c) == 1 and geo.is_leaf[c[0]]
+    return int(c[0])
+
+
+def lattice2d_leaves(geo):
+    """A corner, an edge and an interior leaf (all 27 vectors) of each of the four classes: twelve leaves."""
+    ends = (0, 15)
+    at = [kind(b0, b1) for kind in (lambda b0, b1: (ends[b0], ends[b1]), lambda b0, b1: (ends[b0], 6 + b1),
+                                    lambda b0, b1: (6 + b0, 8 + b1)) for b1 in (0, 1) for b0 in (0, 1)]
+    leaves = [leaf_at(geo, 4, a) for a in at]
+    assert all(sorted(geo.octant[leaves[4 * k:4 * k + 4]].tolist()) == [0, 1, 2, 3] for k in range(3))
+    n_v = np.diff(geo.lists["V"][0])[leaves]
+    assert (n_v[8:] == 27).all() and (n_v[:8] < 27).all()
+    return leaves
+
+
+def line_leaves(geo):
+    """Both ends and an interior leaf of the uniform level."""
+    return [leaf_at(geo, 4, (0,)), leaf_at(geo, 4, (15,)), leaf_at(geo, 4, (10,))]
+
+
+def one_leaf_weights(geo, n, leaves, seed):
+    """One right-hand side per leaf, nonzero on that leaf's points alone."""
+    return np.concatenate([leaf_weights(geo, n, leaf, 1, seed + k) for k, leaf in enumerate(leaves)], axis=1)
+
+
+def live_cells(geo, w):
+    """Cells with a nonzero weight below them, from the geometry alone."""
+    live = np.zeros(geo.C, dtype=bool)
+    for c in np.nonzero(np.diff(geo.src_ptr) > 0)[0]:
+        live[c] = np.any(w[geo.src_idx[geo.src_ptr[c]:geo.src_ptr[c + 1]]] != 0)
+    for c in np.argsort(-geo.level, kind="stable"):
+        if live[c] and geo.parent[c] >= 0:
+            live[geo.parent[c]] = True
+    return live
+
+
+def assert_every_vector_is_live(geo, w):
+    """The condition on every M2L case: at the deepest level where all classes are present and whose V lists between them
+    take every transfer vector of the tree (the uniform level of the lattices and of the line: the few cells below it
+    see a handful of vectors whatever the weights), the pairs with a live source hit every one of those vectors."""
+    every = set(geo.v_tidx.tolist())
+    at = geo.level[geo.v_tgt]
+    levels = [lv for lv in range(2, geo.depth + 1) if len(set(geo.octant[geo.level == lv].tolist())) == 1 << geo.d
+              and set(geo.v_tidx[at == lv].tolist()) == every]
+    assert levels, "no level takes every transfer vector"
+    live = live_cells(geo, w)
+    hit = set(geo.v_tidx[(at == levels[-1]) & live[geo.v_src]].tolist())
+    assert hit == every, (levels[-1], len(hit), len(every))
+    return levels[-1]
 
 
 def dense_weights(n, K, seed):

@@ -49,6 +49,15 @@ def test_schwarz_trace_hook_is_declared_and_bound():
         assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n
 
 
+def test_m2l_debug_hooks_are_declared_and_bound():
+    names = ["bbfmm_debug_m2l_variants", "bbfmm_debug_m2l_pairs", "bbfmm_debug_m2l_pairs_axes", "bbfmm_debug_m2l_pairs_stage2",
+             "bbfmm_debug_m2l_pairs_axes_stage2", "bbfmm_debug_m2l_table_digests", "bbfmm_debug_m2l_s2_plan",
+             "bbfmm_debug_m2l_s2_last_ksplit", "bbfmm_debug_m2l_parity_len", "bbfmm_debug_apply_m2l_tables_host"]
+    lib = ctypes.CDLL(L.LIB_PATH)
+    for n in names:
+        assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n
+
+
 def test_params_defaults_match_reference():
     # FmmParams::new_defaults, ferreus_bbfmm/src/bbfmm.rs:96-103
     lib = L.load()

@@ -1,17 +1,49 @@
 """The long-double restatement of the far-field passes (tests/far_field_reference.py) proven without a GPU: against the
 oracle's double passes cell by cell, against the host walk of the product's own M2L tables under every switch setting,
 its 1-D transfers against the product's dense M2M matrices, and the per-cell checker against altered data that the global
-norm lets through."""
+norm lets through.  In three, two and one dimension, and with uncompressed operators.
+
+THE STAGE-2 KERNEL INSTANCE OF EVERY ORDER (debug_m2l_s2_plan() of host-only handles; far_field_cases.S2_PLANS is this
+table as data and test_stage2_plan_of_every_order_is_the_table_of_the_docstring holds the two to the handles).  One axis:
+(GA, GB) of m2l_s2_pairs_kernel x (chunks of the x-even half, of the x-odd half); two axes: (GA, YA, GB, YB) of
+m2l_s2_pairs2_kernel x the same.  The plan depends on the dimension, the order and the axes alone; unset, BBFMM_M2L_S2_AXES
+is picked per tree by executed work.  With BBFMM_M2L_S2_PAIRS=0, without compression and in one dimension there is no
+plan (all zeros: stage 2 runs in the node basis).
+
+   d  order   one axis             two axes
+   3    2     (1, 1)   x (1, 1)    (2, 1, 2, 1)   x (1, 1)
+   3   3, 4   (2, 2)   x (1, 1)    (2, 1, 2, 1)   x (1, 1)
+   3    5     (5, 4)   x (1, 1)    (5, 3, 4, 2)   x (1, 1)
+   3    6     (7, 7)   x (1, 1)    (8, 4, 8, 4)   x (1, 1)
+   3    7     (13, 10) x (1, 1)    (13, 7, 10, 6) x (1, 1)
+   3    8     (8, 8)   x (2, 2)    (8, 4, 8, 4)   x (2, 2)
+   3    9     (13, 11) x (2, 2)    (14, 8, 11, 6) x (2, 2)
+   3   10     (8, 8)   x (4, 4)    (8, 4, 8, 4)   x (4, 4)
+   2   2 - 5  (1, 1)   x (1, 1)    (2, 1, 2, 1)   x (1, 1)
+   2   6 - 8  (2, 2)   x (1, 1)    (2, 1, 2, 1)   x (1, 1)
+   2   9, 10  (4, 4)   x (1, 1)    (4, 2, 4, 2)   x (1, 1)
+   2   11     (5, 4)   x (1, 1)    (5, 3, 4, 2)   x (1, 1)
+   2  12 - 14 (7, 7)   x (1, 1)    (8, 4, 8, 4)   x (1, 1)
+   2  15, 16  (8, 8)   x (1, 1)    (8, 4, 8, 4)   x (1, 1)
+
+Every entry of M2L_S2_PAIR_WIDTHS and of M2L_S2_PAIR2_WIDTHS (device_m2l.hip) is selected by some order of this range:
+none is unreachable here.  3-D orders 6, 8, 9 and 10 select (7, 7), (8, 8), (13, 11), (8, 4, 8, 4) and (14, 8, 11, 6), which
+orders 3, 4, 5 and 7 never reach, and the only plans with more than one chunk per half: far_field_cases.GPU_INSTANCES, what
+tests/test_gpu_far_field_orders.py covers on the device."""
+import os
+import re
+
 import numpy as np
 import pytest
 
 import far_field_cases as C
 import far_field_reference as R
-from conftest import inject_product_operators, relerr
+from conftest import ROOT, inject_product_operators, relerr
 from far_field_reference import LD, U
 from oracle import bbfmm_oracle as O
 
-CLOUDS = {"lattice8": (C.lattice8_cloud, C.LATTICE_LIMIT), "clustered": (C.clustered_cloud, C.CLUSTERED_LIMIT)}
+CLOUDS = {"lattice8": (C.lattice8_cloud, C.LATTICE_LIMIT), "clustered": (C.clustered_cloud, C.CLUSTERED_LIMIT),
+          "lattice2d": (C.lattice2d_cloud, C.LATTICE_LIMIT), "line": (C.line_cloud, C.LINE_LIMIT)}
 cached = C.cached
 
 
@@ -49,17 +81,17 @@ def upward_reference(geo, pts, w, M, terms):
 
 
 # ------------------------------------------------------------------ against the oracle
-@pytest.mark.parametrize("order", [4, 5])
-@pytest.mark.parametrize("cloud", ["lattice8", "clustered"])
+@pytest.mark.parametrize("cloud,order", [("lattice8", 4), ("clustered", 4), ("lattice8", 5), ("clustered", 5), ("lattice2d", 4),
+                                         ("lattice2d", 7), ("line", 4), ("line", 16)])
 def test_restatement_against_the_oracle_cell_by_cell(cloud, order):
     """The oracle multiplies by the dense n x n transfer matrices: n + 3 terms where the device has 3p + 3; its M2L
     (n terms, then the rank columns, pair after pair) and its P2L (the host's kernel functions) are inside the bounds of
     the module docstring as they stand."""
     pts, t, geo, r = setup(cloud, order)
-    if cloud == "lattice8":
-        C.assert_lattice8(t, geo)
-    else:
+    if cloud == "clustered":
         assert t.stats().n_w > 0
+    else:
+        {"lattice8": C.assert_lattice8, "lattice2d": C.assert_lattice2d, "line": C.assert_line}[cloud](t, geo)
     w = C.dense_weights(len(pts), 1, 5)
     M, L = oracle_passes(cloud, order, w)
     ref, bound = upward_reference(geo, pts, w, M, geo.n + 3)
@@ -74,15 +106,27 @@ CONFIGS = [{}] + [dict(s1, BBFMM_M2L_S2_PAIRS=s2) for s1 in ({"BBFMM_M2L_S1_PAIR
                                                               {"BBFMM_M2L_S1_AXES": "2"}) for s2 in ("0", "1")]
 
 
-def lattice8_weights(kind):
-    pts = cached(("pts", "lattice8"), C.lattice8_cloud)
-    return C.dense_weights(len(pts), 1, 7) if kind == "dense" else C.sparse_lattice_weights(pts, 8, 9, C.FEW_COLUMNS)
+WALK_CLOUD = {"dense": "lattice8", "sparse": "lattice8", "every-vector": "lattice8", "two-cells": "lattice8",
+              "dense-2d": "lattice2d"}
+
+
+def walk_weights(kind):
+    """dense, sparse: lattice8 as before; every-vector: lattice8 with the columns that between them reach all 316 vectors;
+    dense-2d: lattice2d."""
+    pts = cached(("pts", WALK_CLOUD[kind]), CLOUDS[WALK_CLOUD[kind]][0])
+    if kind in ("dense", "dense-2d"):
+        return C.dense_weights(len(pts), 1, 7)
+    return C.sparse_lattice_weights(pts, 8, 9, {"sparse": C.FEW_COLUMNS, "every-vector": C.EVERY_VECTOR_COLUMNS,
+                                                "two-cells": [13, 18]}[kind])
 
 
 def m2l_reference(order, kind):
     def make():
-        pts, t, geo, r = setup("lattice8", order)
-        M, _ = oracle_passes("lattice8", order, lattice8_weights(kind))
+        pts, t, geo, r = setup(WALK_CLOUD[kind], order)
+        w = walk_weights(kind)
+        if kind in ("every-vector", "dense-2d"):
+            C.assert_every_vector_is_live(geo, w)
+        M, _ = oracle_passes(WALK_CLOUD[kind], order, w)
         m2l = R.M2L(geo, t)
         Lr, S, Rc = m2l.apply(M)
         return M, Lr, m2l.bound(S, Rc), t.m2l_factors(3, 0)
@@ -91,10 +135,17 @@ def m2l_reference(order, kind):
 
 @pytest.mark.parametrize("env", CONFIGS, ids=lambda e: ",".join(f"{k[10:]}={v}" for k, v in e.items()) or "default")
 @pytest.mark.parametrize("order,kind", [(3, "dense"), (3, "sparse"), (4, "dense"), (4, "sparse"), (5, "dense"), (5, "sparse"),
-                                        (7, "sparse")])
+                                        (7, "sparse"), (6, "every-vector"), (8, "every-vector"), (9, "every-vector")] +
+                         [(p, "dense-2d") for p in (3, 6, 7, 10, 16)])
 def test_host_walk_of_the_m2l_tables_stays_inside_the_m2l_bound(order, kind, env):
-    pts, _, geo, _ = setup("lattice8", order)
-    M, Lr, bound, f0 = m2l_reference(order, kind)
+    """every-vector (orders 6, 8, 9, where a walk takes up to ten seconds per right-hand side): all seven columns under the
+    default configuration, the two interior cells of classes 1 and 6 under the six others.  Measured on eight cores with
+    other work beside it, the seven cases of an order together: order 6 about 45 s (default 22 s), order 8 141 s (default
+    38 s, the others 12 s with stage-2 pairs and 20 to 24 s without), order 9 249 s (default 79 s, the others 15 to 23 s and
+    34 to 43 s) -- the walk, not the restatement, is the cost: it visits every stacked table of every cell whatever the
+    weights.  With all of FEW_COLUMNS under every configuration orders 8 and 9 would take about 2.5 times as long."""
+    pts, _, geo, _ = setup(WALK_CLOUD[kind], order)
+    M, Lr, bound, f0 = m2l_reference(order, "two-cells" if kind == "every-vector" and env else kind)
     t = C.make_tree(pts, order, C.LATTICE_LIMIT, env=env, host_only=True)
     if "BBFMM_M2L_S1_PAIRS" in env:
         assert not t.debug_m2l_pairs()[0]
@@ -105,10 +156,79 @@ def test_host_walk_of_the_m2l_tables_stays_inside_the_m2l_bound(order, kind, env
     for a, b in zip(f0, t.m2l_factors(3, 0)):                       # the switches change the tables, not the operators
         assert np.array_equal(a, b)
     Lh = np.stack([t.debug_apply_m2l_tables_host(M[k]) for k in range(M.shape[0])])
-    if kind == "sparse":                                            # cells no source reaches hold exact zeros
+    if kind in ("sparse", "every-vector"):                          # cells no source reaches hold exact zeros
         untouched = bound == 0
         assert untouched.any() and (Lh[untouched] == 0).all()
     R.check_cells("M2L tables", Lh, Lr.transpose(1, 0, 2), bound.T, range(geo.C), f"order {order} {kind} {env}")
+
+
+def test_host_walk_of_the_uncompressed_m2l_tables_stays_inside_the_m2l_bound():
+    """M2LCompressionType none: no Vt, the rank is n, nothing pairs (the multipoles do not depend on the compression: they
+    are those of the compressed setup)."""
+    pts, _, geo, _ = setup("lattice8", 4)
+    w = walk_weights("every-vector")
+    C.assert_every_vector_is_live(geo, w)
+    M, _ = oracle_passes("lattice8", 4, w)
+    t = C.make_tree(pts, 4, C.LATTICE_LIMIT, host_only=True, compression=C.NO_COMPRESSION)
+    assert not t.debug_m2l_pairs()[0] and not t.debug_m2l_pairs(stage=2)[0] and t.debug_m2l_s2_plan() == (0,) * 6
+    u, vt = t.m2l_factors(3, 0)
+    assert vt is None and u.shape == (geo.n, geo.n) and (t.m2l_ranks()[2:] == geo.n).all()
+    m2l = R.M2L(geo, t)
+    Lr, S, Rc = m2l.apply(M)
+    bound = m2l.bound(S, Rc)
+    Lh = np.stack([t.debug_apply_m2l_tables_host(M[k]) for k in range(M.shape[0])])
+    untouched = bound == 0
+    assert untouched.any() and (Lh[untouched] == 0).all()
+    R.check_cells("M2L tables", Lh, Lr.transpose(1, 0, 2), bound.T, range(geo.C), "order 4 uncompressed")
+
+
+# ------------------------------------------------------------------ the stage-2 kernel instance of every order
+def s2_plan_table():
+    """{(d, order, axes): (ga, gb, ce, co, ya, yb)} from host-only handles; the plan depends on d, the order and the axes."""
+    def make():
+        table = {}
+        for d, orders in ((2, range(2, 17)), (3, range(2, 11))):
+            pts = C.random_cloud(d, 400, 27)
+            for order in orders:
+                for axes in (1, 2):
+                    t = C.make_tree(pts, order, 30, env={"BBFMM_M2L_S2_AXES": str(axes)}, host_only=True)
+                    assert t.debug_m2l_pairs_axes(stage=2)[0]["axes"] == axes
+                    table[d, order, axes] = t.debug_m2l_s2_plan()
+        return table
+    return cached(("s2 plans",), make)
+
+
+def kernel_widths(macro):
+    """The entries X(...) of a width list of csrc/device_m2l.hip, from which the planner's table and the launcher's dispatch
+    are generated: a set of tuples."""
+    path = os.path.join(ROOT, "ferreus_rbf_rs_amd", "csrc", "device_m2l.hip")
+    line = re.search(r"^#define %s\(X\)(.*)$" % macro, open(path).read(), re.M).group(1)
+    assert "\\" not in line                                         # the list is one line
+    return {tuple(int(v) for v in e.split(",")) for e in re.findall(r"X\(([\d, ]+)\)", line)}
+
+
+def test_stage2_plan_of_every_order_is_the_table_of_the_docstring():
+    table = s2_plan_table()
+    assert table == C.S2_PLANS
+    for (d, order, axes), (ga, gb, ce, co, ya, yb) in table.items():
+        n_e, n_o = (order + 1) // 2 * order ** (d - 1), order // 2 * order ** (d - 1)
+        assert (ya > 0 and yb > 0) == (axes == 2)
+        if axes == 1:                                               # each half fits its chunks
+            assert n_e <= 16 * ga * ce and n_o <= 16 * gb * co
+    # every instance the kernels are built for is selected somewhere in the range: none is unreachable
+    one, two = kernel_widths("M2L_S2_PAIR_WIDTHS"), kernel_widths("M2L_S2_PAIR2_WIDTHS")
+    assert len(one) == 8 and len(two) == 6 and (13, 11) in one and (14, 8, 11, 6) in two
+    assert {(p[0], p[1]) for k, p in table.items() if k[2] == 1} == one
+    assert {(p[0], p[4], p[1], p[5]) for k, p in table.items() if k[2] == 2} == two
+    # the switches that turn stage 2's pairs off, and a tree without pairs at all
+    pts = C.random_cloud(3, 400, 27)
+    assert C.make_tree(pts, 6, 30, env={"BBFMM_M2L_S2_PAIRS": "0"}, host_only=True).debug_m2l_s2_plan() == (0,) * 6
+    assert C.make_tree(C.random_cloud(1, 64, 22), 6, 9, host_only=True).debug_m2l_s2_plan() == (0,) * 6
+    # unset, the axes are picked by executed work, and the plan is that of the picked axes
+    for d, order in ((2, 4), (2, 10), (3, 5), (3, 9)):
+        t = C.make_tree(C.random_cloud(d, 400, 27), order, 30, host_only=True)
+        assert t.debug_m2l_s2_plan() == table[d, order, t.debug_m2l_pairs_axes(stage=2)[0]["axes"]]
+    assert C.GPU_INSTANCES == {(p[0], p[1], p[4], p[5]) for k, p in table.items() if k[0] == 3 and k[1] in (6, 8, 9, 10)}
 
 
 # ------------------------------------------------------------------ the 1-D transfers, multiplied out

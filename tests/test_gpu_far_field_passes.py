@@ -37,24 +37,31 @@ def _release_everything_at_the_end():
 def cloud(name):
     return cached(("cloud", name), {"populations": lambda: C.populations_cloud()[0], "lattice8": C.lattice8_cloud,
                                     "lattice16": C.lattice16_cloud, "clustered": C.clustered_cloud,
-                                    "2d": lambda: C.random_cloud(2, 16 ** 3, 21), "1d": lambda: C.random_cloud(1, 64, 22)}[name])
+                                    "2d": lambda: C.random_cloud(2, 16 ** 3, 21), "1d": lambda: C.random_cloud(1, 64, 22),
+                                    "lattice2d": C.lattice2d_cloud, "clustered2d": C.clustered2d_cloud, "line": C.line_cloud}[name])
 
 
 LIMITS = {"populations": C.POPULATIONS_LIMIT, "lattice8": C.LATTICE_LIMIT, "lattice16": C.LATTICE_LIMIT,
-          "clustered": C.CLUSTERED_LIMIT, "2d": 70, "1d": 9}
+          "clustered": C.CLUSTERED_LIMIT, "2d": 70, "1d": 9, "lattice2d": C.LATTICE_LIMIT, "clustered2d": C.CLUSTERED_LIMIT,
+          "line": C.LINE_LIMIT}
 
 
-def tree(name, order, env=None, kernel=(0, 1.0, 1.0), epsilon=1e-7):
+def tree(name, order, env=None, kernel=(0, 1.0, 1.0), epsilon=1e-7, compression=C.ACA):
     """(handle, geometry) of a cloud, built once per configuration; the populations tree stores its empty cells."""
     def make():
-        t = C.make_tree(cloud(name), order, LIMITS[name], env=env, kernel=kernel, sparse=name != "populations", epsilon=epsilon)
+        t = C.make_tree(cloud(name), order, LIMITS[name], env=env, kernel=kernel, sparse=name != "populations", epsilon=epsilon,
+                        compression=compression)
         geo = R.Geometry(t)
         if name == "populations":
             C.assert_populations(t, C.populations_cloud()[1])
         if name == "lattice8":
             C.assert_lattice8(t, geo)
+        if name == "lattice2d":
+            C.assert_lattice2d(t, geo)
+        if name == "line":
+            C.assert_line(t, geo)
         return t, geo
-    return cached(("tree", name, order, tuple(sorted((env or {}).items())), kernel, epsilon), make)
+    return cached(("tree", name, order, tuple(sorted((env or {}).items())), kernel, epsilon, compression), make)
 
 
 # ------------------------------------------------------------------ P2M
