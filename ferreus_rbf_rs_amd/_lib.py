@@ -155,6 +155,7 @@ SIGNATURES = {
     "bbfmm_debug_m2l_pairs_axes_stage2": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
     "bbfmm_debug_m2l_table_digests": (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_i32, c_p]),
     "bbfmm_debug_m2l_s2_plan": (ctypes.c_int, [c_p, c_p]),
+    "bbfmm_debug_wx_jobs": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_debug_m2l_s2_last_ksplit": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_debug_leaf_runs": (ctypes.c_int, [c_p, c_p]),
     "bbfmm_debug_group_state": (ctypes.c_int, [c_p, c_p, c_i64]),

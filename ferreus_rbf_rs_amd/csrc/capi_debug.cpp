@@ -241,6 +241,12 @@ int bbfmm_debug_m2l_s2_plan(const bbfmm_handle *h, int32_t *out) {
     return BBFMM_OK;
 }
 
+// The W / X jobs of the resident target set (FmmTree::debug_wx_jobs).
+int bbfmm_debug_wx_jobs(const bbfmm_handle *h, int32_t *out) {
+    if (!h || !out) return BBFMM_BAD_ARGUMENT;
+    return h->tree.debug_wx_jobs(out);
+}
+
 // Digests of the integer M2L tables, one per family, and the per-level flop counts (FmmTree::debug_m2l_table_digests).
 int bbfmm_debug_m2l_table_digests(const bbfmm_handle *h, uint64_t *digests, int32_t cap, int32_t *n_out, double *flops_level,
                                   int32_t flops_cap, int32_t *n_levels_out) {

@@ -93,6 +93,66 @@ int FmmTree::build_l2p_runs(TargetSet *ts, const std::vector<int32_t> &jc, const
     return BBFMM_OK;
 }
 
+// The jobs of the fused M2P + P2L pass for the candidate leaves `cand` (see build_sym_runs): chunk jobs (wtb, wte, wr) and
+// whole-leaf jobs (ltb2, lte2, lr2), in leaf order.  Host work alone: debug_wx_jobs plans a host-only handle with it.
+void FmmTree::plan_wx_jobs(const std::vector<int32_t> &cand, bool whole, int64_t pb, int64_t pe,
+                           const std::vector<uint8_t> *part_active, std::vector<int32_t> *wtb, std::vector<int32_t> *wte,
+                           std::vector<int64_t> *wr, std::vector<int32_t> *ltb2, std::vector<int32_t> *lte2,
+                           std::vector<int64_t> *lr2) const {
+    const HostTree &t = tree_;
+    std::vector<int32_t> wx_leaves; // the leaves that take part
+    for (size_t j = 0; j < cand.size(); ++j) {
+        const int32_t c = cand[j];
+        if (t.w.ptr[c + 1] == t.w.ptr[c]) continue;
+        if (!whole) {
+            const bool own = t.pt_begin[c] >= pb && t.pt_begin[c] < pe;
+            bool feeds = false;
+            for (int64_t q = t.w.ptr[c]; q < t.w.ptr[c + 1] && !own && !feeds; ++q) feeds = (*part_active)[static_cast<size_t>(t.w.idx[q])] != 0;
+            if (!own && !feeds) continue;
+        }
+        // jobs = (row chunk of the leaf) x (chunk of its W list): a nearly uniform tree has a few dozen coarse
+        // leaves with long W lists (10M uniform points: 90 leaves of 250 points, about 100 W cells each), and whole-list
+        // jobs would be a handful of long workgroups (0.96 ms for 0.6e9 kernel evaluations); both sums are atomic
+        wx_leaves.push_back(c);
+        const int64_t max_rows_wx = wx_sym_rows_per_job(), max_cells_wx = 16;
+        const int64_t a0 = t.pt_begin[c], na = t.pt_end[c] - a0, nj = (na + max_rows_wx - 1) / max_rows_wx;
+        const int64_t w0 = t.w.ptr[c], nw = t.w.ptr[c + 1] - w0, nwj = (nw + max_cells_wx - 1) / max_cells_wx;
+        for (int64_t i = 0; i < nj; ++i)
+            for (int64_t jw = 0; jw < nwj; ++jw) {
+                wtb->push_back(static_cast<int32_t>(a0 + na * i / nj));
+                wte->push_back(static_cast<int32_t>(a0 + na * (i + 1) / nj));
+                wr->push_back(w0 + nw * jw / nwj);
+                wr->push_back(w0 + nw * (jw + 1) / nwj);
+            }
+    }
+    // whole-leaf jobs for one rhs: all rows of a leaf (bigger ones than the kernel takes in equal parts) x a chunk of its W
+    // list; the chunks shrink until there are a few jobs per CU (a nearly uniform tree has a few dozen leaves with long lists)
+    const int64_t leaf_rows_wx = wx_sym3_rows_per_job();
+    if (leaf_rows_wx > 0 && !wx_leaves.empty()) {
+        int64_t cells_per_job = 16;
+        for (;;) {
+            int64_t nj_total = 0;
+            for (int32_t c : wx_leaves) {
+                const int64_t na = t.pt_end[c] - t.pt_begin[c], nw = t.w.ptr[c + 1] - t.w.ptr[c];
+                nj_total += ((na + leaf_rows_wx - 1) / leaf_rows_wx) * ((nw + cells_per_job - 1) / cells_per_job);
+            }
+            if (nj_total >= 4 * static_cast<int64_t>(n_cu_) || cells_per_job == 1) break;
+            cells_per_job = std::max<int64_t>(1, cells_per_job / 2);
+        }
+        for (int32_t c : wx_leaves) {
+            const int64_t a0 = t.pt_begin[c], na = t.pt_end[c] - a0, nj = (na + leaf_rows_wx - 1) / leaf_rows_wx;
+            const int64_t w0 = t.w.ptr[c], nw = t.w.ptr[c + 1] - w0, nwj = (nw + cells_per_job - 1) / cells_per_job;
+            for (int64_t i = 0; i < nj; ++i)
+                for (int64_t jw = 0; jw < nwj; ++jw) {
+                    ltb2->push_back(static_cast<int32_t>(a0 + na * i / nj));
+                    lte2->push_back(static_cast<int32_t>(a0 + na * (i + 1) / nj));
+                    lr2->push_back(w0 + nw * jw / nwj);
+                    lr2->push_back(w0 + nw * (jw + 1) / nwj);
+                }
+        }
+    }
+}
+
 // Run lists of the symmetric P2P for the target leaves `job_cells` (in job order) when the targets are the
 // sorted sources [pb, pe): the leaf itself and the U points outside [pb, pe) one-sided, the U points after
 // the leaf inside the range two-sided; the U points before the leaf inside the range belong to those leaves'
@@ -208,58 +268,7 @@ int FmmTree::build_sym_runs(TargetSet *ts, const std::vector<int32_t> &job_cells
         // window).  X = W^T (linear_tree.rs:388-392), so this covers the X lists of the partition's cells.
         std::vector<int32_t> wtb, wte, ltb2, lte2;
         std::vector<int64_t> wr, lr2;
-        std::vector<int32_t> wx_leaves; // the leaves that take part
-        const std::vector<int32_t> &cand = whole ? job_cells : src_leaves_;
-        for (size_t j = 0; j < cand.size(); ++j) {
-            const int32_t c = cand[j];
-            if (t.w.ptr[c + 1] == t.w.ptr[c]) continue;
-            if (!whole) {
-                const bool own = t.pt_begin[c] >= pb && t.pt_begin[c] < pe;
-                bool feeds = false;
-                for (int64_t q = t.w.ptr[c]; q < t.w.ptr[c + 1] && !own && !feeds; ++q) feeds = (*part_active)[static_cast<size_t>(t.w.idx[q])] != 0;
-                if (!own && !feeds) continue;
-            }
-            // jobs = (row chunk of the leaf) x (chunk of its W list): a nearly uniform tree has a few dozen coarse
-            // leaves with long W lists (10M uniform points: 90 leaves of 250 points, about 100 W cells each), and whole-list
-            // jobs would be a handful of long workgroups (0.96 ms for 0.6e9 kernel evaluations); both sums are atomic
-            wx_leaves.push_back(c);
-            const int64_t max_rows_wx = wx_sym_rows_per_job(), max_cells_wx = 16;
-            const int64_t a0 = t.pt_begin[c], na = t.pt_end[c] - a0, nj = (na + max_rows_wx - 1) / max_rows_wx;
-            const int64_t w0 = t.w.ptr[c], nw = t.w.ptr[c + 1] - w0, nwj = (nw + max_cells_wx - 1) / max_cells_wx;
-            for (int64_t i = 0; i < nj; ++i)
-                for (int64_t jw = 0; jw < nwj; ++jw) {
-                    wtb.push_back(static_cast<int32_t>(a0 + na * i / nj));
-                    wte.push_back(static_cast<int32_t>(a0 + na * (i + 1) / nj));
-                    wr.push_back(w0 + nw * jw / nwj);
-                    wr.push_back(w0 + nw * (jw + 1) / nwj);
-                }
-        }
-        // whole-leaf jobs for one rhs: all rows of a leaf (bigger ones than the kernel takes in equal parts) x a chunk of its W
-        // list; the chunks shrink until there are a few jobs per CU (a nearly uniform tree has a few dozen leaves with long lists)
-        const int64_t leaf_rows_wx = wx_sym3_rows_per_job();
-        if (leaf_rows_wx > 0 && !wx_leaves.empty()) {
-            int64_t cells_per_job = 16;
-            for (;;) {
-                int64_t nj_total = 0;
-                for (int32_t c : wx_leaves) {
-                    const int64_t na = t.pt_end[c] - t.pt_begin[c], nw = t.w.ptr[c + 1] - t.w.ptr[c];
-                    nj_total += ((na + leaf_rows_wx - 1) / leaf_rows_wx) * ((nw + cells_per_job - 1) / cells_per_job);
-                }
-                if (nj_total >= 4 * static_cast<int64_t>(n_cu_) || cells_per_job == 1) break;
-                cells_per_job = std::max<int64_t>(1, cells_per_job / 2);
-            }
-            for (int32_t c : wx_leaves) {
-                const int64_t a0 = t.pt_begin[c], na = t.pt_end[c] - a0, nj = (na + leaf_rows_wx - 1) / leaf_rows_wx;
-                const int64_t w0 = t.w.ptr[c], nw = t.w.ptr[c + 1] - w0, nwj = (nw + cells_per_job - 1) / cells_per_job;
-                for (int64_t i = 0; i < nj; ++i)
-                    for (int64_t jw = 0; jw < nwj; ++jw) {
-                        ltb2.push_back(static_cast<int32_t>(a0 + na * i / nj));
-                        lte2.push_back(static_cast<int32_t>(a0 + na * (i + 1) / nj));
-                        lr2.push_back(w0 + nw * jw / nwj);
-                        lr2.push_back(w0 + nw * (jw + 1) / nwj);
-                    }
-            }
-        }
+        plan_wx_jobs(whole ? job_cells : src_leaves_, whole, pb, pe, part_active, &wtb, &wte, &wr, &ltb2, &lte2, &lr2);
         auto wx_longest_first = [&](std::vector<int32_t> *b, std::vector<int32_t> *e, std::vector<int64_t> *rg) { // rows x W cells
             const size_t n = b->size();
             std::vector<int32_t> perm(n), b2(n), e2(n);
@@ -1205,6 +1214,34 @@ int FmmTree::debug_partition_upward_counts(int64_t *counts_out, uint8_t *reads_o
     info_out[1] = dp.coarse_cells;
     info_out[2] = static_cast<int64_t>(dp.up_leaves_h.size());
     info_out[3] = n_parents;
+    return BBFMM_OK;
+}
+
+// Test hook: the W / X jobs of the resident target set (see the header).  The lists are planned again on the host with the
+// functions that planned them at create time; a handle with a device must find the job counts it uploaded.
+int FmmTree::debug_wx_jobs(int32_t out[8]) const {
+    const HostTree &t = tree_;
+    std::vector<int32_t> mtb, mte, wtb, wte, ltb, lte;
+    std::vector<int64_t> mb, me, wr, lr;
+    for (int32_t c : src_leaves_)
+        add_w_jobs(t, c, static_cast<int32_t>(t.pt_begin[c]), static_cast<int32_t>(t.pt_end[c]), &mtb, &mte, &mb, &me, deterministic_);
+    if (!t.w.idx.empty() && static_cast<int64_t>(t.n_cells()) * round_up(ops_.n, 32) < (int64_t(1) << 31))
+        plan_wx_jobs(src_leaves_, true, 0, t.n_points, nullptr, &wtb, &wte, &wr, &ltb, &lte, &lr);
+    std::fill(out, out + 8, 0);
+    out[0] = static_cast<int32_t>(mtb.size());
+    out[1] = static_cast<int32_t>(wtb.size());
+    out[2] = static_cast<int32_t>(ltb.size());
+    for (size_t i = 0; i < wtb.size(); ++i) {
+        out[3] = std::max(out[3], wte[i] - wtb[i]);
+        out[5] = std::max(out[5], static_cast<int32_t>(wr[2 * i + 1] - wr[2 * i]));
+    }
+    for (size_t i = 0; i < ltb.size(); ++i) {
+        out[4] = std::max(out[4], lte[i] - ltb[i]);
+        out[6] = std::max(out[6], static_cast<int32_t>(lr[2 * i + 1] - lr[2 * i]));
+    }
+    for (size_t i = 0; i < mtb.size(); ++i) out[7] = std::max(out[7], static_cast<int32_t>(me[i] - mb[i]));
+    if (!host_only_ && (out[0] != src_targets_.n_w_jobs || out[1] != src_targets_.n_wx_jobs || out[2] != src_targets_.n_wxl_jobs))
+        return BBFMM_UNSUPPORTED; // the plan on the device is not the one restated here
     return BBFMM_OK;
 }
 

@@ -307,6 +307,11 @@ class FmmTree {
     // Test hook: the kernel instance of stage 2 in the parity basis, out = {ga, gb, ce, co, ya, yb} of m2l_s2_plan_ (ya = yb =
     // 0 with one axis); all zeros when the handle has no stage-2 pairs.  Made on the host: host-only handles answer too.
     void debug_m2l_s2_plan(int32_t out[6]) const;
+    // Test hook: the W / X jobs of the resident target set (targets = sources).  out = {M2P jobs, chunk jobs and whole-leaf jobs
+    // of the fused pass; the largest row count of a chunk job and of a whole-leaf job; the largest W-cell count of a chunk job,
+    // of a whole-leaf job and of an M2P job}.  Planned on the host: host-only handles answer too (with the default count of
+    // compute units, on which the W chunks of the whole-leaf jobs depend).
+    int debug_wx_jobs(int32_t out[8]) const;
     // Test hook: one 64-bit FNV-1a digest per family of the integer tables build_m2l_tables() produces, for host-only handles
     // (upload() releases cslot and the zero lists of the others).  Every vector is hashed as its length, then its elements;
     // no floating-point value is hashed.  The families, in the order of *out:
@@ -409,6 +414,9 @@ class FmmTree {
                               std::vector<int32_t> *leaves_out);
     int build_source_target_set();
     int build_l2p_runs(TargetSet *ts, const std::vector<int32_t> &jc, const std::vector<int32_t> &tb, const std::vector<int32_t> &te);
+    void plan_wx_jobs(const std::vector<int32_t> &cand, bool whole, int64_t pb, int64_t pe, const std::vector<uint8_t> *part_active,
+                      std::vector<int32_t> *wtb, std::vector<int32_t> *wte, std::vector<int64_t> *wr, std::vector<int32_t> *ltb2,
+                      std::vector<int32_t> *lte2, std::vector<int64_t> *lr2) const;
     int build_sym_runs(TargetSet *ts, const std::vector<int32_t> &job_cells, int64_t pb, int64_t pe, const std::vector<uint8_t> *part_active = nullptr);
     void free_target_set(TargetSet *ts);
     hipError_t columns_to_host(double *dst, int64_t ld, const double *d_src, int64_t m, int ncols);

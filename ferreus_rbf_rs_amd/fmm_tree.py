@@ -787,6 +787,17 @@ class FmmTree:
         self._raise(self._lib.bbfmm_debug_m2l_s2_plan(self._h, out))
         return tuple(int(v) for v in out)
 
+    WX_JOB_FIELDS = ("n_w_jobs", "n_wx_jobs", "n_wxl_jobs", "max_rows_wx", "max_rows_wxl", "max_cells_wx", "max_cells_wxl",
+                     "max_cells_w")
+
+    def debug_wx_jobs(self) -> dict:
+        """The W / X jobs of the resident target set (targets = sources): the number of M2P jobs, of chunk jobs and of
+        whole-leaf jobs of the fused M2P + P2L pass, the largest row count of a chunk job and of a whole-leaf job, the largest
+        W-cell count of a chunk job, of a whole-leaf job and of an M2P job.  Planned on the host: host_only handles answer."""
+        out = (ctypes.c_int32 * 8)()
+        self._raise(self._lib.bbfmm_debug_wx_jobs(self._h, out))
+        return {k: int(v) for k, v in zip(self.WX_JOB_FIELDS, out)}
+
     def debug_m2l_s2_last_ksplit(self) -> int:
         """Parts into which this handle's most recent parity-basis stage-2 launch split the contraction (0: none yet)."""
         ks = ctypes.c_int32()

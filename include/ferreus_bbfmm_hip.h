@@ -777,6 +777,11 @@ int bbfmm_debug_m2l_pairs_axes_stage2(const bbfmm_handle *h, int32_t *out, int64
  * (ga, gb), chunks per half (ce, co), and with two axes the groups of a chunk that belong to its y-even part (ya, yb; 0, 0
  * with one axis).  All zeros when the handle has no stage-2 pairs.  Made on the host: BBFMM_FLAG_HOST_ONLY handles answer. */
 int bbfmm_debug_m2l_s2_plan(const bbfmm_handle *h, int32_t *out);
+/* The W / X jobs of the resident target set (targets = sources): out[8] = the number of M2P jobs, of chunk jobs and of
+ * whole-leaf jobs of the fused M2P + P2L pass; the largest row count of a chunk job and of a whole-leaf job; the largest
+ * W-cell count of a chunk job, of a whole-leaf job and of an M2P job.  Planned on the host: BBFMM_FLAG_HOST_ONLY handles
+ * answer (with the default count of compute units).  BBFMM_UNSUPPORTED if a handle with a device uploaded other counts. */
+int bbfmm_debug_wx_jobs(const bbfmm_handle *h, int32_t *out);
 /* One 64-bit FNV-1a digest per family of the integer M2L tables (FmmTree::debug_m2l_table_digests lists the families and
  * their order), for BBFMM_FLAG_HOST_ONLY handles: *n_out = number of families, digests (capacity cap, may be NULL)
  * receives the first min(cap, *n_out).  flops_level (capacity flops_cap, may be NULL) receives the M2L flop count of

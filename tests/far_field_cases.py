@@ -1,6 +1,6 @@
 """The clouds, weights and handles of the far-field tests: the smallest at which each pass can go wrong.  A plain helper
-module (no tests); tests/test_far_field_reference_host.py, tests/test_gpu_far_field_passes.py and
-tests/test_gpu_far_field_orders.py share it."""
+module (no tests); tests/test_far_field_reference_host.py, tests/test_gpu_far_field_passes.py,
+tests/test_gpu_far_field_orders.py and tests/test_gpu_wx_passes.py share it."""
 import contextlib
 import os
 
@@ -290,6 +290,138 @@ def assert_every_vector_is_live(geo, w):
     hit = set(geo.v_tidx[(at == levels[-1]) & live[geo.v_src]].tolist())
     assert hit == every, (levels[-1], len(hit), len(every))
     return levels[-1]
+
+
+# ---- two-level clouds: the W lists of level-1 leaves
+# The unit cube (square, interval) is split once; the octants of `refined` hold more points than the limit (the largest
+# prescribed population) and split once more into level-2 leaves that all hold points, the others are level-1 leaves with
+# the prescribed populations.  Every octant touches every other one, so a level-1 leaf has in its W list the children of
+# each refined octant that do not touch it: 4 of a face neighbour, 6 of an edge neighbour, 7 of a vertex neighbour (2 and 3
+# in two dimensions, the far child in one).  A level-1 cell has no V list; with more than one refined octant the children
+# of different refined octants are in each other's V lists (M2L is live between level-2 cells, never into a level-1 leaf).
+# Octant o: bit a = the upper half along axis a.  {dimension: {name: (refined octants, {octant: population})}}
+TWO_LEVEL = {
+    3: {"w4-7": ((7,), {0: 1, 1: 2, 2: 7, 3: 8, 4: 9, 5: 47, 6: 48}),                   # W lists of 7, 6, 6, 4, 6, 4, 4
+        "w8-12": ((0, 3), {1: 49, 2: 63, 4: 64, 5: 65, 6: 66, 7: 33}),                  # 8, 8, 11, 12, 12, 11
+        "w14-19": ((1, 3, 5), {0: 95, 2: 96, 4: 97, 6: 127, 7: 128}),                   # 16, 17, 17, 19, 14
+        "w14-19-small": ((1, 3, 5), {0: 66, 2: 1, 4: 9, 6: 47, 7: 8}),
+        "w10": ((0, 7), {1: 129, 2: 255, 3: 256, 4: 257, 5: 511, 6: 512}),              # 10 throughout
+        "w8-12-big": ((0, 3), {1: 513, 2: 257, 4: 129, 5: 66, 6: 9, 7: 2})},
+    2: {"w2-3": ((3,), {0: 49, 1: 257, 2: 8}),                                          # 3, 2, 2
+        "w7": ((1, 2, 3), {0: 513}),
+        "w4-5": ((0, 3), {1: 66, 2: 129})},                                             # 2 + 2 = 4 each
+    1: {"low": ((1,), {0: 130}), "high": ((0,), {1: 513})}}
+# what the 3-D layouts must show between them (tests/test_far_field_reference_host.py asserts it): the waves of a job (8),
+# the rows of a chunk job (48) and of a whole-leaf job (256), 64-lane batches, the source tiles and plan_targets passes
+TWO_LEVEL_POPULATIONS = {1, 2, 7, 8, 9, 47, 48, 49, 63, 64, 65, 66, 95, 96, 97, 127, 128, 129, 255, 256, 257, 511, 512, 513}
+W_CELLS_BY_BITS = {3: {1: 4, 2: 6, 3: 7}, 2: {1: 2, 2: 3}, 1: {1: 1}}
+SMALL_TWO_LEVEL = ("w4-7", "w8-12", "w14-19-small")                  # 3-D layouts whose level-1 leaves hold at most 66 points
+
+
+def two_level_limit(d, name):
+    return max(TWO_LEVEL[d][name][1].values())
+
+
+def two_level_w_length(d, name, octant):
+    """The W-list length of the level-1 leaf in `octant`, by the count above."""
+    return sum(W_CELLS_BY_BITS[d][bin(octant ^ q).count("1")] for q in TWO_LEVEL[d][name][0])
+
+
+def expected_wx_jobs(d, name, n_cu=256):
+    """debug_wx_jobs() restated from the layout: add_w_jobs cuts a W list at 8 cells; a chunk job has at most 48 rows and 16
+    cells, a whole-leaf job at most 256 rows, both in equal parts; the cells of a whole-leaf job halve from 16 until there are
+    four jobs per compute unit, down to one cell on trees this small."""
+    leaves = [(n, two_level_w_length(d, name, o)) for o, n in TWO_LEVEL[d][name][1].items()]
+    ceil = lambda a, b: -(-a // b)
+    part = lambda n, k: max((n * (i + 1)) // k - (n * i) // k for i in range(k))
+    cells = 16
+    while cells > 1 and sum(ceil(n, 256) * ceil(w, cells) for n, w in leaves) < 4 * n_cu:
+        cells //= 2
+    return {"n_w_jobs": sum(ceil(w, 8) for _, w in leaves),
+            "n_wx_jobs": sum(ceil(n, 48) * ceil(w, 16) for n, w in leaves),
+            "n_wxl_jobs": sum(ceil(n, 256) * ceil(w, cells) for n, w in leaves),
+            "max_rows_wx": max(part(n, ceil(n, 48)) for n, _ in leaves),
+            "max_rows_wxl": max(part(n, ceil(n, 256)) for n, _ in leaves),
+            "max_cells_wx": max(part(w, ceil(w, 16)) for _, w in leaves),
+            "max_cells_wxl": max(part(w, ceil(w, cells)) for _, w in leaves),
+            "max_cells_w": max(min(w, 8) for _, w in leaves)}
+
+
+def two_level_cloud(d, name):
+    """Points on the 2^-30 grid, strictly inside their cells of the root box of centre 0.5 and radius 0.501."""
+    refined, pops = TWO_LEVEL[d][name]
+    assert sorted(refined + tuple(pops)) == list(range(1 << d)) and len(set(pops.values())) == len(pops)
+    limit = two_level_limit(d, name)
+    assert limit >= 2
+    rng = np.random.default_rng([d, limit, len(name), sum(pops.values())])
+    radius = 0.501
+    pts = []
+    for o in range(1 << d):
+        lo = 0.5 - radius + radius * np.array([(o >> a) & 1 for a in range(d)])
+        if o in pops:
+            boxes = [(lo, radius, pops[o])]
+        else:                                                         # limit + 2^d points: more than the limit, no child above it
+            total, nch = limit + (1 << d), 1 << d
+            boxes = [(lo + radius / 2 * np.array([(ch >> a) & 1 for a in range(d)]), radius / 2,
+                      total // nch + (1 if ch < total % nch else 0)) for ch in range(nch)]
+            assert all(1 <= b[2] <= limit for b in boxes)
+        for blo, side, count in boxes:
+            pts.append(on_grid(blo + side * (0.06 + 0.88 * rng.random((count, d)))))
+    pts = np.concatenate(pts)
+    pts = pts[rng.permutation(len(pts))]
+    assert pts.min() > 0 and pts.max() < 1 and len(np.unique(pts, axis=0)) == len(pts)
+    return np.ascontiguousarray(pts)
+
+
+def assert_two_level(t, geo, d, name):
+    """From the handle: depth 2, the level-1 leaves with their populations and W-list lengths, the refined octants with 2^d
+    leaves that hold points, no V list at level 1, X = W^T live.  Returns {octant: cell} of the level-1 leaves."""
+    refined, pops = TWO_LEVEL[d][name]
+    s = t.stats()
+    assert s.depth == 2 and s.n_x == s.n_w > 0, (s.depth, s.n_x, s.n_w)
+    octant_of = {c: int(sum(int(geo.anchor[c][a]) << a for a in range(d))) for c in range(geo.C) if geo.level[c] == 1}
+    assert sorted(octant_of.values()) == list(range(1 << d))
+    n_pts, n_w, n_v = np.diff(geo.src_ptr), np.diff(geo.lists["W"][0]), np.diff(geo.lists["V"][0])
+    leaves = {}
+    for c, o in octant_of.items():
+        assert n_v[c] == 0
+        if o in pops:
+            assert geo.is_leaf[c] and n_pts[c] == pops[o] and n_w[c] == two_level_w_length(d, name, o), (o, n_pts[c], n_w[c])
+            leaves[o] = c
+        else:
+            ch = geo.children[c]
+            assert not geo.is_leaf[c] and len(ch) == 1 << d and geo.is_leaf[ch].all()
+            assert (n_pts[ch] > 0).all() and (n_pts[ch] <= two_level_limit(d, name)).all() and (n_w[ch] == 0).all()
+    assert n_w.sum() == sum(n_w[c] for c in leaves.values())       # no other cell has a W list
+    return leaves
+
+
+def inside_copies(geo, leaf, pts, count, seed):
+    """`count` copies of points of a leaf displaced per axis by grid multiples of 1/64 to 1/16 of the leaf's side and kept
+    at least an eighth of the side inside it (count rows, cycling through the points)."""
+    rng = np.random.default_rng(seed)
+    rows = np.arange(count) % len(pts)
+    side = geo.lengths[leaf]
+    off = np.floor(rng.uniform(side / 64, side / 16, (count, geo.d)) / GRID) * GRID * rng.choice([-1.0, 1.0], (count, geo.d))
+    lo, hi = geo.centres[leaf] - side / 2, geo.centres[leaf] + side / 2
+    out = on_grid(np.clip(pts[rows] + off, lo + side / 8, hi - side / 8))
+    assert (out > lo).all() and (out < hi).all()
+    return out
+
+
+def w_cell_weights(geo, n, leaf, K, seed):
+    """Signed weights on the points under the cells of the W list of `leaf`, zero elsewhere."""
+    wp, wi = geo.lists["W"]
+    w = np.zeros((n, K))
+    rng = np.random.default_rng(seed)
+    stack = [int(c) for c in wi[wp[leaf]:wp[leaf + 1]]]
+    while stack:
+        c = stack.pop()
+        stack += [int(x) for x in geo.children[c]]
+        rows = geo.src_idx[geo.src_ptr[c]:geo.src_ptr[c + 1]]
+        if geo.is_leaf[c]:
+            w[rows] = rng.standard_normal((len(rows), K))
+    return w
 
 
 def dense_weights(n, K, seed):

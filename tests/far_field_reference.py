@@ -1,4 +1,4 @@
-"""The five far-field passes (P2M, M2M, M2L, L2L, L2P) and P2L in extended precision (numpy longdouble), restated from
+"""The five far-field passes (P2M, M2M, M2L, L2L, L2P), P2L and M2P in extended precision (numpy longdouble), restated from
 their mathematical definitions, with the magnitude sums and the derived rounding bounds the cell-by-cell tests need.  A
 plain helper module (no tests), the far-field sibling of tests/kernel_reference.py.
 
@@ -49,6 +49,25 @@ throughout) and s_fac (the same with one factor at a time replaced by 1, summed 
   P2L   err_j <= u [(n_src + a + 4) s_phi_j + (b + 4 + 8 g) s_arg_j], (a, b) = kernel_pointwise.sum_budget and s_phi,
         s_arg the sums of kernel_reference.Dense (as test_gpu_pair_kernels.py bounds a pair sum); g = max |node
         coordinate| / len covers the rounding of the node positions centre + (len / 2) node (see p2l).
+  M2P   the mirror image of P2L: the sources are the Chebyshev nodes of the cells of the leaf's W list, with the device's
+        M[k, cell, :n] as weights, the targets are points of the leaf.  Per target and right-hand side
+        err_t <= u [(N + a + 4) s_phi_t + (b + 4 + 8 g) s_arg_t]
+        N = the nodes of the whole W list (n per cell): the product with the weight and a sum of N terms in ANY order --
+        m2p_kernel's slices, the tiles of 512 (DIRECT_TILE) or of 768 / 384 columns of the fused kernels, the waves of a
+        job and the atomic additions of the jobs that share a target are one sum of those N terms, regrouped.  (a, b) =
+        kernel_pointwise.sum_budget; 4: the differences, their squares and the sum that form r^2.  g = the largest over the
+        W cells of max |node coordinate| / len(cell).  A node coordinate c + (len / 2) node_i is formed on the device from
+        the double node (one rounding of the long-double node), one product and one sum (or one fused step): its absolute
+        error is at most u (len + |coordinate|) <= u len (1 + g).  A W cell is a descendant of a colleague of the leaf that
+        does not touch the leaf, so every target is at least len(cell) away from every node of it: the relative change of
+        r^2 is at most 2 sqrt(d) u (1 + g) <= 3.47 u (1 + g), which is <= 8 u g, the term p2l carries, as soon as g >= 0.77.
+        Every cell lies in the positive orthant (up to the root's margin of 1e-3), where max |coordinate| >= (len / 2) (1 +
+        cos(pi / 4)) = 0.85 len: m2p asserts g >= 0.8.
+        A gradient component sum_j w_j f_tj (x_t - x_j)_a takes the form tests/test_gpu_pair_kernels.py uses for pair
+        gradients, u [(N + a_f + 4) s_f + (b_f + 4 + 8 g) s_xf] with s_f = sum |w| |f| |dx_a|, s_xf = sum |w| |r^2 f'| |dx_a| and
+        (a_f, b_f) the budget of the factor path, PLUS u s_pos, s_pos = sum_j |w_j| |f_tj| (len + max |coordinate|) of j's cell:
+        the absolute error of the node position enters dx_a itself, which may be far smaller than len (a pair sum has
+        exact differences on the grid; this one does not).  The values of a gradient call use the value_g budget.
 """
 import numpy as np
 
@@ -346,6 +365,63 @@ def p2l(geo, kernel, pts, w, cell, where=1):
     return y.T, LD(U) * ((len(srcs) + a + 4) * s_phi + (b + 4 + 8 * g) * s_arg).T.max(axis=-1)
 
 
+# ------------------------------------------------------------------ M2P
+def cell_nodes(geo, cell):
+    """The Chebyshev nodes of a cell, (n, d) doubles in node-index order: centre + (len / 2) node formed in long double
+    from the doubles the handle exposes and rounded to double (as p2l forms its targets)."""
+    nd = np.stack(np.meshgrid(*[nodes(geo.p)] * geo.d, indexing="ij"), -1).reshape(-1, geo.d)
+    return (geo.centres[cell].astype(LD) + (LD(geo.lengths[cell]) / 2) * nd).astype(np.float64)
+
+
+class M2PMatrices:
+    """The kernel matrices of (targets in `leaf`) x (nodes of the cells of its W list), computed once: the sums for any
+    multipoles come from them.  Without gradients only the three matrices of the value path are kept."""
+
+    def __init__(self, geo, kernel, leaf, targets, where=1, gradients=False):
+        import kernel_pointwise as KP
+        import kernel_reference as KR
+        wp, wi = geo.lists["W"]
+        self.n, self.cells = geo.n, [int(c) for c in wi[wp[leaf]:wp[leaf + 1]]]
+        assert self.cells, "the leaf has no W list"
+        pos = [cell_nodes(geo, c) for c in self.cells]
+        self.g = max(float(np.abs(q).max() / geo.lengths[c]) for q, c in zip(pos, self.cells))
+        assert self.g >= 0.8                                          # the premise of the 8 g term (module docstring)
+        self.N = sum(len(q) for q in pos)
+        self.budget = {path: KP.sum_budget(where, kernel[0], path) for path in ("value", "value_g", "factor")}
+        D = KR.Dense(kernel[0], kernel[1], kernel[2], targets, np.concatenate(pos))
+        self.value, self.abs_value, self.abs_x_dvalue = D.value, D.abs_value, D.abs_x_dvalue
+        self.D = D if gradients else None
+        self.delta = np.concatenate([np.full(len(q), geo.lengths[c] + np.abs(q).max()) for q, c in zip(pos, self.cells)]).astype(LD)
+
+    def weights(self, M_dev):
+        return np.concatenate([np.asarray(M_dev[:, c, :self.n], dtype=np.float64).T for c in self.cells]).astype(LD)   # (N, K)
+
+    def _bound(self, path, s_main, s_arg):
+        a, b = self.budget[path]
+        return LD(U) * ((self.N + a + 4) * s_main + (b + 4 + 8 * self.g) * s_arg)
+
+    def values(self, M_dev, rows=slice(None)):
+        """y (m, K) and its bound at the targets `rows`."""
+        w = self.weights(M_dev)
+        aw = np.abs(w)
+        return self.value[rows] @ w, self._bound("value", self.abs_value[rows] @ aw, self.abs_x_dvalue[rows] @ aw)
+
+    def gradients(self, M_dev):
+        """(values, their bound under the value_g budget, gradients (m, K, d), their bound)."""
+        w = self.weights(M_dev)
+        y, gr, s_phi, s_arg, s_f, s_xf = self.D.grad_sums(w)
+        s_pos = np.abs(self.D.factor) @ (np.abs(w) * self.delta[:, None])
+        return y, self._bound("value_g", s_phi, s_arg), gr, self._bound("factor", s_f, s_xf) + LD(U) * s_pos[:, :, None]
+
+
+def m2p(geo, kernel, M_dev, leaf, targets, with_grads=False, where=1):
+    """y (m, K) and its bound (m, K) of the W-list term at targets in `leaf`, from the device's M (K, C, n); with_grads
+    the values of a gradient call (the value_g budget) and their bound, then the gradients (m, K, d) and their bound.
+    kernel = (id, base_range, total_sill); where as in p2l."""
+    mats = M2PMatrices(geo, kernel, leaf, targets, where, gradients=with_grads)
+    return mats.gradients(M_dev) if with_grads else mats.values(M_dev)
+
+
 # ------------------------------------------------------------------ L2P
 def l2p(geo, L_dev, cell, targets, with_grads=False):
     """y (m, K) and its bound (m, K) for targets in leaf `cell` from the device's L (K, C, n); with_grads also the
@@ -435,10 +511,12 @@ def l2l_many(geo, xf, L_dev, cells, terms=None):
     return val, bnd
 
 
-def downward(geo, m2l, xf, M_dev, L_dev, cells, p2l_args=None, terms=None, skip=None, m2l_result=None):
+def downward(geo, m2l, xf, M_dev, L_dev, cells, p2l_args=None, terms=None, skip=None, m2l_result=None, p2l_cache=None):
     """What L holds in the listed cells after the downward pass, one step from its inputs: M2L of M_dev, plus L2L of the
     parent's L_dev, plus (p2l_args = (kernel, pts, w, where)) the X-list term.  Two dicts: ref[c] (K, n), bound[c] (K,).
-    m2l_result: m2l.apply(M_dev) computed before (it depends on M_dev alone)."""
+    m2l_result: m2l.apply(M_dev) computed before (it depends on M_dev alone).  p2l_cache: a dict that keeps the X-list terms
+    of the cells (they depend on the weights alone, column by column): w may then hold more columns than L_dev has
+    right-hand sides, every column is restated once and later calls take the first K."""
     cells = [int(c) for c in cells]
     Lm, S, R = m2l.apply(M_dev, cells=np.asarray(cells), skip=skip) if m2l_result is None else m2l_result
     bm = m2l.bound(S, R)
@@ -452,7 +530,12 @@ def downward(geo, m2l, xf, M_dev, L_dev, cells, p2l_args=None, terms=None, skip=
             b = b + lb[:, i]
         if p2l_args is not None and xp[c + 1] > xp[c]:
             kernel, pts, w, where = p2l_args
-            v, bp = p2l(geo, kernel, pts, w, c, where)
+            if p2l_cache is None:
+                v, bp = p2l(geo, kernel, pts, w, c, where)
+            else:
+                if c not in p2l_cache:
+                    p2l_cache[c] = p2l(geo, kernel, pts, w, c, where)
+                v, bp = (a[:L_dev.shape[0]] for a in p2l_cache[c])
             parts.append(v)
             b = b + bp
         ref[c] = sum(parts)

@@ -52,7 +52,8 @@ def test_schwarz_trace_hook_is_declared_and_bound():
 def test_m2l_debug_hooks_are_declared_and_bound():
     names = ["bbfmm_debug_m2l_variants", "bbfmm_debug_m2l_pairs", "bbfmm_debug_m2l_pairs_axes", "bbfmm_debug_m2l_pairs_stage2",
              "bbfmm_debug_m2l_pairs_axes_stage2", "bbfmm_debug_m2l_table_digests", "bbfmm_debug_m2l_s2_plan",
-             "bbfmm_debug_m2l_s2_last_ksplit", "bbfmm_debug_m2l_parity_len", "bbfmm_debug_apply_m2l_tables_host"]
+             "bbfmm_debug_m2l_s2_last_ksplit", "bbfmm_debug_m2l_parity_len", "bbfmm_debug_apply_m2l_tables_host",
+             "bbfmm_debug_wx_jobs"]
     lib = ctypes.CDLL(L.LIB_PATH)
     for n in names:
         assert n in declared_functions() and n in L.SIGNATURES and hasattr(lib, n), n

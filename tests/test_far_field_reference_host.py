@@ -1,7 +1,8 @@
 """The long-double restatement of the far-field passes (tests/far_field_reference.py) proven without a GPU: against the
 oracle's double passes cell by cell, against the host walk of the product's own M2L tables under every switch setting,
 its 1-D transfers against the product's dense M2M matrices, and the per-cell checker against altered data that the global
-norm lets through.  In three, two and one dimension, and with uncompressed operators.
+norm lets through.  In three, two and one dimension, and with uncompressed operators.  M2P: against the oracle's
+multipole-to-particle on the same multipoles, the altered-data proof of its bound, the two-level layouts and the job hook.
 
 THE STAGE-2 KERNEL INSTANCE OF EVERY ORDER (debug_m2l_s2_plan() of host-only handles; far_field_cases.S2_PLANS is this
 table as data and test_stage2_plan_of_every_order_is_the_table_of_the_docstring holds the two to the handles).  One axis:
@@ -340,3 +341,120 @@ def test_l2p_restatement_against_the_oracle_target_by_target(d, order):
         worst, worst_g = max(worst, float((e / yb).max())), max(worst_g, float((eg / gb).max()))
     print(f"L2P d = {d} order {order}: largest error / bound {worst:.3g}, gradients {worst_g:.3g}")
     assert worst > 0 and worst_g > 0
+
+
+# ------------------------------------------------------------------ M2P and the two-level clouds
+def test_the_two_level_layouts_show_every_required_population_and_w_list_length():
+    pops, lengths = set(), set()
+    for name, (refined, leaves) in C.TWO_LEVEL[3].items():
+        pops |= set(leaves.values())
+        lengths |= {C.two_level_w_length(3, name, o) for o in leaves}
+        assert sum(leaves.values()) + len(refined) * (max(leaves.values()) + 8) <= 3000
+    assert C.TWO_LEVEL_POPULATIONS <= pops, sorted(C.TWO_LEVEL_POPULATIONS - pops)
+    # the chunks of add_w_jobs (8) and of the fused jobs (16): below, at, between, at and above
+    assert 4 in lengths and 8 in lengths and lengths & set(range(9, 16)) and 16 in lengths and max(lengths) >= 17
+    assert all(max(C.TWO_LEVEL[3][name][1].values()) <= 66 for name in C.SMALL_TWO_LEVEL)
+    small = {C.two_level_w_length(3, name, o) for name in C.SMALL_TWO_LEVEL for o in C.TWO_LEVEL[3][name][1]}
+    assert {4, 8, 16, 17} <= small                                    # the layouts of the high orders show every chunk edge too
+
+
+@pytest.mark.parametrize("d,name", [(d, name) for d in (3, 2, 1) for name in C.TWO_LEVEL[d]])
+def test_two_level_geometry_and_jobs_from_host_only_handles(d, name):
+    pts = C.two_level_cloud(d, name)
+    t = C.make_tree(pts, 3, C.two_level_limit(d, name), host_only=True)
+    C.assert_two_level(t, R.Geometry(t), d, name)
+    assert t.debug_wx_jobs() == C.expected_wx_jobs(d, name)
+
+
+M2P_KERNELS = [(0, 1.0, 1.0), (3, 0.5, 0.4)]                        # LinearRbf; Spheroidal3 with both branches inside the cube
+
+
+def m2p_setup(d, name, order, kernel, K=2):
+    """(points, geometry, level-1 leaves, oracle tree with its multipoles of dense weights), built once."""
+    def make():
+        pts = C.two_level_cloud(d, name)
+        limit = C.two_level_limit(d, name)
+        t = C.make_tree(pts, order, limit, host_only=True, kernel=kernel)
+        geo = R.Geometry(t)
+        leaves = C.assert_two_level(t, geo, d, name)
+        r = O.FmmTree(pts, order, kernel[0], True, True, None, O.FmmParams(limit, C.ACA, 1e-7, 1024), base_range=kernel[1],
+                      total_sill=kernel[2])
+        inject_product_operators(t, r)
+        assert geo.keys == [int(k) for k in r.cell_keys]
+        w = C.dense_weights(len(pts), K, 61)
+        r.set_weights(w)
+        return pts, geo, leaves, r, w
+    return cached(("m2p setup", d, name, order, kernel, K), make)
+
+
+@pytest.mark.parametrize("kernel", M2P_KERNELS, ids=lambda k: f"kernel{k[0]}")
+@pytest.mark.parametrize("d,name,order", [(3, "w8-12", 4), (2, "w2-3", 5), (1, "low", 6)])
+def test_m2p_restatement_against_the_oracle_target_by_target(d, name, order, kernel):
+    """The oracle's leaf pass with only its M2P term (flags = 2) on its own multipoles: values and gradients to 1e-13 of the
+    largest value per leaf, and inside the bound of the module docstring (the host's kernel functions); targets in the
+    level-2 leaves, which have no W list, receive exact zeros."""
+    pts, geo, leaves, r, w = m2p_setup(d, name, order, kernel)
+    K = w.shape[1]
+    extra = [C.inside_copies(geo, c, pts[geo.src_idx[geo.src_ptr[c]:geo.src_ptr[c + 1]]], 12, 63 + o) for o, c in leaves.items()]
+    targets = np.ascontiguousarray(np.concatenate([pts] + extra))
+    y, g = r._eval(w, targets, True, flags=2)
+    z = r._eval(w, targets, False, flags=2)[0]
+    g = g.reshape(len(targets), K, d)
+    leaf_of = np.asarray(r._assign_targets(targets)[3])
+    level1 = np.isin(leaf_of, list(leaves.values()))
+    assert (y[~level1] == 0).all() and (g[~level1] == 0).all() and (~level1).any()
+    worst = [0.0, 0.0, 0.0]
+    for o, c in leaves.items():
+        rows = np.nonzero(leaf_of == c)[0]
+        assert len(rows) == C.TWO_LEVEL[d][name][1][o] + 12
+        yr, yb, gr, gb = R.m2p(geo, kernel, r.M, c, targets[rows], with_grads=True, where=0)
+        zr, zb = R.m2p(geo, kernel, r.M, c, targets[rows], where=0)
+        assert relerr(y[rows], yr) < 1e-13 and relerr(z[rows], zr) < 1e-13 and relerr(g[rows], gr) < 1e-13
+        for i, (got, ref, bound) in enumerate(((z[rows], zr, zb), (y[rows], yr, yb), (g[rows], gr, gb))):
+            ratio = float((np.abs(got.astype(LD) - ref) / bound).max())
+            worst[i] = max(worst[i], ratio)
+            assert ratio <= 1, (o, i, ratio)
+    print(f"M2P d = {d} {name} order {order} kernel {kernel[0]}: largest error / bound, values {worst[0]:.3g}, values of the "
+          f"gradient call {worst[1]:.3g}, gradients {worst[2]:.3g}")
+    assert min(worst) > 0
+
+
+@pytest.mark.parametrize("what", ["entry", "nodes", "cell", "rhs"])
+@pytest.mark.parametrize("kernel", M2P_KERNELS, ids=lambda k: f"kernel{k[0]}")
+def test_m2p_bound_catches_altered_multipoles(kernel, what):
+    """From the restatement alone: one entry of M scaled by 1 + 1e-9, two nodes of one W cell swapped, one W cell dropped,
+    right-hand sides 0 and 1 exchanged -- each moves every target it touches by more than its bound, in the values and in
+    the largest gradient component.  The leaf with the longest W list of the layout (19 cells): the largest N, the widest
+    bound."""
+    d, name, order = 3, "w14-19-small", 4
+    pts, geo, leaves, r, w = m2p_setup(d, name, order, kernel)
+    c = leaves[6]
+    wp, wi = geo.lists["W"]
+    cells = wi[wp[c]:wp[c + 1]]
+    assert len(cells) == 19
+    own = pts[geo.src_idx[geo.src_ptr[c]:geo.src_ptr[c + 1]]]
+    targets = np.concatenate([own, C.inside_copies(geo, c, own, 12, 65)])
+    M = np.array(r.M)
+    bad = M.copy()
+    touched = [0]
+    if what == "entry":                                               # the largest entry of one cell, first right-hand side
+        j = int(np.argmax(np.abs(M[0, cells[3]])))
+        bad[0, cells[3], j] *= 1 + 1e-9
+    elif what == "nodes":                                             # opposite corners of the cell
+        bad[0, cells[5], [0, geo.n - 1]] = M[0, cells[5], [geo.n - 1, 0]]
+    elif what == "cell":
+        bad[0, cells[-1]] = 0
+    else:
+        bad[[0, 1]] = M[[1, 0]]
+        touched = [0, 1]
+    assert not np.array_equal(bad, M)
+    yr, yb, gr, gb = R.m2p(geo, kernel, M, c, targets, with_grads=True)
+    ya, _, ga, _ = R.m2p(geo, kernel, bad, c, targets, with_grads=True)
+    zr, zb = R.m2p(geo, kernel, M, c, targets)
+    za = R.m2p(geo, kernel, bad, c, targets)[0]
+    ratios = [(np.abs(zr - za) / zb)[:, touched], (np.abs(yr - ya) / yb)[:, touched], (np.abs(gr - ga) / gb)[:, touched].max(axis=2)]
+    print(f"M2P altered ({what}, kernel {kernel[0]}): smallest |reference - altered| / bound over the targets: values "
+          f"{float(ratios[0].min()):.3g}, values of the gradient call {float(ratios[1].min()):.3g}, gradients {float(ratios[2].min()):.3g}")
+    assert all(float(q.min()) > 1 for q in ratios)
+    rest = [k for k in range(M.shape[0]) if k not in touched]
+    assert np.array_equal(zr[:, rest], za[:, rest])                  # the other right-hand sides are untouched

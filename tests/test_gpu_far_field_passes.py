@@ -113,18 +113,30 @@ def device_passes(t, w):
     return t.debug_get_coefficients("M", K), t.debug_get_coefficients("L", K)
 
 
-def check_downward(t, geo, key, pts, w, what, kernel=(0, 1.0, 1.0), cells=None, M=None, L=None):
+def check_downward(t, geo, key, pts, w, what, kernel=(0, 1.0, 1.0), cells=None, M=None, L=None, p2l_cache=None):
     """Every cell from level 2 down (or the listed ones) against M2L of the device's M plus L2L of the device's parent L
     plus the X-list term; returns the largest ratio and the number of (right-hand side, cell) pairs nothing reaches.  The
     M2L restatement depends on M alone, which the M2L switches do not touch: it is shared by the handles whose M agrees
-    bit for bit."""
+    bit for bit.  p2l_cache: see far_field_reference.downward; with listed cells it also keeps the M2L restatement of those
+    cells column by column (M2L treats the right-hand sides independently), so that calls which differ in the number of
+    right-hand sides, or handles whose M agrees bit for bit, restate a column once."""
     if M is None:
         M, L = device_passes(t, w)
     m2l = cached(("m2l operators", key), lambda: R.M2L(geo, t))
     full = cells is None
     cells = np.nonzero(geo.level >= 2)[0] if full else np.asarray(cells)
     res = cached(("m2l result", key, hashlib.sha256(M.tobytes()).hexdigest()), lambda: m2l.apply(M)) if full else None
-    ref, bound = R.downward(geo, m2l, R.Transfers(geo), M, L, cells, (kernel, pts, w, 1), m2l_result=res)
+    if p2l_cache is not None and not full:
+        live = (M != 0).any(axis=2)
+        assert (live == live[:1]).all()                               # the same sources are live in every column: one R for all
+        cols = []
+        for k in range(M.shape[0]):
+            col = ("m2l column", hashlib.sha256(M[k].tobytes()).hexdigest(), len(cells))
+            if col not in p2l_cache:
+                p2l_cache[col] = m2l.apply(M[k:k + 1], cells=cells)
+            cols.append(p2l_cache[col])
+        res = (np.concatenate([c[0] for c in cols]), np.concatenate([c[1] for c in cols]), cols[0][2])
+    ref, bound = R.downward(geo, m2l, R.Transfers(geo), M, L, cells, (kernel, pts, w, 1), m2l_result=res, p2l_cache=p2l_cache)
     untouched = [(k, c) for c in cells for k in range(L.shape[0]) if bound[c][k] == 0]   # nothing reaches them: exact zeros
     assert all((L[k, c] == 0).all() for k, c in untouched)
     ratio = R.check_cells("M2L + L2L", L, ref, bound, cells, what,
